@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- camera rays/sec of zoic's lens hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--precision fast|strict]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--precision fast|strict] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of camera_create_ray over one full frame of synthetic samples (config C3 by default:
 F_2.0_DOUBLE_GAUSS + image-based bokeh sampler, 3840x2160x16spp = 132,710,400 samples), samples already resident
-in HBM, rays written to HBM.  Rank 0 prints ONE JSON line (kept under 6 KB: what a field means is said once, in `notes`):
+in HBM, rays written to HBM.  Rank 0 prints ONE JSON line (kept under 6 KB: what a field means is said once, in `notes`).
+A plain run measures the headline only (value / ms_per_step, its roofline block and the frame buffers' placement);
+everything else below (parity, configs, sharded_frame, host_path, cpu_baseline, the clock / power reading, the N = 1
+frame_api / frame_layout legs and the N > 1 single-process frame) runs with --full:
 
   value / ms_per_step   N=1: the headline frame, K timed steps between barriers.  N>1 (one rank per GPU; `python bench.py --gpus N`
-                        without a launcher re-executes itself under torch.distributed.run): north_star's number -- the SAME
+                        without a launcher starts itself under torch.distributed.run): north_star's number -- the SAME
                         frame rendered ONCE per step in N ray-index slabs INCLUDING the RCCL gather of the 28-byte payload on
                         rank 0 (strong scaling); compute_only, the weak-scaling figure (every rank its own frame, no
                         collective), the root's ingest rate against its (N-1) x 153 GB/s of xGMI and the single-process
@@ -91,13 +94,21 @@ def parse_args():
     ap.add_argument("--no-host-path", action="store_true")
     ap.add_argument("--placement-candidates", type=int, default=8, help="ray-buffer allocations to choose the frame's from, at most (1: the plain first allocation; zoic_amd/placement.py)")
     ap.add_argument("--no-device-state", action="store_true", help="skip the second of frames with the clock / power sensors read beside it")
-    ap.add_argument("--only-headline", action="store_true", help="= --no-configs --no-sharded --no-host-path --no-cpu-baseline --no-parity --no-device-state")
+    ap.add_argument("--full", action="store_true", help="every leg besides the headline (parity, configs, sharded frames, host path, CPU baseline, device state); "
+                                                        "the --no-* options then skip single legs")
+    ap.add_argument("--only-headline", action="store_true", help="the headline only: what a run without --full does (kept for scripts that pass it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: origin (k,3), dir (k,3), weight (k,) float32 "
+                         "and flags (k,) float64 of a fixed seeded sample of k = %d rays of rank 0's frame (all of them on a smaller frame)" % (1 << 20))
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="minimum wall time of one repetition of a CPU baseline leg")
     ap.add_argument("--no-sparse-leg", action="store_true", help="N > 1: skip the sparse gather's timing (it runs last, behind everything else)")
     ap.add_argument("--no-single-process", action="store_true", help="N > 1: skip the zoic_frame_* measurement (rank 0 driving all devices)")
     ap.add_argument("--sharded-timeout", type=int, default=240, help="N > 1: seconds everything behind the weak-scaling leg (gathers included) may take before the line is printed with what has been measured")
     ap.add_argument("--gather-chunk-mb", type=int, default=0, help="payload MB per gather chunk (0: a quarter of a slab, at least 64 MB)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------- cameras
@@ -359,6 +370,18 @@ def time_frame(torch, cam, cfg, n, base, steps, warmup, dev, dist=None, local_ra
         keep["samples"], keep["out"] = samples, out
     del samples, out
     return elapsed, kernel_ms
+
+
+def dump_outputs(out, n, outdir, k=1 << 20, seed=20261015):
+    """--dump-outputs: what create_rays handed its caller in the last timed step (the (n, 8) records' origin, dir, weight and flag
+    word) for a fixed seeded sample of k of the n rays, in ray order -- 36 MB of .npy for k = 2^20; every ray when n <= k."""
+    import numpy as np
+    import torch
+    idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    rec = out["rays"][torch.from_numpy(idx).to(out["rays"].device)].cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in (("origin", rec[:, 0:3]), ("dir", rec[:, 3:6]), ("weight", rec[:, 6]), ("flags", rec[:, 7].view(np.int32).astype(np.float64))):
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def device_sensor_files(torch, device_index):
@@ -746,7 +769,7 @@ def resolve_launch(args, env, device_count, argv):
     """How many ranks this invocation means, and whether it has to start them itself.
 
     Returns ("run", world) -- this process is one rank of `world` (a launcher exported WORLD_SIZE, or N = 1) -- or
-    ("exec", command) -- `python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU.
+    ("exec", command) -- `python bench.py --gpus N` without a launcher: run under torch.distributed.run in a child process, one rank per GPU.
     Raises SystemExit (non-zero) when --gpus contradicts the launcher's WORLD_SIZE or asks for more GPUs than the node has."""
     env_world = int(env["WORLD_SIZE"]) if env.get("WORLD_SIZE") else None
     want = args.gpus if args.gpus is not None else (env_world or 1)
@@ -789,8 +812,9 @@ def flush_c_stdio():
 
 def main():
     args = parse_args()
-    if args.only_headline:
+    if args.only_headline or not args.full:
         args.no_configs = args.no_sharded = args.no_host_path = args.no_cpu_baseline = args.no_parity = args.no_device_state = True
+        args.no_single_process = True
     import torch
     from zoic_amd.workloads import CONFIGS, ray_count
 
@@ -798,7 +822,8 @@ def main():
     what, plan = resolve_launch(args, os.environ, ndev, sys.argv[1:])
     if what == "exec":
         flush_c_stdio()
-        os.execv(plan[0], plan)
+        # the ranks run in a child process: this one has opened the HIP runtime (device_count above) and is not replaced
+        sys.exit(subprocess.call(plan))
     world = plan
     if args.dry_launch:
         return dry_launch(world)
@@ -831,8 +856,14 @@ def main():
     frame = args.rays or ray_count(args.config)
     n, base, n_total = frame, rank * frame, frame * world        # weak leg: rank r renders frame r (distinct global ray indices)
     cam = make_camera(args.config, args.precision, local_rank)
-    keep = {"hold": world == 1 and not args.no_device_state}
+    device_state = world == 1 and not args.no_device_state
+    keep = {"hold": device_state or bool(args.dump_outputs)}
     elapsed, kernel_ms = time_frame(torch, cam, cfg, n, base, args.steps, args.warmup, dev, dist, local_rank, keep=keep, candidates=args.placement_candidates)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(keep["out"], n, args.dump_outputs)
+    if not device_state:
+        for k in ("samples", "out"):
+            keep.pop(k, None)
 
     line = None
     if rank == 0:
@@ -852,7 +883,7 @@ def main():
         # which allocation holds the frame's rays (zoic_amd/placement.py): every candidate's rate over a few frames BEFORE the timed
         # region; `first_pair_mrays_s` is what the plain first allocation would have given
         line["placement"] = keep.get("placement")
-        if world == 1 and not args.no_device_state:
+        if device_state:
             # outside the timed region: what clock did the kernel get?  (the peaks above are at 2.4 GHz; the socket's power limit decides)
             state = device_state_entry(torch, cam, cfg, n, base, dev, buffers=(keep.pop("samples"), keep.pop("out")))
             if state:
@@ -997,7 +1028,7 @@ def main():
         rank_barrier(dist, local_rank)
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
-    line["notes"] = {k: v for k, v in NOTES.items() if k != "multi_gpu"}
+    line["notes"] = {k: v for k, v in NOTES.items() if k in line or k in ("roofline", "mode")}
     text = json.dumps(line, separators=(",", ":"))
     if len(text) > 6000:     # the driver keeps the tail of the line: what explains goes first, the numbers stay
         del line["notes"]
