@@ -16,7 +16,7 @@
  * thread with no sample in flight, and camera_create_ray concurrently from every render thread, zoic.cpp:1752):
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
- *   - zoic_create_rays_device / _host / _arnold / _device_resident, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
+ *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
  *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
@@ -47,7 +47,9 @@ extern "C" {
  *      outlives its camera is DETACHED by zoic_camera_destroy (every call but zoic_tile_destroy fails, the array getters return NULL)
  *      instead of dangling; zoic_tile_done restarts a resident kernel that retired under the poll; ZOIC_FRAME_PAYLOAD_AUTO +
  *      zoic_frame_auto_layout (the gather's layout chosen from the camera's dead-ray fraction); zoic_create_rays_device_resident (device
- *      buffers through the resident kernel, no launch).  Nothing of ABI 4 changed shape. */
+ *      buffers through the resident kernel, no launch).  Nothing of ABI 4 changed shape.
+ *      Added later without a new number (additive: nothing existing changed shape or behaviour): zoic_ray_differential,
+ *      zoic_ray_differentials_device and zoic_create_rays_arnold_differentials (traced ray differentials). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -222,6 +224,37 @@ zoic_status zoic_create_rays_host(zoic_camera *cam, uint64_t n, const float *h_s
  * taken as 0, as Arnold hands it in.  Ray i draws its retries from the stream keyed by ray_index_base + i. */
 zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs,
                                     zoic_camera_output *outputs, uint64_t ray_index_base);
+
+/* ---- traced ray differentials (opt-in; csrc/differentials.hpp has the full definition) ------------------------------------
+ * The ray entry points above keep the reference's derivative fields (zoic.cpp:1971-1977: dOdx = dDdx = 0, dOdy = origin and
+ * dDdy = dir for retried rays), which are not derivatives.  These two calls compute them.  For a ray with weight > 0 and
+ * (sx, sy) its screen sample:
+ *   RAYTRACED  the accepted try (tries = bits 1-5 of the flags) starts at the sensor point o = (sx sw/2, sy sw/2, originShift),
+ *              sw = sensorWidth, and aims at the lens point L -- the try's sample after the exit-pupil transform (with the LUT:
+ *              scale, translation, rotation, zoic.cpp:1891-1943; without it the sample times lenses[0].aperture).  The derivatives
+ *              hold L FIXED while (sx, sy) move o, and follow the ray through every interface and the final flip (zoic.cpp:1959).
+ *   THINLENS   the lens point (the origin) is held fixed: dO = 0, dD = d/ds normalize(p |focalDistance| - origin) with the z flip,
+ *              p = (sx tan_fov, sy tan_fov, 1); without DOF d/ds normalize(p).
+ *   dOdx = dO/dsx * dsx, dOdy = dO/dsy * dsy, likewise for D (Arnold's convention).  Rays of weight 0 (the exhausted ones
+ *   included) and every ray of lensModel NONE get +0.0 in all 12 floats.  Rays outside the exit-pupil LUT (flag bit 6) are
+ *   differentiated through the same fenced lookup the ray kernels used.
+ * The result is the derivative of the path the record took (not a finite difference; the unit-square sample is not held fixed).
+ * The arithmetic is the same in every precision mode: STRICT and FAST cameras give bitwise-equal differentials on rays whose
+ * tries agree.  Not covered (their derivative fields stay the reference's): zoic_camera_create_ray and the tiles (resident
+ * kernel), zoic_create_rays_host, zoic_frame_*; chromatic aberration. */
+typedef struct zoic_ray_differential { zoic_vec3 dOdx, dOdy, dDdx, dDdy; } zoic_ray_differential;   /* 48 bytes */
+/* The differentials of rays zoic_create_rays_device made: pass what that call was given (d_samples, d_rng_states,
+ * ray_index_base) and what it wrote (d_rays).  The camera must not be updated between the two calls.  dsx = dsy = 1 returns the
+ * raw Jacobian columns.  d_out: n records in device memory, 16-byte aligned.  Asynchronous on `stream`, with the threading
+ * contract of zoic_create_rays_device.  ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL or
+ * misaligned pointer; n = 0 returns ZOIC_OK. */
+zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const float *d_samples, const uint32_t *d_rng_states,
+                                          uint64_t ray_index_base, const zoic_ray *d_rays, float dsx, float dsy,
+                                          zoic_ray_differential *d_out, void *stream);
+/* zoic_create_rays_arnold with traced derivative fields: origin, dir and weight[3] of every row are bit-identical to that
+ * call's; dOdx, dOdy, dDdx, dDdy are the differentials above, scaled by the row's own input dsx / dsy. */
+zoic_status zoic_create_rays_arnold_differentials(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs,
+                                                  zoic_camera_output *outputs, uint64_t ray_index_base);
 /* camera_create_ray(node, input, output, tid), zoic.cpp:1752: the per-sample signature.  No launch per call: the sample goes
  * to a resident kernel through mapped pinned memory (csrc/mailbox.hip; ~7 us per call; the kernel retires by itself after 1 ms
  * without a call and is started again by the next one).  Re-entrant: every tid owns a retry stream that carries over from call

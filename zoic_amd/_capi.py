@@ -44,6 +44,10 @@ class CameraOutput(C.Structure):
                 ("weight", C.c_float * 3)]
 
 
+class RayDifferential(C.Structure):   # zoic_ray_differential: 48 bytes per ray
+    _fields_ = [("dOdx", Vec3), ("dOdy", Vec3), ("dDdx", Vec3), ("dDdy", Vec3)]
+
+
 class Ray(C.Structure):   # zoic_ray: one 32-byte record per camera ray
     _fields_ = [(n, C.c_float) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "weight")] + [("flags", C.c_uint32)]
 
@@ -93,6 +97,8 @@ SYMBOLS = {
     "zoic_create_rays_device": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "zoic_create_rays_host": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp]),
     "zoic_create_rays_arnold": (C.c_int, [_vp, _u64, C.POINTER(CameraInput), C.POINTER(CameraOutput), _u64]),
+    "zoic_create_rays_arnold_differentials": (C.c_int, [_vp, _u64, C.POINTER(CameraInput), C.POINTER(CameraOutput), _u64]),
+    "zoic_ray_differentials_device": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.c_float, C.c_float, _vp, _vp]),
     "zoic_camera_create_ray": (C.c_int, [_vp, C.POINTER(CameraInput), C.POINTER(CameraOutput), C.c_uint16]),
     "zoic_tile_create": (C.c_int, [_vp, _u32, C.c_uint16, C.POINTER(_vp)]),
     "zoic_tile_destroy": (None, [_vp]),

@@ -328,15 +328,52 @@ class ZoicCamera:
         t = C.c_float(0.0)
         return bool(self._lib.zoic_camera_reverse_ray(self._h, C.byref(po), float(fov), ps, C.byref(t)))
 
-    def create_rays_arnold(self, inputs, ray_index_base=0):
-        """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1)."""
+    def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
+        """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1).
+
+        differentials=True: zoic_create_rays_arnold_differentials -- the same origin / dir / weight, and traced dOdx, dOdy, dDdx,
+        dDdy (columns 6-17) scaled by each row's dsx / dsy (columns 2, 3) instead of the reference's placeholders."""
         a = np.ascontiguousarray(inputs, dtype=np.float32)
         n = a.shape[0]
         outs = np.zeros((n, 21), dtype=np.float32)
         outs[:, 18:21] = 1.0
-        self._check(self._lib.zoic_create_rays_arnold(self._h, n, a.ctypes.data_as(C.POINTER(_capi.CameraInput)),
-                                                      outs.ctypes.data_as(C.POINTER(_capi.CameraOutput)), int(ray_index_base)))
+        fn = self._lib.zoic_create_rays_arnold_differentials if differentials else self._lib.zoic_create_rays_arnold
+        self._check(fn(self._h, n, a.ctypes.data_as(C.POINTER(_capi.CameraInput)), outs.ctypes.data_as(C.POINTER(_capi.CameraOutput)),
+                       int(ray_index_base)))
         return outs
+
+    def ray_differentials(self, samples, rays, dsx=1.0, dsy=1.0, rng_states=None, ray_index_base=0, out=None, stream=None):
+        """Traced ray differentials (zoic_ray_differentials_device) of rays create_rays made from device tensors.
+
+        samples, rng_states, ray_index_base: what that create_rays call was given; rays: the (n,8) float32 record tensor it returned
+        (or its result dict).  The camera must not have been updated in between.  Returns an (n,12) float32 device tensor, columns
+        dOdx, dOdy, dDdx, dDdy (x y z each), scaled by dsx / dsy (1: the raw Jacobian columns); asynchronous on `stream` (default:
+        torch's current stream).  Rays of weight 0 get zeros."""
+        import torch
+        if isinstance(rays, dict):
+            rays = rays["rays"]
+        if not _is_torch(samples) or not _is_torch(rays):
+            raise ValueError("samples and rays must be device tensors (create_rays with a torch tensor)")
+        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
+            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
+        if samples.device.index != self.device:
+            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
+        n = samples.shape[0]
+        if tuple(rays.shape) != (n, 8) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
+            raise ValueError("rays must be the contiguous (n,8) float32 record tensor on the samples' device")
+        rs_ptr = None
+        if rng_states is not None:
+            if rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4) or not rng_states.is_contiguous():
+                raise ValueError("rng_states must be (n,4) int32/uint32 on the device")
+            rs_ptr = rng_states.data_ptr()
+        if out is None:
+            out = torch.empty((n, 12), dtype=torch.float32, device=samples.device)
+        if tuple(out.shape) != (n, 12) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != samples.device:
+            raise ValueError("out must be a contiguous (n,12) float32 tensor on the samples' device")
+        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        self._check(self._lib.zoic_ray_differentials_device(self._h, n, samples.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(),
+                                                            float(dsx), float(dsy), out.data_ptr(), C.c_void_p(st)))
+        return out
 
     def tile(self, capacity, tid=0):
         """A ZoicTile of this camera (closed with the camera at the latest: ZoicCamera.close() closes the tiles still alive)."""

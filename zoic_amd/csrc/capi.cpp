@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/zoic_amd.h"
+#include "differentials.hpp"
 #include "kernels.hpp"
 #include "mailbox.hpp"
 #include "lens_system.hpp"
@@ -1179,8 +1180,10 @@ zoic_status zoic_create_rays_host(zoic_camera *cam, uint64_t n, const float *h_s
     return status;
 }
 
-zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs, zoic_camera_output *outputs,
-                                    uint64_t ray_index_base)
+// zoic_create_rays_arnold and zoic_create_rays_arnold_differentials: one pipeline, the expansion of the records to rows differs
+// (differentials: the rows' derivative fields are traced from the inputs still on the device, differentials.hip)
+static zoic_status create_rays_arnold_rows(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs, zoic_camera_output *outputs,
+                                           uint64_t ray_index_base, bool differentials)
 {
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
@@ -1217,7 +1220,12 @@ zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_cam
         if (e != hipSuccess) { status = fail(ZOIC_ERR_HIP, std::string("H2D + pack: ") + hipGetErrorString(e)); break; }
         status = launch_rays(cam, m, C.dSamples[b].ptr, nullptr, ray_index_base + off, C.dRays[b].ptr, C.sRun);
         if (status != ZOIC_OK) break;
-        e = static_cast<hipError_t>(launch_expand_outputs(C.dRays[b].ptr, C.dOut21[b].ptr, m, C.sRun));
+        if (differentials)
+            e = static_cast<hipError_t>(launch_expand_outputs_differentials(cam->params.p.lensModel, cam->kolb, cam->thin, cam->bokehDev,
+                                                                            C.dInputs7[b].ptr, ray_index_base + off, m, C.dRays[b].ptr,
+                                                                            C.dOut21[b].ptr, C.sRun));
+        else
+            e = static_cast<hipError_t>(launch_expand_outputs(C.dRays[b].ptr, C.dOut21[b].ptr, m, C.sRun));
         if (e == hipSuccess) e = hipEventRecord(C.runDone[b], C.sRun);
         if (e == hipSuccess) e = hipStreamWaitEvent(C.sOut, C.runDone[b], 0);
         if (e == hipSuccess) e = hipMemcpyAsync(outputs + off, C.dOut21[b].ptr, m * sizeof(zoic_camera_output), hipMemcpyDeviceToHost, C.sOut);
@@ -1229,6 +1237,43 @@ zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_cam
         if (e != hipSuccess && status == ZOIC_OK) status = fail(ZOIC_ERR_HIP, std::string("stream sync: ") + hipGetErrorString(e));
     }
     return status;
+}
+
+zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs, zoic_camera_output *outputs,
+                                    uint64_t ray_index_base)
+{
+    return create_rays_arnold_rows(cam, n, inputs, outputs, ray_index_base, false);
+}
+
+zoic_status zoic_create_rays_arnold_differentials(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs, zoic_camera_output *outputs,
+                                                  uint64_t ray_index_base)
+{
+    return create_rays_arnold_rows(cam, n, inputs, outputs, ray_index_base, true);
+}
+
+zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const float *d_samples, const uint32_t *d_rng_states,
+                                          uint64_t ray_index_base, const zoic_ray *d_rays, float dsx, float dsy,
+                                          zoic_ray_differential *d_out, void *stream)
+{
+    static_assert(sizeof(zoic_ray_differential) == 48, "zoic_ray_differential layout");
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_samples || (reinterpret_cast<uintptr_t>(d_samples) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be non-NULL and 16-byte aligned");
+    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_out must be non-NULL and 16-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int model = cam->params.p.lensModel;
+    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no derivative
+        ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
+        return ZOIC_OK;
+    }
+    const int rc = launch_ray_differentials(model, cam->kolb, cam->thin, cam->bokehDev, d_samples, d_rng_states, ray_index_base, n,
+                                            reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy, reinterpret_cast<float *>(d_out), st);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
 }
 
 }  // extern "C"
