@@ -49,7 +49,9 @@ extern "C" {
  *      zoic_frame_auto_layout (the gather's layout chosen from the camera's dead-ray fraction); zoic_create_rays_device_resident (device
  *      buffers through the resident kernel, no launch).  Nothing of ABI 4 changed shape.
  *      Added later without a new number (additive: nothing existing changed shape or behaviour): zoic_ray_differential,
- *      zoic_ray_differentials_device and zoic_create_rays_arnold_differentials (traced ray differentials). */
+ *      zoic_ray_differentials_device and zoic_create_rays_arnold_differentials (traced ray differentials).
+ *      Added later without a new number (additive): zoic_create_rays_spectral_device, zoic_camera_get_dispersion and
+ *      zoic_camera_set_abbe_numbers (rays at a wavelength per ray: chromatic aberration); flag bit 7 of zoic_ray (wavelength rejected). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -132,7 +134,8 @@ typedef struct zoic_camera_output {
 
 /* Batch output: one 32-byte record per ray (the fields of AtCameraOutput that zoic writes, zoic.cpp:1752-1990).
  * flags: bit0 = retried (tries > 0  => the caller sets dOdy=origin, dDdy=dir, zoic.cpp:1974-1977),
- *        bits1-5 = tries (0..26; 26 => weight 0, zoic.cpp:1951-1953), bit6 = outside the exit-pupil LUT (fenced UB). */
+ *        bits1-5 = tries (0..26; 26 => weight 0, zoic.cpp:1951-1953), bit6 = outside the exit-pupil LUT (fenced UB),
+ *        bit7 = wavelength rejected (zoic_create_rays_spectral_device: the record is all zero but for flags == 0x80). */
 typedef struct zoic_ray {
     float ox, oy, oz;   /* output.origin */
     float dx, dy, dz;   /* output.dir    */
@@ -255,6 +258,31 @@ zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const fl
  * call's; dOdx, dOdy, dDdx, dDdy are the differentials above, scaled by the row's own input dsx / dsy. */
 zoic_status zoic_create_rays_arnold_differentials(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs,
                                                   zoic_camera_output *outputs, uint64_t ray_index_base);
+/* ---- rays at a wavelength per ray: chromatic aberration (opt-in; csrc/spectral.hpp has the full definition) -----------------
+ * Each medium behind interface i (trace order, rear first) gets a two-term Cauchy index through its d-line index n_d (the
+ * prescription's ior) and its Abbe number V (the prescription's fifth column, zoic.cpp:524, or zoic_camera_set_abbe_numbers):
+ *   n_i(lambda) = n_d,i + B_i (1/lambda^2 - 1/587.5618^2),  B_i = (n_d,i - 1) / (V_i (1/486.1327^2 - 1/656.2725^2))
+ * (B_i = 0 for air, a 4-column prescription or V <= 0).  Every interface applies the reference's eta and TIR rules (zoic.cpp:1013,
+ * 1019) to the ray's own indices.  The exit-pupil LUT, the focus, the focal-length rescale and the bokeh tables stay those of the
+ * d-line: the camera is focused at 587.5618 nm and other colours show longitudinal chromatic aberration. */
+/* zoic_create_rays_device with a wavelength per ray: d_wavelengths = n f32 in nanometres in device memory, 4-byte aligned; every other
+ * argument, the stream semantics, the retry streams keyed by ray index, the counters and the threading contract are that call's.
+ * RAYTRACED: the model above (STRICT: the reference's arithmetic on the per-ray indices; at lambda = 587.5618 the records are
+ * zoic_create_rays_device's bit for bit; FAST modes: decision-safe as there).  THINLENS and NONE ignore the wavelength: their records
+ * (or NONE's error) are zoic_create_rays_device's.  A wavelength outside [360, 830] or NaN rejects that ray only: origin = dir = +0.0,
+ * weight 0, flags == 0x80 (bit 7), and no counter counts it.  zoic_ray_differentials_device is NOT valid for these records: it
+ * replays the d-line trace.  ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer;
+ * n = 0 returns ZOIC_OK. */
+zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
+                                             const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream);
+/* The dispersion table of the camera's lens (works on a ZOIC_DEVICE_NONE camera): returns the surface count and writes up to
+ * `capacity` entries, trace order (rear first), of n_d (after the 0 -> 1.0 fix, zoic.cpp:937-940), V (the override if one is set)
+ * and B (nm^2) into the arrays that are not NULL; -1 for a NULL camera or a negative capacity. */
+int zoic_camera_get_dispersion(const zoic_camera *cam, int capacity, float *ior_d, float *abbe, float *cauchy_b);
+/* V-numbers for the dispersion table, in FILE order (front to rear, as a prescription lists them): gives glass data to 4-column
+ * prescriptions.  count = 0 clears the override (V may be NULL).  A count that differs from the loaded lens's surface count returns
+ * ZOIC_ERR_INVALID_ARGUMENT, here and at every zoic_camera_update while the override is set.  Changes nothing but the dispersion table. */
+zoic_status zoic_camera_set_abbe_numbers(zoic_camera *cam, int count, const float *V);
 /* camera_create_ray(node, input, output, tid), zoic.cpp:1752: the per-sample signature.  No launch per call: the sample goes
  * to a resident kernel through mapped pinned memory (csrc/mailbox.hip; ~7 us per call; the kernel retires by itself after 1 ms
  * without a call and is started again by the next one).  Re-entrant: every tid owns a retry stream that carries over from call

@@ -237,14 +237,20 @@ class ZoicCamera:
         return self
 
     # ------------------------------------------------------------------ camera_create_ray
-    def create_rays(self, samples, rng_states=None, ray_index_base=0, out=None, stream=None):
+    def create_rays(self, samples, rng_states=None, ray_index_base=0, out=None, stream=None, wavelengths=None):
         """samples: (n,4) float32 rows (sx, sy, lensx, lensy).
 
         numpy in  -> host API (H2D, kernels, D2H); returns a dict of numpy arrays built from the (n,) zoic_ray records:
                      rays (structured), planes (7,n) = ox oy oz dx dy dz weight, origin (3,n), dir (3,n), weight, flags, tries.
         torch device tensor in -> device API, asynchronous on `stream` (default: torch's current stream); returns a dict
                      with rays = (n,8) float32 tensor (column 7 holds the flag word's bits) and strided views into it.
+        wavelengths: None (the d-line path above, untouched) or n float32 wavelengths in nm, one per ray
+                     (zoic_create_rays_spectral_device).  With torch samples a (n,) float32 device tensor, asynchronous as above;
+                     with numpy samples a numpy array: samples, wavelengths and rng_states are copied to the camera's device through
+                     torch, the call waits for the records and returns the numpy dict (out must be None there).
         """
+        if wavelengths is not None:
+            return self._create_rays_spectral(samples, wavelengths, rng_states, ray_index_base, out, stream)
         if _is_torch(samples):
             return self._create_rays_torch(samples, rng_states, ray_index_base, out, stream)
         s = np.ascontiguousarray(samples, dtype=np.float32)
@@ -291,6 +297,70 @@ class ZoicCamera:
         out.update(origin=rays[:, 0:3].t(), dir=rays[:, 3:6].t(), weight=rays[:, 6], planes=rays[:, 0:7].t(),
                    flags=rays[:, 7].view(torch.int32))
         return out
+
+    def _create_rays_spectral(self, samples, wavelengths, rng_states, ray_index_base, out, stream):
+        import torch
+        if not _is_torch(samples):
+            if _is_torch(wavelengths) or (rng_states is not None and _is_torch(rng_states)):
+                raise TypeError("numpy samples need numpy wavelengths and rng_states")
+            if out is not None:
+                raise ValueError("out is for torch samples")
+            s = np.ascontiguousarray(samples, dtype=np.float32)
+            if s.ndim != 2 or s.shape[1] != 4:
+                raise ValueError("samples must be (n, 4)")
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                self._check(self._lib.zoic_create_rays_spectral_device(self._h, s.shape[0], None, None, None, int(ray_index_base), None, None))
+            dev = torch.device("cuda", self.device)
+            ts = torch.from_numpy(s).to(dev)
+            tw = torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            tr = None if rng_states is None else torch.from_numpy(np.ascontiguousarray(rng_states, dtype=np.uint32).view(np.int32)).to(dev)
+            res = self._create_rays_spectral(ts, tw, tr, ray_index_base, None, None)
+            torch.cuda.synchronize(dev)
+            rays = np.ascontiguousarray(res["rays"].cpu().numpy()).view(_capi.RAY_DTYPE).reshape(-1)
+            return rays_to_dict(rays)
+        if not _is_torch(wavelengths):
+            raise TypeError("torch samples need a torch wavelength tensor")
+        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
+            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
+        if samples.device.index != self.device:
+            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
+        n = samples.shape[0]
+        if wavelengths.dtype != torch.float32 or tuple(wavelengths.shape) != (n,) or not wavelengths.is_contiguous() or wavelengths.device != samples.device:
+            raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the samples' device")
+        if out is None:
+            out = dict(rays=torch.empty((n, 8), dtype=torch.float32, device=samples.device))
+        rays = out["rays"]
+        if rays.device != samples.device:
+            raise ValueError("out['rays'] must live on the samples' device")
+        rs_ptr = None
+        if rng_states is not None:
+            if rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4):
+                raise ValueError("rng_states must be (n,4) int32/uint32 on the device")
+            rs_ptr = rng_states.data_ptr()
+        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        self._check(self._lib.zoic_create_rays_spectral_device(self._h, n, samples.data_ptr(), wavelengths.data_ptr(), rs_ptr,
+                                                               int(ray_index_base), rays.data_ptr(), C.c_void_p(st)))
+        out.update(origin=rays[:, 0:3].t(), dir=rays[:, 3:6].t(), weight=rays[:, 6], planes=rays[:, 0:7].t(),
+                   flags=rays[:, 7].view(torch.int32))
+        return out
+
+    def dispersion(self):
+        """The lens's dispersion table (zoic_camera_get_dispersion), trace order (rear first): dict of float32 arrays ior_d, abbe and
+        cauchy_b (nm^2).  Works on a tables-only camera (device=-1)."""
+        n = self._lib.zoic_camera_get_dispersion(self._h, 0, None, None, None)
+        if n < 0:
+            self._check(1)   # ZOIC_ERR_INVALID_ARGUMENT with the library's detail
+        a = {k: np.zeros(n, dtype=np.float32) for k in ("ior_d", "abbe", "cauchy_b")}
+        self._lib.zoic_camera_get_dispersion(self._h, n, a["ior_d"].ctypes.data, a["abbe"].ctypes.data, a["cauchy_b"].ctypes.data)
+        return a
+
+    def set_abbe_numbers(self, V):
+        """V-numbers in FILE order (front to rear, as the prescription lists them) for the dispersion table; None clears them."""
+        if V is None:
+            self._check(self._lib.zoic_camera_set_abbe_numbers(self._h, 0, None))
+            return
+        v = np.ascontiguousarray(V, dtype=np.float32).reshape(-1)
+        self._check(self._lib.zoic_camera_set_abbe_numbers(self._h, v.shape[0], v.ctypes.data))
 
     def create_rays_device_ptr(self, n, d_samples, d_rays, d_rng=None, ray_index_base=0, stream=0):
         """Raw-pointer form of zoic_create_rays_device (d_rays: n x 32-byte zoic_ray records)."""

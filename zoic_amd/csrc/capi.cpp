@@ -34,6 +34,7 @@
 #include "differentials.hpp"
 #include "kernels.hpp"
 #include "mailbox.hpp"
+#include "spectral.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
 
@@ -285,6 +286,7 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     std::mutex tilesM;
     std::vector<zoic_tile *> liveTiles;
     std::atomic<int> waitMode{ZOIC_WAIT_SPIN};   // zoic_camera_set_wait_mode: how a render thread waits for the resident kernel
+    std::vector<float> abbeOverride;             // zoic_camera_set_abbe_numbers: V-numbers in file order (empty: the prescription's own)
 
     TidState *tid_state(uint16_t tid);
     CallContext *lease_context(hipError_t &err);
@@ -763,6 +765,24 @@ zoic_status fast_self_check(zoic_camera *cam, bool &keep)
     return ZOIC_OK;
 }
 
+// the dispersion table of the camera's lens (spectral.hpp), trace order: the prescription's V-numbers or the override (file order,
+// front first: reversed here)
+void fill_spectral(const zoic_camera *cam, SpectralTable &W)
+{
+    W = SpectralTable{};
+    const std::vector<LensRow> &rows = cam->lens.rows;
+    const size_t n = std::min<size_t>(rows.size(), kMaxSurfaces);
+    W.count = static_cast<int32_t>(n);
+    const bool override = cam->abbeOverride.size() == rows.size() && !rows.empty();
+    for (size_t i = 0; i < n; ++i) {
+        const float abbe = override ? cam->abbeOverride[rows.size() - 1 - i] : rows[i].abbe;
+        W.iorD[i] = rows[i].ior;
+        W.cauchyB[i] = cauchy_b(rows[i].ior, abbe);
+        const double R = static_cast<double>(rows[i].radius);
+        W.invAbsRR[i] = static_cast<float>(1.0 / (std::fabs(R) * R));
+    }
+}
+
 }  // namespace
 
 static void detach_tiles(zoic_camera *cam);   // (defined with the tile entry points below)
@@ -1056,6 +1076,9 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
         break;
     default: break;
     }
+    if (p->lensModel == ZOIC_RAYTRACED && !cam->abbeOverride.empty() && cam->abbeOverride.size() != cam->lens.rows.size())
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_abbe_numbers: " + std::to_string(cam->abbeOverride.size()) +
+                                                   " V-numbers for a lens of " + std::to_string(cam->lens.rows.size()) + " surfaces");
 
     // camera->params = parms, zoic.cpp:1719
     cam->params.p = *p;
@@ -1273,6 +1296,65 @@ zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const fl
     const int rc = launch_ray_differentials(model, cam->kolb, cam->thin, cam->bokehDev, d_samples, d_rng_states, ray_index_base, n,
                                             reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy, reinterpret_cast<float *>(d_out), st);
     if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
+                                             const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
+    if (reinterpret_cast<uintptr_t>(d_samples) & 15u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be 16-byte aligned");
+    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
+    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    RayRecord *rays = reinterpret_cast<RayRecord *>(d_rays);
+    if (cam->params.p.lensModel != ZOIC_RAYTRACED) {
+        // THINLENS (and NONE's error): the records of zoic_create_rays_device, then the rows of invalid wavelengths rejected
+        if (zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, rays, st)) return s;
+        const int rc = launch_spectral_reject(d_wavelengths, n, rays, cam->dCounters, cam->thin.useDof != 0, st);
+        if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        return ZOIC_OK;
+    }
+    SpectralTable W;
+    fill_spectral(cam, W);
+    const int rc = launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, rays,
+                                        cam->dCounters, cam->kernel_mode(), st);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+int zoic_camera_get_dispersion(const zoic_camera *cam, int capacity, float *ior_d, float *abbe, float *cauchy_b_out)
+{
+    if (!cam) { fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL"); return -1; }
+    if (capacity < 0) { fail(ZOIC_ERR_INVALID_ARGUMENT, "capacity is negative"); return -1; }
+    SpectralTable W;
+    fill_spectral(cam, W);
+    const std::vector<LensRow> &rows = cam->lens.rows;
+    const bool override = cam->abbeOverride.size() == rows.size() && !rows.empty();
+    for (int i = 0; i < W.count && i < capacity; ++i) {
+        if (ior_d) ior_d[i] = W.iorD[i];
+        if (abbe) abbe[i] = override ? cam->abbeOverride[rows.size() - 1 - i] : rows[i].abbe;
+        if (cauchy_b_out) cauchy_b_out[i] = W.cauchyB[i];
+    }
+    return W.count;
+}
+
+zoic_status zoic_camera_set_abbe_numbers(zoic_camera *cam, int count, const float *V)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (count < 0 || count > ZOIC_MAX_LENS_SURFACES) return fail(ZOIC_ERR_INVALID_ARGUMENT, "count out of range");
+    if (count == 0) { cam->abbeOverride.clear(); return ZOIC_OK; }
+    if (!V) return fail(ZOIC_ERR_INVALID_ARGUMENT, "V is NULL");
+    const bool loaded = cam->updated && cam->params.p.lensModel == ZOIC_RAYTRACED && !cam->lens.rows.empty();
+    if (loaded && static_cast<size_t>(count) != cam->lens.rows.size())
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_abbe_numbers: " + std::to_string(count) + " V-numbers for a lens of " +
+                                                   std::to_string(cam->lens.rows.size()) + " surfaces");
+    cam->abbeOverride.assign(V, V + count);
     return ZOIC_OK;
 }
 

@@ -1,0 +1,314 @@
+// spectral.hip -- camera_create_ray (RAYTRACED, zoic.cpp:1850-1964) at a wavelength per ray (spectral.hpp has the model).
+//
+// Mapping.  Persistent lanes: a wave claims CHUNKS of kSpecChunk consecutive rays (grid-stride over the batch) and each lane holds
+// one ray until it is finished, then takes the next ray of the chunk (ballot + mbcnt).  A round of the wave's loop is
+//   * refill: free lanes take the chunk's next rays and set them up -- the reference's set-up arithmetic (setup_ray<true>: sensor
+//     point, exit-pupil LUT, parabola rotation), the sample's own lens point, the ray's wavelength;
+//   * candidate search: a lane whose try dies at interface 0 (a clip there is geometry only: the wavelength plays no part) draws
+//     the next lens sample from its retry stream, as the pool kernels do -- tries and stream advance exactly as in the reference's
+//     loop -- while enough lanes are looking (kSpecMinSearching) or no lane has a candidate yet;
+//   * trace: the candidates go through every interface with the eta and TIR rule of THEIR wavelength;
+//   * the finished rays' records are written and their counts kept per lane; a failed try goes back to the search.
+// Dead pixels (outside the image circle, all 27 tries are one) and retry-dead rays (no retry can reach the rear element:
+// dead_ray_end) end after their first try, as in the pool kernels.
+// STRICT: trace_lens_spectral_strict (spectral.hpp), the reference's arithmetic bit for bit.  FAST (both FAST modes): f32 with
+// explicit FMAs (fast_optics.hpp FastHit / fast_refract) on per-lane eta, qOffset and krScale; set-up, lens samples, directions and
+// the interface-0 test stay the reference's, and a try with a clip inside a guard band (FastSurface::housingLo/Hi) is traced again
+// in the reference's arithmetic from the same start: every clip decision is either a FAST one outside its band or a STRICT one.
+#include <hip/hip_runtime.h>
+
+#include "kolb_pool_body.hpp"
+#include "spectral.hpp"
+
+#pragma STDC FP_CONTRACT OFF
+
+namespace zoic {
+namespace {
+
+constexpr int kSpecBlock = 256;
+constexpr uint32_t kSpecChunk = 256;           // rays per claim of a wave: 4 per lane
+constexpr uint32_t kSpecMinSearching = 16;     // the search goes on while at least this many lanes are looking
+constexpr uint64_t kSpecGridCap = 2048;        // 8 waves per SIMD on 256 CUs
+
+// The kernels' argument list as a struct (HIP lays kernel arguments out like a C struct, kolb_pool_body.hpp KolbKernelArgs): the
+// traces read the tables through the kernarg segment (spectral.hpp ZOIC_SPEC_PIN).
+struct SpectralKernelArgs {
+    KolbTable T; SpectralTable W; BokehTables B; const float4 *samples; const float *lambdas; const uint4 *rngStates; uint64_t rayBase; uint64_t n;
+    RayRecord *out; DeviceCounters *counters;
+};
+typedef const Surface __attribute__((address_space(4))) *SurfaceTable;
+typedef const SpectralTable __attribute__((address_space(4))) *SpectralTablePtr;
+__device__ __forceinline__ SurfaceTable kernarg_surfaces()
+{
+    typedef const char __attribute__((address_space(4))) *KernargBytes;
+    return (SurfaceTable)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpectralKernelArgs, T) + offsetof(KolbTable, surf));
+}
+__device__ __forceinline__ SpectralTablePtr kernarg_spectral()
+{
+    typedef const char __attribute__((address_space(4))) *KernargBytes;
+    return (SpectralTablePtr)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpectralKernelArgs, W));
+}
+
+__device__ __forceinline__ bool trace_strict(int count, float dl, V3 &o, V3 &d, uint32_t &tirCount)
+{
+    return trace_lens_spectral_strict(kernarg_surfaces(), kernarg_spectral(), count, dl, o, d, tirCount);
+}
+
+// One try's trace in FAST arithmetic with the per-lane constants of the ray's wavelength.  (o, d) as trace_lens_fast_rolled leaves
+// them; `unsure`: a clip decision inside its interface's guard band was met (the caller then traces the try in STRICT).
+__device__ __forceinline__ bool trace_fast(int n, float dl, V3 &o, V3 &d, uint32_t &tirCount, bool &unsure)
+{
+    const float inv = frsq_fast(fast_norm2(d));
+    V3 u{d.x * inv, d.y * inv, d.z * inv};
+    float oAxis2 = fast_axis2(o);
+    bool ok = true, refracted = false;
+    SpectralTablePtr W = kernarg_spectral();
+    float n1 = ffma(W->cauchyB[0], dl, W->iorD[0]);
+    for (int ii = 0; ii < n; ++ii) {
+        const int i = __builtin_amdgcn_readfirstlane(ii);
+        FastSurface S = load_surface<true>(kernarg_fast_surfaces(), i);
+        ZOIC_SPEC_PIN(W);
+        const float n2 = (i + 1 < n) ? ffma(W->cauchyB[i + 1], dl, W->iorD[i + 1]) : 1.0f;
+        // eta = n1 / n2 (== n1 where n2 == 1, zoic.cpp:1013); qOffset = R^2 (1 - eta^2) / eta^2 = R^2 (n2 - n1)(n2 + n1) / n1^2 (no
+        // cancellation at cemented interfaces); krScale = eta / (|R| R)
+        S.eta = n1 * frcp_fast(n2);
+        S.qOffset = S.radius2 * (((n2 - n1) * (n2 + n1)) * frcp_fast(n1 * n1));
+        S.krScale = S.eta * W->invAbsRR[i];
+        bool near = false;
+        const int r = fast_interface(S, o, oAxis2, u, &near);
+        unsure |= near;
+        if (r != 0) { if (r == 2) ++tirCount; ok = false; break; }
+        refracted = true;
+        n1 = n2;
+    }
+    if (refracted) d = u;
+    return ok;
+}
+
+// the ray's private retry stream before its first draw (the pool kernels' seeding)
+__device__ __forceinline__ Rng ray_stream(const uint4 *rngStates, uint32_t seed, uint64_t rayBase, uint64_t idx)
+{
+    if (rngStates) { const uint4 r = rngStates[idx]; return Rng{r.x, r.y, r.z, r.w}; }
+    return rng_for_ray(seed, rayBase + idx);
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+}  // namespace
+
+// budget: 0 scratch, 0 spills
+template <bool FAST>
+__global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTable T, const SpectralTable W, const BokehTables B,
+                                                                   const float4 *__restrict__ samples, const float *__restrict__ lambdas,
+                                                                   const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
+                                                                   RayRecord *__restrict__ out, DeviceCounters *counters)
+{
+    __shared__ __align__(16) float2 lut[kLutEntries];   // (maxScale, centroid.x) pairs of the exit-pupil LUT: setup_ray's lookup
+    if (threadIdx.x < kLutEntries) lut[threadIdx.x] = make_float2(T.lutMaxScale[threadIdx.x], T.lutCentroidX[threadIdx.x]);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kSpecBlock / 64);
+    const uint64_t waveId = static_cast<uint64_t>(blockIdx.x) * (kSpecBlock / 64) + (threadIdx.x >> 6);
+    const uint32_t kOut = static_cast<uint32_t>(kMaxTries) + 1u;
+    uint32_t succ = 0, vign = 0, tir = 0;
+
+    for (uint64_t chunk = waveId * kSpecChunk; chunk < n; chunk += waves * kSpecChunk) {
+        const uint64_t end = (n - chunk < kSpecChunk) ? n : chunk + kSpecChunk;
+        uint64_t next = chunk;   // wave-uniform
+        bool busy = false, searching = false, cand = false, finiteSample = true;
+        uint64_t idx = 0;
+        uint32_t tries = 0;
+        float dl = 0.0f;
+        RaySetup rs{};
+        Rng rng{1u, 2u, 3u, 4u};
+        V3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
+        for (;;) {
+            // ---- refill ---------------------------------------------------------------------------------------------------
+            const unsigned long long freeMask = __ballot(!busy);
+            bool fresh = false;
+            if (next < end && freeMask != 0ull) {
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(freeMask >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(freeMask), 0u));
+                const uint64_t left = end - next;
+                if (!busy && rank < left) { idx = next + rank; fresh = true; }
+                const uint64_t took = static_cast<uint64_t>(__popcll(freeMask));
+                next += took < left ? took : left;
+            }
+            if (fresh) {
+                const float lambda = lambdas[idx];
+                if (!spectral_valid(lambda)) {
+                    store_ray_record(out, idx, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, kSpectralRejected);   // no counter
+                } else {
+                    busy = true;
+                    const float4 s = samples[idx];
+                    dl = spectral_dl(lambda);
+                    rs = setup_ray<true>(T, lut, s.x, s.y);
+                    tries = 0;
+                    o = V3{rs.o0x, rs.o0y, T.originShift};
+                    V2 lens = lens_sample<true>(T, B, nullptr, s.z, s.w);                       // zoic.cpp:1870
+                    finiteSample = (fabsf(lens.x) <= 3.0e38f) && (fabsf(lens.y) <= 3.0e38f);
+                    if (!T.useLUT) {                                                             // zoic.cpp:1873-1877
+                        d = V3{(lens.x * T.rearAperture) - o.x, (lens.y * T.rearAperture) - o.y, T.dirZ};
+                    } else {                                                                     // zoic.cpp:1913-1924 (x only)
+                        lens.x *= rs.maxScale; lens.y *= rs.maxScale;
+                        lens.x += rs.translation;
+                        const float rx = lens.x * rs.cs - lens.y * rs.sn, ry = lens.x * rs.sn + lens.y * rs.cs;
+                        d = V3{rx - o.x, ry - o.y, T.dirZ};
+                    }
+                    searching = true;
+                    cand = false;
+                }
+            }
+            if (__ballot(busy) == 0ull) {
+                if (next >= end) break;
+                continue;
+            }
+
+            // ---- candidate search (zoic.cpp:1927-1947: a clip at interface 0 bumps no counter and leaves (o, d) untouched) -------
+            bool done = false, failed = false;
+            for (;;) {
+                const uint32_t looking = static_cast<uint32_t>(__popcll(__ballot(searching)));
+                if (looking == 0u || (looking < kSpecMinSearching && __ballot(cand) != 0ull)) break;
+                if (searching) {
+                    bool inRange;
+                    bool pass = interface0_clear_strict_lean(T, o, d, inRange);
+                    if (__builtin_expect(!inRange, 0)) pass = interface0_clear_strict(T, o, d);
+                    if (pass) {
+                        cand = true; searching = false;
+                    } else if (tries == 0u && rs.dead && finiteSample) {
+                        tries = kOut; searching = false; done = true; failed = true;             // all 27 tries are this one
+                    } else if (tries == 0u && (rs.flags & kRetryDeadBit) != 0u) {
+                        searching = false; done = true; failed = true; tries = 0xffu;            // dead_ray_end below
+                    } else if (tries >= kOut) {
+                        searching = false; done = true; failed = true;
+                    } else {
+                        if (tries == 0u) rng = ray_stream(rngStates, T.seed, rayBase, idx);
+                        const float u = rng_unit(xor128(rng));   // zoic.cpp:1930
+                        const float v = rng_unit(xor128(rng));
+                        ++tries;
+                        d = retry_direction(T, lens_sample<true>(T, B, nullptr, u, v), rs.o0x, rs.o0y, rs.maxScale, rs.translation, rs.sn, rs.cs);
+                    }
+                }
+            }
+
+            // ---- the candidates' traces ------------------------------------------------------------------------------------
+            if (__ballot(cand) != 0ull && cand) {
+                cand = false;
+                uint32_t tirTry = 0;
+                bool ok;
+                if constexpr (FAST) {
+                    const V3 os = o, ds = d;
+                    bool unsure = false;
+                    ok = trace_fast(T.lensCount, dl, o, d, tirTry, unsure);
+                    if (unsure) {   // a clip too close to call: this try in the reference's arithmetic
+                        o = os; d = ds; tirTry = 0;
+                        ok = trace_strict(T.lensCount, dl, o, d, tirTry);
+                    }
+                } else {
+                    ok = trace_strict(T.lensCount, dl, o, d, tirTry);
+                }
+                tir += tirTry;
+                if (ok) {
+                    done = true;
+                    failed = tries > static_cast<uint32_t>(kMaxTries);   // a success at try 26 is still out of tries (zoic.cpp:1927, 1951)
+                } else if (tries == 0u && (rs.flags & kRetryDeadBit) != 0u) {
+                    done = true; failed = true; tries = 0xffu;
+                } else if (tries >= kOut) {
+                    done = true; failed = true;   // the partial state of try 26 (zoic.cpp:1951-1961)
+                } else {
+                    o = V3{rs.o0x, rs.o0y, T.originShift};
+                    searching = true;
+                    if (tries == 0u) rng = ray_stream(rngStates, T.seed, rayBase, idx);
+                    const float u = rng_unit(xor128(rng));
+                    const float v = rng_unit(xor128(rng));
+                    ++tries;
+                    d = retry_direction(T, lens_sample<true>(T, B, nullptr, u, v), rs.o0x, rs.o0y, rs.maxScale, rs.translation, rs.sn, rs.cs);
+                }
+            }
+
+            // ---- finished rays -----------------------------------------------------------------------------------------------
+            if (done) {
+                float w;
+                uint32_t flags;
+                if (tries == 0xffu) {   // retry-dead: retries 1 ... 26 die at interface 0 (the arithmetic of the pool kernels)
+                    const DeadRayEnd e = dead_ray_end<true>(T, B, nullptr, rs, ray_stream(rngStates, T.seed, rayBase, idx));
+                    o = e.o; d = e.d; w = e.w;
+                    flags = 1u | (e.tries << 1) | ((rs.flags & 1u) << 6);
+                    if (e.nanDraw) ++succ; else ++vign;
+                } else {
+                    w = failed ? 0.0f : 1.0f;
+                    if (T.exposureOn) w *= T.exposureMul;                                        // zoic.cpp:1981-1987
+                    flags = (tries > 0u ? 1u : 0u) | (tries << 1) | ((rs.flags & 1u) << 6);
+                    if (failed) ++vign; else ++succ;                                             // zoic.cpp:1951-1957
+                }
+                store_ray_record(out, idx, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);   // zoic.cpp:1960-1961
+                busy = false; searching = false; cand = false;
+            }
+        }
+    }
+    DeviceCounters *cs = counter_set(counters);
+    succ = wave_sum(succ); vign = wave_sum(vign); tir = wave_sum(tir);
+    if (cs && lane == 0u) {
+        if (succ) atomicAdd(&cs->succes, static_cast<unsigned long long>(succ));
+        if (vign) atomicAdd(&cs->vignetted, static_cast<unsigned long long>(vign));
+        if (tir) atomicAdd(&cs->tir, static_cast<unsigned long long>(tir));
+    }
+}
+
+// rows of the other lens models: invalid wavelengths -> a rejected record; the thin-lens kernel's count of that row is taken back
+__global__ __launch_bounds__(kSpecBlock) void spectral_reject_kernel(const float *__restrict__ lambdas, uint64_t n, RayRecord *__restrict__ out,
+                                                                     DeviceCounters *counters, int countsRays)
+{
+    uint32_t succ = 0, vign = 0;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kSpecBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSpecBlock + threadIdx.x; i < n; i += stride) {
+        if (spectral_valid(lambdas[i])) continue;
+        const uint32_t flags = out[i].flags;
+        if (countsRays) { if (((flags >> 1) & 31u) > static_cast<uint32_t>(kMaxTries)) ++vign; else ++succ; }
+        store_ray_record(out, i, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, kSpectralRejected);
+    }
+    DeviceCounters *cs = counter_set(counters);
+    succ = wave_sum(succ); vign = wave_sum(vign);
+    if (cs && (threadIdx.x & 63u) == 0u) {   // two's complement: the host sums the counter sets modulo 2^64
+        if (succ) atomicAdd(&cs->succes, 0ull - static_cast<unsigned long long>(succ));
+        if (vign) atomicAdd(&cs->vignetted, 0ull - static_cast<unsigned long long>(vign));
+    }
+}
+
+namespace {
+uint32_t spec_grid(uint64_t n, uint64_t raysPerBlock)
+{
+    const uint64_t blocks = (n + raysPerBlock - 1) / raysPerBlock;
+    return static_cast<uint32_t>(blocks < kSpecGridCap ? blocks : kSpecGridCap);
+}
+}  // namespace
+
+int launch_kolb_spectral(const KolbTable &table, const SpectralTable &spec, const BokehTables &bokeh, const float *d_samples,
+                         const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, RayRecord *out,
+                         DeviceCounters *d_counters, int mode, void *stream)
+{
+    if (n == 0) return 0;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const float4 *samples = reinterpret_cast<const float4 *>(d_samples);
+    const uint4 *rng = reinterpret_cast<const uint4 *>(d_rng);
+    const dim3 grid(spec_grid(n, static_cast<uint64_t>(kSpecChunk) * (kSpecBlock / 64)));
+    if (mode == 0)
+        hipLaunchKernelGGL(kolb_spectral_kernel<false>, grid, dim3(kSpecBlock), 0, s, table, spec, bokeh, samples, d_lambda, rng, rayBase, n, out, d_counters);
+    else
+        hipLaunchKernelGGL(kolb_spectral_kernel<true>, grid, dim3(kSpecBlock), 0, s, table, spec, bokeh, samples, d_lambda, rng, rayBase, n, out, d_counters);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_spectral_reject(const float *d_lambda, uint64_t n, RayRecord *out, DeviceCounters *d_counters, bool countsRays, void *stream)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(spectral_reject_kernel, dim3(spec_grid(n, kSpecBlock)), dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), d_lambda, n, out,
+                       d_counters, countsRays ? 1 : 0);
+    return static_cast<int>(hipGetLastError());
+}
+
+}  // namespace zoic
