@@ -11,7 +11,8 @@
 //   node_update         zoic.cpp:1575-1720  -> AiTextureLoad + zoic_camera_set_bokeh_image + zoic_camera_update
 //   node_finish         zoic.cpp:1723-1749  -> zoic_camera_get_counters + zoic_camera_destroy
 //   camera_create_ray   zoic.cpp:1752-1990  -> zoic_camera_create_ray(cam, input, output, tid)   (re-entrant per tid)
-//   camera_reverse_ray  zoic.cpp:1992-1995  -> zoic_camera_reverse_ray                           (false)
+//   camera_reverse_ray  zoic.cpp:1992-1995  -> zoic_camera_reverse_ray   (false, as the reference; with the opt-in parameter
+//                                              "reverseRay" the chief-ray projection of csrc/reverse.hpp: Ps written, true if projected)
 //   NodeLoader          zoic.cpp:1999-2007  -> same fields
 // The per-sample callback goes through the library's resident mailbox kernel (no launch per call: ~7.5 us per sample with one
 // render thread, ~0.8 M calls/s with 16 -- still ~20x below 16 threads of the CPU plug-in); a renderer that can hand over a
@@ -57,6 +58,9 @@ node_parameters
     AiParameterFlt("opticalVignettingDistance", 0.0f);
     AiParameterFlt("opticalVignettingRadius", 1.0f);
     AiParameterFlt("exposureControl", 0.0f);             // zoic.cpp:1562
+    // not a parameter of the reference: opt in to answering camera_reverse_ray (zoic_camera_set_reverse_projection).  Like the rest of
+    // this file it has never been built against a real Arnold SDK.
+    AiParameterBool("reverseRay", false);
 }
 
 node_initialize
@@ -103,6 +107,7 @@ node_update
                 zoic_camera_set_bokeh_image(data->cam, static_cast<int>(w), static_cast<int>(h), static_cast<int>(c), px.data());
         }
     }
+    zoic_camera_set_reverse_projection(data->cam, AiNodeGetBool(node, "reverseRay") ? 1 : 0);
     if (zoic_camera_update(data->cam, &p) != ZOIC_OK) {   // zoic.cpp:1589-1592, 1639-1642: message, abort, carry on
         AiMsgError("%s", zoic_last_error_string());
         AiRenderAbort();
@@ -140,7 +145,11 @@ camera_reverse_ray
     const NodeData *data = static_cast<const NodeData *>(AiNodeGetLocalData(node));
     float ps[2] = {Ps.x, Ps.y};
     const zoic_vec3 po = {Po.x, Po.y, Po.z};
-    return zoic_camera_reverse_ray(data ? data->cam : nullptr, &po, fov, ps, &relative_time) != 0;   // false, zoic.cpp:1992-1995
+    // false, zoic.cpp:1992-1995 -- unless "reverseRay" is on: then the projection (switched off, the call leaves ps as it is)
+    const bool projected = zoic_camera_reverse_ray(data ? data->cam : nullptr, &po, fov, ps, &relative_time) != 0;
+    Ps.x = ps[0];
+    Ps.y = ps[1];
+    return projected;
 }
 
 node_loader

@@ -17,7 +17,7 @@
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
  *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
- *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
+ *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
  *   - No entry point changes the calling thread's current HIP device.
@@ -51,7 +51,9 @@ extern "C" {
  *      Added later without a new number (additive: nothing existing changed shape or behaviour): zoic_ray_differential,
  *      zoic_ray_differentials_device and zoic_create_rays_arnold_differentials (traced ray differentials).
  *      Added later without a new number (additive): zoic_create_rays_spectral_device, zoic_camera_get_dispersion and
- *      zoic_camera_set_abbe_numbers (rays at a wavelength per ray: chromatic aberration); flag bit 7 of zoic_ray (wavelength rejected). */
+ *      zoic_camera_set_abbe_numbers (rays at a wavelength per ray: chromatic aberration); flag bit 7 of zoic_ray (wavelength rejected).
+ *      Added later without a new number (additive): zoic_project_points_device, zoic_project_point and
+ *      zoic_camera_set_reverse_projection (reverse projection; zoic_camera_reverse_ray answers only when opted in). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -357,9 +359,45 @@ zoic_status zoic_camera_create_rays_tile(zoic_camera *cam, uint32_t n, const zoi
 #define ZOIC_RESIDENT_MAX_SAMPLES 1048576u
 zoic_status zoic_create_rays_device_resident(zoic_camera *cam, uint32_t n, const float *d_samples, zoic_ray *d_rays, uint64_t ray_index_base,
                                              uint16_t tid);
-/* camera_reverse_ray, zoic.cpp:1992-1995: the reference returns false and writes nothing; so does this (returns 0). */
+/* camera_reverse_ray, zoic.cpp:1992-1995: the reference returns false and writes nothing; so does this (returns 0) by default.
+ * Opted in with zoic_camera_set_reverse_projection(cam, 1): returns flags & 1 of zoic_project_point and writes Ps (also when it
+ * returns 0: then (+0, +0)); fov is ignored and relative_time is not written.  A camera that has no successful update returns 0. */
 int zoic_camera_reverse_ray(const zoic_camera *cam, const zoic_vec3 *Po, float fov, float *Ps /* [2] */,
                             float *relative_time);
+/* ---- reverse projection: scene points to screen samples (opt-in; csrc/reverse.hpp has the full definition) ------------------
+ * Po is a point in the frame of the records the forward calls write (zoic_ray origin / dir after the reference's flips).  Ps = (sx, sy)
+ * is the screen sample the forward calls would take:
+ *   THINLENS   the sample whose lens-centre ray passes through Po: sx = Po.x / (-Po.z) / tan_fov, sy likewise; only for Po.z < 0.
+ *   RAYTRACED  the sensor point (sx sw/2, sy sw/2, originShift), sw = sensorWidth, of the CHIEF ray through Po: the ray through the centre
+ *              of the aperture stop, refracted at every interface (the near-vertex intersection of each sphere; the stop as the plane
+ *              through its vertex; of several roots the one continuous with the paraxial solution).  A point on the axis gives (+0, +0).
+ *              A camera outside the geometric domain of the FAST modes (negative focal-length rescale, or sensor in front of the rear
+ *              vertex: see zoic_precision) projects no point; lensModel NONE neither.
+ * Flags: bit 0 projected (Ps written); bit 1 the chief ray is clipped by some element's housing (Ps is still the chief ray's); bit 2
+ * the sensor radius lies beyond the exit-pupil LUT's last key (forward rays there carry zoic_ray flag bit 6); bits 8-11 when bit 0 is
+ * clear: the reason below.  A point that is not projected gets Ps = (+0, +0).
+ * The arithmetic is f32 with correctly rounded square roots and reciprocals, the same on the host and on the device in every
+ * precision mode: zoic_project_points_device and zoic_project_point give the same bits for the same point. */
+#define ZOIC_PROJECTED 0x1u
+#define ZOIC_PROJECT_CLIPPED 0x2u
+#define ZOIC_PROJECT_PAST_LUT 0x4u
+#define ZOIC_PROJECT_REASON(flags) (((flags) >> 8) & 0xFu)
+enum {
+    ZOIC_PROJECT_BEHIND = 1,         /* behind the lens (RAYTRACED: not in front of the front element's cap), or Po.z >= 0 (THINLENS) */
+    ZOIC_PROJECT_NO_ROOT = 2,        /* no chief ray: a sphere missed or total internal reflection on every candidate (or Ps overflows) */
+    ZOIC_PROJECT_NON_FINITE = 3,     /* a NaN or infinite coordinate */
+    ZOIC_PROJECT_MODEL_NONE = 4,     /* lensModel NONE */
+    ZOIC_PROJECT_OUTSIDE_DOMAIN = 5  /* RAYTRACED camera outside the geometric domain above */
+};
+/* n points (packed float3, device memory, 4-byte aligned) -> n (sx, sy) pairs (device memory, 8-byte aligned) and, unless d_flags is
+ * NULL, n flag words (device memory).  Works whatever zoic_camera_set_reverse_projection says.  Asynchronous on `stream`.
+ * ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL, misaligned or non-device pointer; n = 0 returns ZOIC_OK. */
+zoic_status zoic_project_points_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */, float *d_screen /* n x 2 */,
+                                       uint32_t *d_flags /* may be NULL */, void *stream);
+/* The host build of the same code for one point (no GPU round trip; works on a ZOIC_DEVICE_NONE camera).  flags may be NULL. */
+zoic_status zoic_project_point(const zoic_camera *cam, const zoic_vec3 *Po, float *Ps /* [2] */, uint32_t *flags);
+/* Off by default.  On: zoic_camera_reverse_ray answers with zoic_project_point (see there).  A _set_* call. */
+zoic_status zoic_camera_set_reverse_projection(zoic_camera *cam, int enable);
 
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins

@@ -1,0 +1,214 @@
+"""numpy f64 restatement of the reverse projection (zoic_amd/csrc/reverse.hpp) for the tests: the lens of ZoicCamera.info() as
+meridional (r, z) interfaces, the FORWARD chief ray of a sensor point (its own 1-D search for the ray through the stop's centre) and
+the REVERSE projection of a point (an independent 1-D search, on the angle of the ray leaving the point).
+
+Geometry, as the definition states it: interface i (trace order, rear first) has its vertex at computeLensCenters' summed thickness
+(f32 sums, zoic.cpp:963-969) and curvature 1/R; the stop is the plane through its vertex; the near-vertex intersection of every sphere;
+Snell with the media of the prescription (air in front of the front element and behind the rear one)."""
+import numpy as np
+
+F32 = np.float32
+
+
+class Lens:
+    """the interfaces of a RAYTRACED camera: info = ZoicCamera.info(), sensor_width = the camera's sensorWidth"""
+
+    def __init__(self, info, sensor_width):
+        el = info["elements"]
+        n = int(info["lensCount"])
+        self.n = n
+        self.stop = int(info["apertureElement"])
+        R = el[:n, 0].astype(F32)
+        th = el[:n, 1].astype(F32)
+        ior = el[:n, 2].astype(F32)
+        ap = el[:n, 3].astype(F32)
+        vtx = np.zeros(n, F32)
+        s = F32(0)
+        for i in range(n):
+            s = th[0] if i == 0 else F32(s + th[i])
+            vtx[i] = s
+        self.vtx = vtx.astype(np.float64)
+        self.curv = np.where(np.arange(n) == self.stop, 0.0, 1.0 / R.astype(np.float64))
+        self.ior_rear = ior.astype(np.float64)                                   # medium behind interface i
+        self.ior_front = np.append(ior[1:], F32(1)).astype(np.float64)          # medium in front of it
+        # the reference's clip (zoic.cpp:1114-1115), in f64
+        half = ap.astype(np.float64) * 0.5
+        h2 = half * half
+        ua = float(info["userApertureRadius"])
+        h2[self.stop] = min(h2[self.stop], float(F32(F32(ua) * F32(ua))))
+        self.housing2 = h2
+        self.origin_shift = float(info["originShift"])
+        self.half_sensor = float(F32(sensor_width) * F32(0.5))
+
+    def interface(self, i, x, z, ur, uz, forward):
+        """intersect and refract at interface i (vectorised over rays; absolute z); returns x, z, ur, uz, ok, clipped"""
+        c, zv = self.curv[i], self.vtx[i]
+        zr = z - zv
+        F = c * (x * x + zr * zr) + 2.0 * zr
+        B = uz + c * (x * ur + zr * uz)
+        disc = B * B - c * F
+        ok = disc >= 0.0
+        sq = np.sqrt(np.where(ok, disc, 0.0))
+        # the root on the vertex side (zoic.cpp:986): the larger sgn(R) z of the two, i.e. t = (-B + sq) / c going +z and
+        # (-B - sq) / c going -z, each in its form without cancellation
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if forward:
+                t = np.where(B >= 0, -F / (B + sq), (-B + sq) / c)
+            else:
+                t = np.where(B <= 0, -F / (B - sq), (-B - sq) / c)
+        hx, hz = x + t * ur, zr + t * uz
+        clipped = hx * hx > self.housing2[i]
+        nx, nz = c * hx, 1.0 + c * hz
+        if forward:                       # the normal against the ray (+z): -n
+            nx, nz = -nx, -nz
+            eta = self.ior_rear[i] / self.ior_front[i]
+        else:
+            eta = self.ior_front[i] / self.ior_rear[i]
+        cosi = -(ur * nx + uz * nz)
+        k2 = 1.0 - eta * eta * (1.0 - cosi * cosi)
+        ok &= k2 >= 0.0
+        g = eta * cosi - np.sqrt(np.where(k2 >= 0.0, k2, 0.0))
+        return hx, hz + zv, eta * ur + g * nx, eta * uz + g * nz, ok & np.isfinite(hx), clipped
+
+    def trace(self, idx, x, z, ur, uz, forward):
+        ok = np.ones(np.shape(x), bool)
+        clipped = np.zeros(np.shape(x), bool)
+        for i in idx:
+            x, z, ur, uz, k, c = self.interface(i, x, z, ur, uz, forward)
+            ok &= k
+            clipped |= c
+        return x, z, ur, uz, ok, clipped
+
+    # ---- forward: sensor height rs -> the chief ray leaving the front element (trace frame)
+    def forward_chief(self, rs, iters=60):
+        """rs: (m,) signed sensor heights.  Returns (x, z, ur, uz) at the front element (trace frame, the ray going +z), ok, clipped."""
+        rs = np.asarray(rs, np.float64)
+        zs = self.origin_shift
+        rear = list(range(0, self.stop + 1))
+
+        def stop_height(a):
+            ur, uz = np.sin(a), np.cos(a)
+            x, z, ur, uz, ok, _ = self.trace(rear, rs, np.full_like(rs, zs), ur, uz, True)
+            return x, ok
+        a = np.arctan2(-rs, self.vtx[self.stop] - zs)      # aimed at the stop's centre past the rear group
+        for _ in range(iters):
+            f, ok = stop_height(a)
+            h = 1e-7
+            fp, _ = stop_height(a + h)
+            fm, _ = stop_height(a - h)
+            d = (fp - fm) / (2 * h)
+            step = np.where(ok & (d != 0), -f / np.where(d != 0, d, 1.0), 0.0)
+            a = a + np.clip(step, -0.05, 0.05)
+        f, ok = stop_height(a)
+        ok &= np.abs(f) < 1e-11
+        ur, uz = np.sin(a), np.cos(a)
+        x, z, ur, uz, ok2, clipped = self.trace(range(self.n), rs, np.full_like(rs, zs), ur, uz, True)
+        return (x, z, ur, uz), ok & ok2, clipped
+
+    def entrance_pupil(self):
+        """paraxial entrance pupil z (trace frame): a marginal-angle ray from the stop's centre through the front group"""
+        y, u, z = 0.0, 1e-3, self.vtx[self.stop]
+        for i in range(self.stop + 1, self.n):
+            y += u * (self.vtx[i] - z)
+            z = self.vtx[i]
+            # n' u' = n u + y (n' - n) / R: the centre of curvature lies at vertex - R
+            n1, n2 = self.ior_rear[i], self.ior_front[i]
+            u = (n1 * u + y * (n2 - n1) * self.curv[i]) / n2
+        return z - y / u if self.stop + 1 < self.n else z
+
+    # ---- reverse: points (trace frame, meridional) -> sensor height of the chief ray
+    def reverse_chief(self, rq, zq, iters=80):
+        """rq >= 0, zq: points in the trace frame.  Returns the sensor heights (signed along rq), ok."""
+        rq = np.asarray(rq, np.float64)
+        zq = np.asarray(zq, np.float64)
+        front = list(range(self.n - 1, self.stop - 1, -1))
+        zep = self.entrance_pupil()
+
+        def stop_height(a):      # the ray leaving Q at angle a from -z, towards the lens
+            ur, uz = np.sin(a), -np.cos(a)
+            x, z, ur, uz, ok, _ = self.trace(front, rq, zq, ur, uz, False)
+            return x, ok
+        a = np.arctan2(-rq, zq - zep)
+        for _ in range(iters):
+            f, ok = stop_height(a)
+            h = 1e-9
+            d = (stop_height(a + h)[0] - stop_height(a - h)[0]) / (2 * h)
+            step = np.where(ok & (d != 0), -f / np.where(d != 0, d, 1.0), 0.0)
+            a = a + np.clip(step, -0.05, 0.05)
+        f, ok = stop_height(a)
+        ok &= np.abs(f) < 1e-10
+        ur, uz = np.sin(a), -np.cos(a)
+        x, z, ur, uz, ok2, _ = self.trace(range(self.n - 1, -1, -1), rq, zq, ur, uz, False)
+        t = (self.origin_shift - z) / uz
+        return x + t * ur, ok & ok2
+
+
+def chief_points(lens, sx, sy, depths):
+    """Points on the chief rays of screen samples (sx, sy), in the frame of the records (Po = -Q): for each depth d, the point of
+    the ray leaving the front element with Po.z = -d (trace frame z = d).  Returns (points (k, m, 3), ok (m,), clipped (m,),
+    exit z of the rays in the trace frame (m,)) for the k depths."""
+    sx = np.asarray(sx, np.float64)
+    sy = np.asarray(sy, np.float64)
+    ox, oy = sx * lens.half_sensor, sy * lens.half_sensor
+    rs = np.hypot(ox, oy)
+    (x, z, ur, uz), ok, clipped = lens.forward_chief(rs)
+    ok &= uz > 0
+    ca = np.where(rs > 0, ox / np.where(rs > 0, rs, 1), 1.0)
+    sa = np.where(rs > 0, oy / np.where(rs > 0, rs, 1), 0.0)
+    pts = []
+    for d in depths:
+        dd = np.broadcast_to(np.asarray(d, np.float64), z.shape)
+        t = (dd - z) / np.where(uz > 0, uz, 1.0)
+        r = x + t * ur
+        pts.append(np.stack([-(r * ca), -(r * sa), -dd], 1))
+    return np.stack(pts), ok, clipped, z
+
+
+def thin_project(po, tan_fov):
+    po = np.asarray(po, np.float64)
+    return po[:, 0] / -po[:, 2] / tan_fov, po[:, 1] / -po[:, 2] / tan_fov
+
+
+def kolb_point_set(info, sensor_width, focal_distance, grid=64):
+    """The accuracy set of one RAYTRACED camera: a grid x grid lattice of screen samples over [-1, 1]^2 whose f64 chief ray is unclipped,
+    and points on each chief ray at four depths (trace-frame z): just in front of the front element, focalDistance, 10 x focalDistance
+    and 1e4 cm.  A point is kept only where the chief rays at its depth are still ordered from the axis out to its own (the definition
+    takes the root continuous with the axis: beyond a fold of the chief-ray family -- the caustic of a strongly aberrated pupil -- the
+    point's own sample is not that root).  Returns (points (m,3) float32 in the frame of the records, samples (m,2), depth index (m,))."""
+    L = Lens(info, sensor_width)
+    g = (np.arange(grid) + 0.5) / grid * 2.0 - 1.0
+    sx, sy = [a.ravel() for a in np.meshgrid(g, g)]
+    _, ok, clipped, zex = chief_points(L, sx, sy, [1.0])
+    sel = ok & ~clipped
+    front = max(L.vtx[-1], float(zex[sel].max())) + 1e-3
+    depths = [front, float(focal_distance), 10.0 * float(focal_distance), 1e4]
+    pts, ok, clipped, _ = chief_points(L, sx, sy, depths)
+    sel &= ok & ~clipped
+    rs = np.hypot(sx, sy) * L.half_sensor
+    rho = np.linspace(0.0, float(rs[sel].max()) * 1.0001, 4001)[1:]
+    (x, z, ur, uz), rok, _ = L.forward_chief(rho)
+    P, S, D = [], [], []
+    for k, d in enumerate(depths):
+        r = x + (d - z) / uz * ur
+        good = rok & (uz > 0) & (np.diff(np.concatenate([[0.0], r])) * np.sign(r[0]) > 0)
+        fold = rho[np.argmin(good)] if not good.all() else np.inf
+        keep = sel & (rs < fold)
+        # and where the f32 rounding of the point moves its sample by less than 1e-6 (near a fold the map is singular)
+        slope = np.interp(rs, rho, np.abs(np.gradient(r, rho)))
+        keep &= np.linalg.norm(pts[k], axis=1) * 2.0 ** -24 <= 1e-6 * slope * L.half_sensor
+        P.append(pts[k][keep])
+        S.append(np.stack([sx[keep], sy[keep]], 1))
+        D.append(np.full(keep.sum(), k))
+    return np.concatenate(P).astype(F32), np.concatenate(S), np.concatenate(D)
+
+
+def thin_point_set(tan_fov, focal_distance, grid=64):
+    """the same lattice and depths for a thin lens: Po = (sx tan_fov d, sy tan_fov d, -d)"""
+    g = (np.arange(grid) + 0.5) / grid * 2.0 - 1.0
+    sx, sy = [a.ravel() for a in np.meshgrid(g, g)]
+    P, S, D = [], [], []
+    for k, d in enumerate([1e-2, float(focal_distance), 10.0 * float(focal_distance), 1e4]):
+        P.append(np.stack([sx * tan_fov * d, sy * tan_fov * d, np.full_like(sx, -d)], 1))
+        S.append(np.stack([sx, sy], 1))
+        D.append(np.full(sx.size, k))
+    return np.concatenate(P).astype(F32), np.concatenate(S), np.concatenate(D)

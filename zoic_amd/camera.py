@@ -392,11 +392,63 @@ class ZoicCamera:
         return o
 
     def reverse_ray(self, Po=(0.0, 0.0, 0.0), fov=0.0):
-        """camera_reverse_ray (zoic.cpp:1992-1995): always False, nothing written."""
+        """camera_reverse_ray (zoic.cpp:1992-1995): False, nothing written -- unless set_reverse_projection(True): then whether Po
+        projects (zoic_project_point's flag bit 0)."""
         po = _capi.Vec3(*[float(v) for v in Po])
         ps = (C.c_float * 2)(0.0, 0.0)
         t = C.c_float(0.0)
         return bool(self._lib.zoic_camera_reverse_ray(self._h, C.byref(po), float(fov), ps, C.byref(t)))
+
+    def set_reverse_projection(self, enable):
+        """Opt in (True) or out (False, the default) of answering reverse_ray / camera_reverse_ray with the projection."""
+        self._check(self._lib.zoic_camera_set_reverse_projection(self._h, 1 if enable else 0))
+
+    def project_point(self, Po):
+        """Reverse projection of one point on the host (zoic_project_point): (sx, sy, flags).  Po in the frame of the records the
+        forward calls write.  flags bit 0: projected; bit 1: the chief ray is clipped; bit 2: beyond the exit-pupil LUT; bits 8-11:
+        the reason a point is not projected (csrc/reverse.hpp).  Works on a tables-only camera (device=-1)."""
+        po = _capi.Vec3(*[float(v) for v in Po])
+        ps = (C.c_float * 2)(0.0, 0.0)
+        f = C.c_uint32(0)
+        self._check(self._lib.zoic_project_point(self._h, C.byref(po), ps, C.byref(f)))
+        return float(ps[0]), float(ps[1]), int(f.value)
+
+    def project_points(self, points, out=None, flags=None, stream=None):
+        """Reverse projection of (n,3) float32 points (zoic_project_points_device): returns (screen (n,2) float32, flags (n,) int32).
+
+        numpy in  -> the points are copied to the camera's device through torch, the call waits and returns numpy arrays (out and
+                     flags must be None there).
+        torch device tensor in -> asynchronous on `stream` (default: torch's current stream); out / flags: optional (n,2) float32 and
+                     (n,) int32 tensors on the points' device to write into."""
+        import torch
+        if not _is_torch(points):
+            if out is not None or flags is not None:
+                raise ValueError("out and flags are for torch points")
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("points must be (n, 3)")
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                self._check(self._lib.zoic_project_points_device(self._h, a.shape[0], None, None, None, None))
+            dev = torch.device("cuda", self.device)
+            scr, fl = self.project_points(torch.from_numpy(a).to(dev))
+            torch.cuda.synchronize(dev)
+            return scr.cpu().numpy(), fl.cpu().numpy()
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
+            raise ValueError("points must be a contiguous (n,3) float32 device tensor")
+        if points.device.index != self.device:
+            raise ValueError("points live on cuda:%s but this camera is bound to device %d" % (points.device.index, self.device))
+        n = points.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=points.device)
+        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
+            raise ValueError("out must be a contiguous (n,2) float32 tensor on the points' device")
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.int32, device=points.device)
+        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != points.device:
+            raise ValueError("flags must be a contiguous (n,) int32 tensor on the points' device")
+        st = stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream
+        self._check(self._lib.zoic_project_points_device(self._h, n, points.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
+        return out, flags
 
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
         """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1).

@@ -35,6 +35,7 @@
 #include "kernels.hpp"
 #include "mailbox.hpp"
 #include "spectral.hpp"
+#include "reverse.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
 
@@ -287,6 +288,8 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     std::vector<zoic_tile *> liveTiles;
     std::atomic<int> waitMode{ZOIC_WAIT_SPIN};   // zoic_camera_set_wait_mode: how a render thread waits for the resident kernel
     std::vector<float> abbeOverride;             // zoic_camera_set_abbe_numbers: V-numbers in file order (empty: the prescription's own)
+    ReverseTable reverse{};                      // reverse.hpp: the projection table of the tables above (filled by every successful update)
+    bool reverseOn = false;                      // zoic_camera_set_reverse_projection: zoic_camera_reverse_ray answers with it
 
     TidState *tid_state(uint16_t tid);
     CallContext *lease_context(hipError_t &err);
@@ -783,6 +786,33 @@ void fill_spectral(const zoic_camera *cam, SpectralTable &W)
     }
 }
 
+// the reverse projection's table (reverse.hpp) of the camera's current tables
+void fill_reverse(zoic_camera *cam)
+{
+    const zoic_params &p = cam->params.p;
+    const LensSystem &L = cam->lens;
+    if (p.lensModel != ZOIC_RAYTRACED) {
+        fill_reverse_table(cam->reverse, p.lensModel == ZOIC_THINLENS ? 0 : 2, cam->tanFov, 0, nullptr, nullptr, nullptr, nullptr, -1, 0.0f,
+                           0.0f, 0.0f, false, 0, false);
+        return;
+    }
+    const int n = static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces));
+    float radius[kMaxSurfaces], thickness[kMaxSurfaces], ior[kMaxSurfaces], aperture[kMaxSurfaces];
+    for (int i = 0; i < n; ++i) {
+        radius[i] = L.rows[i].radius; thickness[i] = L.rows[i].thickness; ior[i] = L.rows[i].ior; aperture[i] = L.rows[i].aperture;
+    }
+    fill_reverse_table(cam->reverse, 1, cam->tanFov, n, radius, thickness, ior, aperture, L.apertureElement, L.userApertureRadius,
+                       L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain);
+}
+
+// device (or managed) memory: what the batch projection may read and write
+bool is_device_memory(const void *ptr)
+{
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.isManaged;
+}
+
 }  // namespace
 
 static void detach_tiles(zoic_camera *cam);   // (defined with the tile entry points below)
@@ -1109,6 +1139,7 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
         exposure_terms(p->exposureControl, t.exposureMul, t.exposureOn);
         t.seed = cam->seed;
     }
+    fill_reverse(cam);   // (RAYTRACED: fastDomain is still the geometric test here; the self-check below may narrow it)
     cam->updated = true;
     // the FAST modes are kept only for a camera they are good for (fast_self_check above; the geometric test comes first).
     // The verdict depends on the lens tables, the LUT and the bokeh tables only: an update that rebuilt none of them (exposure,
@@ -1774,9 +1805,47 @@ zoic_status zoic_create_rays_device_resident(zoic_camera *cam, uint32_t n, const
 
 int zoic_camera_reverse_ray(const zoic_camera *cam, const zoic_vec3 *Po, float fov, float *Ps, float *relative_time)
 {
-    // camera_reverse_ray, zoic.cpp:1992-1995: `return false;` -- nothing is written
-    (void)cam; (void)Po; (void)fov; (void)Ps; (void)relative_time;
-    return 0;
+    // camera_reverse_ray, zoic.cpp:1992-1995: `return false;` -- nothing is written.  Opted in (zoic_camera_set_reverse_projection):
+    // the projection of Po (reverse.hpp); fov is ignored and relative_time is not written.
+    (void)fov; (void)relative_time;
+    if (!cam || !cam->reverseOn || !cam->updated || !Po || !Ps) return 0;
+    float s[2];
+    const uint32_t flags = project_point(cam->reverse, Po->x, Po->y, Po->z, s[0], s[1]);
+    Ps[0] = s[0]; Ps[1] = s[1];
+    return static_cast<int>(flags & kRevProjected);
+}
+
+zoic_status zoic_camera_set_reverse_projection(zoic_camera *cam, int enable)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    cam->reverseOn = enable != 0;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_project_point(const zoic_camera *cam, const zoic_vec3 *Po, float *Ps, uint32_t *flags)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!Po || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "Po and Ps must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    const uint32_t f = project_point(cam->reverse, Po->x, Po->y, Po->z, Ps[0], Ps[1]);
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_project_points_device(zoic_camera *cam, uint64_t n, const float *d_points, float *d_screen, uint32_t *d_flags, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_points || (reinterpret_cast<uintptr_t>(d_points) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points must be non-NULL and 4-byte aligned");
+    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
+    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    if (!is_device_memory(d_points) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points, d_screen and d_flags must be device memory");
+    const int rc = launch_project_points(cam->reverse, d_points, n, d_screen, d_flags, stream);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
 }
 
 zoic_status zoic_host_alloc(size_t bytes, void **out)
