@@ -19,26 +19,31 @@ def surfaces(info):
     return np.stack([center, (r * r).astype(F32), np.where(r < 0, F32(-1), F32(1)), eta], 1).astype(F32)
 
 
+def _interface(o, d, c, r2, sg, eta):
+    """one interface of the f64 trace: (hit point, refracted direction, cos of the incidence angle, cos of the refraction angle)"""
+    u = d / np.linalg.norm(d, axis=1, keepdims=True)
+    L = np.stack([-o[:, 0], -o[:, 1], c - o[:, 2]], 1)
+    tca = (L * u).sum(1)
+    d2 = (L * L).sum(1) - tca * tca
+    thc = np.sqrt(np.abs(r2 - d2))
+    t = tca + thc * sg
+    hit = o + u * t[:, None]
+    cv = np.stack([-hit[:, 0], -hit[:, 1], c - hit[:, 2]], 1)
+    N = cv / np.linalg.norm(cv, axis=1, keepdims=True) * sg
+    c1 = -(u * N).sum(1)
+    cs2 = eta * eta * (1.0 - c1 * c1)
+    ct = np.sqrt(np.abs(1.0 - cs2))
+    k = eta * c1 - ct
+    return hit, u * eta + N * k[:, None], c1, ct
+
+
 def trace(surf, o, d):
     """f64 trace of (n,3) origins / directions through every interface (no clip: the rays are known to pass); returns the
     traced (o, d) BEFORE the final flip"""
     o = np.asarray(o, np.float64).copy()
     d = np.asarray(d, np.float64).copy()
     for c, r2, sg, eta in np.asarray(surf, np.float64):
-        u = d / np.linalg.norm(d, axis=1, keepdims=True)
-        L = np.stack([-o[:, 0], -o[:, 1], c - o[:, 2]], 1)
-        tca = (L * u).sum(1)
-        d2 = (L * L).sum(1) - tca * tca
-        thc = np.sqrt(np.abs(r2 - d2))
-        t = tca + thc * sg
-        hit = o + u * t[:, None]
-        cv = np.stack([-hit[:, 0], -hit[:, 1], c - hit[:, 2]], 1)
-        N = cv / np.linalg.norm(cv, axis=1, keepdims=True) * sg
-        c1 = -(u * N).sum(1)
-        cs2 = eta * eta * (1.0 - c1 * c1)
-        k = eta * c1 - np.sqrt(np.abs(1.0 - cs2))
-        d = u * eta + N * k[:, None]
-        o = hit
+        o, d, _, _ = _interface(o, d, c, r2, sg, eta)
     return o, d
 
 
@@ -153,3 +158,39 @@ def kolb_start(oc, params, samples, tries, states, oracle_lib):
         Lxy = np.stack([lx * cs - ly * sn, lx * sn + ly * cs], 1).astype(F32)
     d0 = np.stack([Lxy[:, 0] - o0[:, 0], Lxy[:, 1] - o0[:, 1], np.full(len(samples), -el[0, 1], F32)], 1).astype(F32)
     return o0, d0
+
+
+def min_cos_incidence(surf, o, d):
+    """(n,) smallest |cos i| of each ray's f64 trace (trace's arithmetic) over every interface: the conditioning of its
+    Jacobian.  Refraction maps a change of the incidence angle by 1 / cos(t) and the hit point moves by 1 / cos(i) per unit of
+    the ray's angle, so a grazing hit anywhere makes the ray's central differences (and its f32 derivatives) unreliable."""
+    o = np.asarray(o, np.float64).copy()
+    d = np.asarray(d, np.float64).copy()
+    worst = np.ones(len(o))
+    for c, r2, sg, eta in np.asarray(surf, np.float64):
+        o, d, c1, ct = _interface(o, d, c, r2, sg, eta)
+        worst = np.minimum(worst, np.minimum(np.abs(c1), ct))
+    return worst
+
+
+def replay_and_restatement(oc, o0, d0, origin, direction):
+    """Checks of the start rays kolb_start rebuilt, against the records (origin, direction: (n,3) f32, flipped as stored):
+    replay -- (n,) bool: the oracle's own f32 trace (zo_trace_record, traceThroughLensElements) from (o0, d0) gives the record bit
+    for bit, i.e. (o0, d0) IS the try the reference traced;  eo, ed -- (n,) relative errors of the f64 restatement (trace) against
+    the records.  Where the replay holds and the restatement misses, the gap is the f32 rounding of the reference's own trace."""
+    o0 = np.asarray(o0, F32)
+    d0 = np.asarray(d0, F32)
+    replay = np.zeros(len(o0), bool)
+    for i in range(len(o0)):
+        ok, _, o, d = oc.trace_record(o0[i], d0[i])
+        replay[i] = ok and np.array_equal((o * F32(-1)).view(np.uint32), np.asarray(origin[i], F32).view(np.uint32)) and \
+            np.array_equal((d * F32(-1)).view(np.uint32), np.asarray(direction[i], F32).view(np.uint32))
+    ro, rd = trace(surfaces(oc.lens_table()), o0, d0)
+    eo = np.linalg.norm(-ro - origin, axis=1) / np.linalg.norm(origin, axis=1)
+    ed = np.linalg.norm(-rd - direction, axis=1) / np.linalg.norm(direction, axis=1)
+    return replay, eo, ed
+
+
+def restatement_holds(eo, ed):
+    """_check_kolb's criterion for the f64 restatement reproducing the records (tests/test_differentials_gpu.py)"""
+    return bool(np.median(eo) < 1e-5 and np.median(ed) < 1e-5 and np.percentile(ed, 99.9) < 1e-4)

@@ -1,0 +1,245 @@
+"""Shared generators of the fuzz tests (a plain helper module, imported by the test files): machine-made prescriptions, random
+camera parameters, random bokeh images, the hostile sample table and the oracle run at a wavelength per ray.
+
+Every generator is a pure function of its arguments (numpy RandomState streams seeded by the caller), so a hypothesis example
+replays the same camera whichever test draws it."""
+import os
+import zlib
+
+import numpy as np
+
+from zoic_amd import RAYTRACED, lens_path
+from zoic_amd.workloads import hexagon_bokeh
+
+from spectral_ref import spectral_iors
+
+# every shipped prescription with an aperture row (zoic rejects a lens without one)
+LENSES = ["double_gauss_f2.0.dat", "tessar_f2.8.dat", "fisheye_muller_f4.0.dat", "petzval_f1.25.dat", "triplet_f2.5.dat", "mori_f2.8.dat"]
+
+# samples nobody should send (test_hostile_sample_fuzz): zeros of both signs, 0.5 (the disk mapping's 0/0), 1.0 and its
+# neighbours, negative and > 1 lens samples, denormals, 1e30, infinities, NaN
+HOSTILE_SAMPLES = np.array([0.0, -0.0, 0.5, 1.0, -1.0, 0.99999994, 1.0000001, 0.49999997, 0.50000006, 1e-40, -1e-40, 1e-30, 1e30, -1e30,
+                            np.inf, -np.inf, np.nan, 2.0, -3.0, 0.25, 0.75, 1e-8, 0.125, 3.875 / 1.8, 4.0], np.float32)
+
+# wavelengths at and around both ends of the valid range [360, 830] nm and the d-line, and ones the library must reject
+LAMBDA_EDGES = np.array([360.0, np.nextafter(np.float32(360.0), np.float32(np.inf)), 830.0, np.nextafter(np.float32(830.0), np.float32(0.0)),
+                         587.5618], np.float32)
+LAMBDA_HOSTILE = np.array([np.nan, -np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-40, -500.0, 1e38, 359.9, 830.1,
+                           np.nextafter(np.float32(360.0), np.float32(0.0)), np.nextafter(np.float32(830.0), np.float32(np.inf))], np.float32)
+
+ABBE_RANGE = (20.0, 90.0)
+SURGERIES = ["keep", "keep", "drop", "double", "drop2", "double2"]   # of the new fuzzers' lenses (lens_args)
+
+REAR_ELEMENT_LENS = """# TESSAR with a strongly curved last surface: housing radius a = 8.25 mm on a sphere of |R| = {r} mm
+42.97	9.8	1.691	54.7	19.2
+-115.33	2.1	1.549	45.4	19.2
+306.84	4.16	0.0	0.0	19.2
+0.0	4.0	0.0	0.0	15.0
+-59.060	1.87	1.64	34.6	17.3
+40.93	10.64	0.0	0.0	17.3
+183.92	7.050	1.691	54.7	16.5
+{radius}	{back}	0.0	0.0	16.5
+"""
+REAR_ELEMENT_CASES = [(-9.0, 20.0), (-8.6, 12.0), (9.0, 20.0), (-12.0, 30.0), (8.4, 9.0)]   # (radius, back focus)
+
+
+def examples(name, default):
+    """hypothesis example count of one fuzzer: its own variable, else ZOIC_FUZZ_EXAMPLES, else `default`"""
+    return int(os.environ.get(name, os.environ.get("ZOIC_FUZZ_EXAMPLES", str(default))))
+
+
+def rows_of(name):
+    """the rows of a shipped prescription, or of prescription text (a string holding a newline)"""
+    rows = []
+    for line in (name.splitlines() if "\n" in name else open(lens_path(name))):
+        line = line.strip()
+        if not line or line.startswith("#"):
+            continue
+        rows.append([float(t) for t in line.replace(",", " ").replace(";", " ").replace(":", " ").split()])
+    return rows
+
+
+class MachineLens:
+    """a machine-made prescription: text (file order, front first) and, for a four-column lens drawn with abbe=True, the V-numbers
+    to give the camera through set_abbe_numbers (None otherwise: five-column rows carry theirs in the V column)"""
+
+    def __init__(self, text, abbe=None):
+        self.text = text
+        self.abbe = abbe
+
+    def load(self, cam, oc=None):
+        cam.set_lens_text(self.text)
+        if self.abbe is not None:
+            cam.set_abbe_numbers(self.abbe)
+        if oc is not None:
+            oc.set_lens_text(self.text)
+
+
+def perturbed_prescription(lens, seed, amount, surgery, abbe=False):
+    """A shipped prescription with every radius, thickness, index and aperture moved by up to +-amount (relative), an element
+    dropped or doubled when surgery says so ("keep", "drop", "double"; "drop2" / "double2" do it twice).  abbe=True: every glass also gets a random V-number in
+    ABBE_RANGE, drawn from a stream of its own so that the geometry is the abbe=False lens of the same arguments."""
+    rs = np.random.RandomState(seed)
+    rows = rows_of(lens)
+    for _ in range(2 if surgery.endswith("2") else 1):    # "drop2" / "double2": twice (interface counts 5 ... 14)
+        stop = [i for i, r in enumerate(rows) if r[0] == 0.0]
+        glass = [i for i in range(len(rows)) if i not in stop]
+        if surgery.startswith("drop") and len(glass) > 3:
+            del rows[glass[rs.randint(len(glass))]]
+        elif surgery.startswith("double"):
+            i = glass[rs.randint(len(glass))]
+            rows.insert(i, list(rows[i]))
+    vs = np.random.RandomState(seed ^ 0x5A5A5)
+    V = vs.uniform(ABBE_RANGE[0], ABBE_RANGE[1], len(rows)).astype(np.float32) if abbe else None
+    text = ""
+    four = False
+    for k, r in enumerate(rows):
+        r = list(r)
+        ap = len(r) - 1                                   # 4 columns: radius thickness ior aperture; 5: ... abbe aperture
+        f = 1.0 + amount * (2.0 * rs.rand(len(r)) - 1.0)
+        r[0] *= f[0]; r[1] *= f[1]; r[ap] *= f[ap]
+        if r[2] > 1.0:
+            r[2] = 1.0 + (r[2] - 1.0) * f[2]
+        if abbe and len(r) == 5:
+            r[3] = float(V[k]) if r[2] > 1.0 else 0.0
+        four = len(r) == 4
+        text += "\t".join("%.6g" % v for v in r) + "\n"
+    return MachineLens(text, V if (abbe and four) else None)
+
+
+def camera_strategy(st, models=(RAYTRACED,)):
+    """the random-camera draw: focal length, f-stop, sensor width, focus distance, LUT switch, lens model, bokeh image (None or
+    (h, w, kind, seed))"""
+    image = st.one_of(st.none(), st.none(), st.tuples(st.integers(2, 96), st.integers(2, 96), st.sampled_from(["noise", "spots", "gaps"]),
+                                                      st.integers(0, 2 ** 16)))
+    return st.fixed_dictionaries(dict(focalLength=st.floats(2.0, 12.0, width=32), fStop=st.floats(1.25, 11.0, width=32),
+                                      sensorWidth=st.floats(1.0, 7.5, width=32), focalDistance=st.floats(20.0, 2000.0, width=32),
+                                      kolbSamplingLUT=st.booleans(), lensModel=st.sampled_from(list(models)), image=image))
+
+
+def bokeh_image(h, w, kind, seed):
+    """(h, w, 3) float32 luminance image: noise, a few bright spots on a dark floor, or noise with black rows and columns"""
+    rs = np.random.RandomState(seed)
+    if kind == "spots":
+        lum = 1e-4 * rs.rand(h, w).astype(np.float32)
+        for _ in range(4):
+            lum[rs.randint(h), rs.randint(w)] = 1.0
+    else:
+        lum = rs.rand(h, w).astype(np.float32)
+        if kind == "gaps":
+            lum[rs.rand(h) < 0.3, :] = 0.0
+            lum[:, rs.rand(w) < 0.3] = 0.0
+            if not (lum > 0).any():
+                lum[h // 2, w // 2] = 1.0
+    return np.repeat(lum[:, :, None], 3, axis=2).astype(np.float32)
+
+
+def camera_params(draw, tag):
+    """(update() keyword arguments, bokeh image or None) of one camera_strategy draw; tag names the in-memory bokeh image"""
+    p = {k: v for k, v in draw.items() if k != "image"}
+    p["sensorHeight"] = p["sensorWidth"] / 1.5
+    img = None
+    if draw["image"] is not None:
+        h, w, kind, seed = draw["image"]
+        img = bokeh_image(h, w, kind, seed)
+        p.update(useImage=True, bokehPath="mem:%s_%dx%d_%s_%d" % (tag, w, h, kind, seed))
+    else:
+        p["useImage"] = False
+    return p, img
+
+
+def update_both(cam, oc, p, oracle_lib):
+    """update the camera and the oracle with the same parameters: (library error class, oracle error class), None where it took them"""
+    perr = oerr = None
+    try:
+        cam.update(**p)
+    except Exception as e:  # noqa: BLE001
+        perr = getattr(e, "status_name", type(e).__name__).replace("ZOIC_ERR_", "")
+    if oc is not None:
+        try:
+            oc.update(**p)
+        except oracle_lib.OracleError as e:
+            oerr = oracle_lib.ERR_NAMES[e.code]
+    return perr, oerr
+
+
+def _oracle_spectral(oracle_lib, p, dispersion, s, lam, states, lens_text=None, image=None):
+    """the oracle camera, group by group: each wavelength's n_i written into its lens table (zo_lenses) after update, restored after.
+    lens_text / image: the prescription text and bokeh image of a camera that was given them (default: p's lens file, the
+    hexagon when p asks for an image)"""
+    oc = oracle_lib.OracleCamera()
+    if lens_text is not None:
+        oc.set_lens_text(lens_text)
+    if p.get("useImage"):
+        oc.set_bokeh_image(hexagon_bokeh() if image is None else image)
+    oc.update(**p)
+    L = oc._L
+    count = L.zo_lens_count(oc._h)
+    le = L.zo_lenses(oc._h)
+    nd = np.array([le[i].ior for i in range(count)], np.float32)
+    assert np.array_equal(nd, dispersion["ior_d"])
+    n = len(s)
+    planes = np.zeros((7, n), np.float32)
+    flags = np.zeros(n, np.uint8)
+    before = oc.counters()
+    for w in np.unique(lam):
+        rows = np.nonzero(lam == w)[0]
+        ior = spectral_iors(nd, dispersion["cauchy_b"], w)
+        for i in range(count):
+            le[i].ior = float(ior[i])
+        r = oc.create_rays(s[rows], rng_states=states[rows])
+        for i in range(count):
+            le[i].ior = float(nd[i])
+        planes[:, rows] = r["planes"]
+        flags[rows] = r["flags"]
+    after = oc.counters()
+    oc.close()
+    return dict(planes=planes, flags=flags), {k: after[k] - before[k] for k in after}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def same_bits(a, b):
+    """elementwise: identical bits, or NaN on both sides"""
+    return (bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))
+
+
+
+def lens_strategy(st, rear=False):
+    """a machine-made lens draw: a 32-bit key that lens_args turns into the arguments of perturbed_prescription; rear=True mixes in the
+    near-hemispherical rear elements of REAR_ELEMENT_CASES (drawn unperturbed: amount 0, surgery "keep")"""
+    shipped = st.integers(0, 2 ** 32 - 1)
+    if not rear:
+        return shipped
+    return st.one_of(shipped, shipped, shipped, st.sampled_from(range(len(REAR_ELEMENT_CASES))).map(lambda k: -1 - k))
+
+
+# explicit lenses every new fuzzer runs besides its draws (hypothesis @example): the fewest and the most interfaces the generator
+# makes -- a triplet with two elements dropped (5) and a fisheye with two doubled (14) -- behind EXAMPLE_CAMERA
+EXAMPLE_LENSES = [("triplet_f2.5.dat", 1, 0.05, "drop2"), ("fisheye_muller_f4.0.dat", 1, 0.05, "double2")]
+EXAMPLE_CAMERA = dict(focalLength=5.0, fStop=4.0, sensorWidth=3.0, focalDistance=200.0, kolbSamplingLUT=True, lensModel=RAYTRACED, image=None)
+
+
+def lens_args(key, *salt):
+    """(prescription, seed, amount, surgery) of a lens_strategy key.  hypothesis' derandomized examples reuse a drawn value with the
+    others changed, so a choice among a few lenses taken from the key alone clusters on some of them: the key is hashed together
+    with the rest of the example (salt) first.  A tuple key is taken as the arguments themselves."""
+    if isinstance(key, tuple):     # an explicit lens (hypothesis @example): the arguments themselves
+        return key
+    if key < 0:
+        r, b = REAR_ELEMENT_CASES[-1 - key]
+        return REAR_ELEMENT_LENS.format(r=abs(r), radius=r, back=b), 0, 0.0, "keep"
+    h = zlib.crc32(repr((key,) + salt).encode())
+    seed = h & 0xFFFF
+    return LENSES[seed % len(LENSES)], seed, 0.25 * (h >> 16) / 65535.0, SURGERIES[(seed // len(LENSES)) % len(SURGERIES)]
+
+
+def lens_name(lens):
+    return "rear%s" % lens.splitlines()[-1].split()[0] if "\n" in lens else lens.split("_")[0]
+
+
+def bands(lam, edges=(360.0, 420.0, 500.0, 600.0, 700.0, 830.0)):
+    """index of the wavelength band of each ray (the last band includes 830)"""
+    return np.clip(np.searchsorted(np.asarray(edges[1:-1], np.float32), lam, side="right"), 0, len(edges) - 2)

@@ -174,12 +174,14 @@ def kolb_point_set(info, sensor_width, focal_distance, grid=64):
     and points on each chief ray at four depths (trace-frame z): just in front of the front element, focalDistance, 10 x focalDistance
     and 1e4 cm.  A point is kept only where the chief rays at its depth are still ordered from the axis out to its own (the definition
     takes the root continuous with the axis: beyond a fold of the chief-ray family -- the caustic of a strongly aberrated pupil -- the
-    point's own sample is not that root).  Returns (points (m,3) float32 in the frame of the records, samples (m,2), depth index (m,))."""
+    point's own sample is not that root).  A lens with no unclipped chief ray on the lattice gives an empty set.  Returns (points (m,3) float32 in the frame of the records, samples (m,2), depth index (m,))."""
     L = Lens(info, sensor_width)
     g = (np.arange(grid) + 0.5) / grid * 2.0 - 1.0
     sx, sy = [a.ravel() for a in np.meshgrid(g, g)]
     _, ok, clipped, zex = chief_points(L, sx, sy, [1.0])
     sel = ok & ~clipped
+    if not sel.any():   # no unclipped chief ray on the lattice (a machine-made lens can vignette its whole field): an empty set
+        return np.zeros((0, 3), F32), np.zeros((0, 2)), np.zeros(0, int)
     front = max(L.vtx[-1], float(zex[sel].max())) + 1e-3
     depths = [front, float(focal_distance), 10.0 * float(focal_distance), 1e4]
     pts, ok, clipped, _ = chief_points(L, sx, sy, depths)

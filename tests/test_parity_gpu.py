@@ -12,6 +12,8 @@ import pytest
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, RAYTRACED, THINLENS, ZoicCamera, lens_path
 from zoic_amd.workloads import CONFIGS, camera_params, hexagon_bokeh, ray_count, ray_rng_states, synthetic_samples
 
+from fuzz_cameras import HOSTILE_SAMPLES, REAR_ELEMENT_CASES, REAR_ELEMENT_LENS, perturbed_prescription
+
 pytestmark = pytest.mark.gpu
 
 DIR_RMSE_TOL = 1e-5        # BASELINE.json north_star: "ray-direction RMSE <1e-5 vs CPU reference"
@@ -506,19 +508,7 @@ def test_bokeh_image_size_envelope(gpu, oracle_lib, shape, path):
         cam.close()
 
 
-REAR_ELEMENT_LENS = """# TESSAR with a strongly curved last surface: housing radius a = 8.25 mm on a sphere of |R| = {r} mm
-42.97	9.8	1.691	54.7	19.2
--115.33	2.1	1.549	45.4	19.2
-306.84	4.16	0.0	0.0	19.2
-0.0	4.0	0.0	0.0	15.0
--59.060	1.87	1.64	34.6	17.3
-40.93	10.64	0.0	0.0	17.3
-183.92	7.050	1.691	54.7	16.5
-{radius}	{back}	0.0	0.0	16.5
-"""
-
-
-@pytest.mark.parametrize("radius,back", [(-9.0, 20.0), (-8.6, 12.0), (9.0, 20.0), (-12.0, 30.0), (8.4, 9.0)])
+@pytest.mark.parametrize("radius,back", REAR_ELEMENT_CASES)
 def test_retry_dead_shortcut_with_a_near_hemispherical_rear_element(gpu, oracle_lib, radius, back):
     """The retry-dead shortcut (tables.hpp KolbTable::retry*) bounds the lens points that can reach the rear element's
     vertex-side cap.  raySphereIntersection takes ONE signed root and never rejects t < 0 (zoic.cpp:986): with a rear
@@ -795,8 +785,7 @@ def test_hostile_sample_fuzz(gpu, oracle_lib):
     LUT lookups off both ends -- fenced UB) the strict kernels must make too, bit for bit, counters included."""
     from hypothesis import given, settings, HealthCheck, strategies as st
     lenses = ["double_gauss_f2.0.dat", "tessar_f2.8.dat", "fisheye_muller_f4.0.dat", "petzval_f1.25.dat", "triplet_f2.5.dat", "mori_f2.8.dat"]
-    special = np.array([0.0, -0.0, 0.5, 1.0, -1.0, 0.99999994, 1.0000001, 0.49999997, 0.50000006, 1e-40, -1e-40, 1e-30, 1e30, -1e30,
-                        np.inf, -np.inf, np.nan, 2.0, -3.0, 0.25, 0.75, 1e-8, 0.125, 3.875 / 1.8, 4.0], np.float32)
+    special = HOSTILE_SAMPLES
 
     @settings(max_examples=int(os.environ.get("ZOIC_FUZZ_EXAMPLES_HOSTILE", os.environ.get("ZOIC_FUZZ_EXAMPLES", "80"))), deadline=None,
               suppress_health_check=list(HealthCheck), derandomize=True)
@@ -863,38 +852,12 @@ def test_perturbed_prescription_fuzz(gpu, oracle_lib):
     from hypothesis import given, settings, HealthCheck, strategies as st
     lenses = ["double_gauss_f2.0.dat", "tessar_f2.8.dat", "fisheye_muller_f4.0.dat", "petzval_f1.25.dat", "triplet_f2.5.dat", "mori_f2.8.dat"]
 
-    def rows_of(name):
-        rows = []
-        for line in open(lens_path(name)):
-            line = line.strip()
-            if not line or line.startswith("#"):
-                continue
-            rows.append([float(t) for t in line.replace(",", " ").replace(";", " ").replace(":", " ").split()])
-        return rows
-
     @settings(max_examples=int(os.environ.get("ZOIC_FUZZ_EXAMPLES_LENS", os.environ.get("ZOIC_FUZZ_EXAMPLES", "150"))), deadline=None,
               suppress_health_check=list(HealthCheck), derandomize=True)
     @given(st.sampled_from(lenses), st.integers(0, 2 ** 16), st.floats(0.0, 0.25), st.sampled_from(["keep", "keep", "drop", "double"]),
            st.floats(2.0, 12.0, width=32), st.floats(1.25, 11.0, width=32), st.booleans(), st.floats(0.02, 0.98))
     def run(lens, seed, amount, surgery, focal, fstop, lut, where):
-        rs = np.random.RandomState(seed)
-        rows = rows_of(lens)
-        stop = [i for i, r in enumerate(rows) if r[0] == 0.0]
-        glass = [i for i in range(len(rows)) if i not in stop]
-        if surgery == "drop" and len(glass) > 3:
-            del rows[glass[rs.randint(len(glass))]]
-        elif surgery == "double":
-            i = glass[rs.randint(len(glass))]
-            rows.insert(i, list(rows[i]))
-        text = ""
-        for r in rows:
-            r = list(r)
-            ap = len(r) - 1                                   # 4 columns: radius thickness ior aperture; 5: ... abbe aperture
-            f = 1.0 + amount * (2.0 * rs.rand(len(r)) - 1.0)
-            r[0] *= f[0]; r[1] *= f[1]; r[ap] *= f[ap]
-            if r[2] > 1.0:
-                r[2] = 1.0 + (r[2] - 1.0) * f[2]
-            text += "\t".join("%.6g" % v for v in r) + "\n"
+        text = perturbed_prescription(lens, seed, amount, surgery).text
         kw = dict(focalLength=focal, fStop=fstop, focalDistance=120.0, kolbSamplingLUT=lut)
         cam, oc = ZoicCamera(0), oracle_lib.OracleCamera()
         cam.set_lens_text(text); oc.set_lens_text(text)

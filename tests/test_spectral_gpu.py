@@ -7,7 +7,8 @@ import pytest
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, ZoicCamera
 from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states
 
-from spectral_ref import LAMBDA_D, spectral_iors
+from fuzz_cameras import _oracle_spectral
+from spectral_ref import LAMBDA_D
 
 pytestmark = pytest.mark.gpu
 
@@ -78,36 +79,6 @@ def test_four_column_lens_ignores_the_wavelength():
     lam[:4] = [360.0, 830.0, 486.1327, 656.2725]
     _records_equal(cam.create_rays(s, wavelengths=lam), plain)
     cam.close()
-
-
-def _oracle_spectral(oracle_lib, p, dispersion, s, lam, states):
-    """the oracle camera, group by group: each wavelength's n_i written into its lens table (zo_lenses) after update, restored after"""
-    oc = oracle_lib.OracleCamera()
-    if p.get("useImage"):
-        oc.set_bokeh_image(hexagon_bokeh())
-    oc.update(**p)
-    L = oc._L
-    count = L.zo_lens_count(oc._h)
-    le = L.zo_lenses(oc._h)
-    nd = np.array([le[i].ior for i in range(count)], np.float32)
-    assert np.array_equal(nd, dispersion["ior_d"])
-    n = len(s)
-    planes = np.zeros((7, n), np.float32)
-    flags = np.zeros(n, np.uint8)
-    before = oc.counters()
-    for w in np.unique(lam):
-        rows = np.nonzero(lam == w)[0]
-        ior = spectral_iors(nd, dispersion["cauchy_b"], w)
-        for i in range(count):
-            le[i].ior = float(ior[i])
-        r = oc.create_rays(s[rows], rng_states=states[rows])
-        for i in range(count):
-            le[i].ior = float(nd[i])
-        planes[:, rows] = r["planes"]
-        flags[rows] = r["flags"]
-    after = oc.counters()
-    oc.close()
-    return dict(planes=planes, flags=flags), {k: after[k] - before[k] for k in after}
 
 
 PARITY = [
