@@ -1,0 +1,386 @@
+"""Edge rays of a Kolb camera (a plain helper module, imported by the test files): camera samples placed exactly where the
+reference's f32 rounding decides an accept / reject, found with the oracle and labelled with an f64 restatement of the trace.
+
+The fast kernels are decision-safe: a housing clip whose h^2 lies inside the interface's guard band, and a sensor
+point at the exit-pupil LUT's end, are too close to call, and such a try is evaluated again in STRICT arithmetic.  Random samples
+reach a guard band for 0.001 ... 2 % of the rays, so a broken guard hides in a flip *fraction*.  The rays built here sit ON the
+edges:
+
+* clip edges -- per seeded screen sample (sx, sy) and lens coordinate lensy, a coarse scan of lensx finds where the oracle's
+  first-try outcome (flag bit 0: retried) changes; the change is bisected down to two adjacent f32 values of lensx.  The same
+  along sx at a fixed lens sample (a bokeh image's sampler is piecewise constant in the lens sample: there only sx moves the ray
+  continuously).  The first try uses the caller's lens sample, so the retry streams play no part in where the edges lie.
+* LUT-end edges -- per seeded (sy, lensx, lensy), the sensor coordinate sx is bisected on flag bit 6 (outside the LUT).
+
+Every edge is emitted as its two adjacent samples plus `neighbours` ulp steps on each side.  Each edge is labelled by where the
+pair's f32 traces part (the oracle's zo_trace_record hit count of the failing first try) and by the f64 margins there:
+housing(i), miss(i), tir(i), lut_end, or other (a jump of the lens sampler, e.g. between bokeh-image cells: the two first-try
+start rays are not one ulp apart).  For housing edges, margin = |h^2 - housing^2| / housing^2 of each ray in f64 and band = the
+relative guard band of that interface as lens_system.cpp fill_surfaces computes it, with the constants read from lens_system.hpp.
+
+Everything is a pure function of its arguments: the same seed gives the same rays."""
+import os
+import re
+
+import numpy as np
+
+from zoic_amd.workloads import hexagon_bokeh, ray_rng_states
+
+from differentials_ref import kolb_start, surfaces
+
+F32 = np.float32
+EPS = F32(5.9604645e-8)        # lens_system.cpp fill_surfaces' eps
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
+
+KINDS = ("housing", "lut_end", "tir", "miss", "other")
+GUARDED = ("housing", "lut_end")        # the decisions the fast kernels guard
+JUMP_REL = 1e-5                         # first-try start directions further apart than this (relative): the sampler jumped
+
+
+# ---- the guard constants, read from the source --------------------------------------------------------------------------
+def _value(defs, text):
+    text = text.strip()
+    while text in defs:
+        text = defs[text].strip()
+    return float(text.rstrip("fF"))
+
+
+def guard_constants():
+    """kGuardScale, kGuardScaleFlat, kGuardMinRelBand, kGuardFloorRel and ZOIC_GUARD_ALL as lens_system.hpp defines them (the
+    default of every #ifndef ... #define; kGuardScaleFlat as its constexpr chooses with tables.hpp's ZOIC_FAST_STABLE_STOP)"""
+    defs = {}
+    for name in ("tables.hpp", "lens_system.hpp"):
+        with open(os.path.join(CSRC, name)) as f:
+            for m in re.finditer(r"^#define\s+(ZOIC_\w+)\s+([^\s/]+)", f.read(), re.M):
+                defs.setdefault(m.group(1), m.group(2))
+    with open(os.path.join(CSRC, "lens_system.hpp")) as f:
+        src = f.read()
+    min_rel = re.search(r"constexpr float kGuardMinRelBand\s*=\s*([^;]+);", src).group(1)
+    flat = re.search(r"constexpr float kGuardScaleFlat\s*=\s*(\w+)\s*\?\s*(\w+)\s*:\s*(\w+)\s*;", src)
+    scale = _value(defs, "ZOIC_GUARD_SCALE")
+    return dict(scale=scale, scale_flat=_value(defs, flat.group(2)) if _value(defs, flat.group(1)) else _value(defs, flat.group(3)),
+                min_rel=_value(defs, min_rel), floor=_value(defs, "ZOIC_GUARD_FLOOR"), all=bool(_value(defs, "ZOIC_GUARD_ALL")))
+
+
+def housing2(info):
+    """(n,) f32 housing^2 of every interface in trace order: the largest f32 <= (aperture/2)^2, and at the stop no more than
+    userApertureRadius^2 (lens_system.cpp fill_surfaces: the reference's two clips folded into one)"""
+    el = info["elements"]
+    n = int(info["lensCount"])
+    ua2 = F32(info["userApertureRadius"] * info["userApertureRadius"])
+    out = np.zeros(n, F32)
+    for i in range(n):
+        half = float(el[i, 3]) * 0.5
+        lim = half * half
+        f = F32(lim)
+        if float(f) > lim:
+            f = np.nextafter(f, F32(-np.inf))
+        if i == int(info["apertureElement"]) and ua2 < f:
+            f = ua2
+        out[i] = f
+    return out
+
+
+def guard_bands(info, consts=None):
+    """(n,) float64 relative guard band of every interface, (housingHi - housing^2) / housing^2 as fill_surfaces rounds it (0 for an
+    interface without a band), and (n,) the oracle's own rounding estimate eps |R| / housing (relBand there)"""
+    c = consts or guard_constants()
+    el = info["elements"]
+    h2 = housing2(info)
+    n = len(h2)
+    band = np.zeros(n)
+    est = np.zeros(n)
+    for i in range(n):
+        rel = F32(F32(EPS * abs(F32(el[i, 0]))) / F32(np.sqrt(h2[i])))
+        flat = rel > F32(c["min_rel"])
+        sc = F32(c["scale_flat"] if flat else c["scale"])
+        if c["all"]:
+            rel_all = F32(sc * rel) if F32(sc * rel) > F32(c["floor"]) else F32(c["floor"])
+            b = F32(rel_all * h2[i]) if c["scale"] > 0 else F32(0)
+        else:
+            b = F32(F32(sc * rel) * h2[i]) if flat else F32(0)
+        if b > 0:
+            hi = np.nextafter(F32(h2[i] + b), F32(np.inf))
+            band[i] = (float(hi) - float(h2[i])) / float(h2[i])
+        est[i] = float(rel)
+    return band, est
+
+
+# ---- the f64 restatement: margins of every decision along the trace ---------------------------------------------------
+def margins(info, o, d):
+    """(housing, miss, tir): (n, count) float64 signed margins of the first-try start rays (o, d) at every interface of an f64 trace
+    that clips nothing -- housing (h^2 - housing^2) / housing^2 (> 0: clipped), sphere miss (d^2 - R^2) / R^2 (> 0: missed), TIR
+    cs2 - 1 (> 0: reflected; NaN where the interface cannot reflect)"""
+    surf = np.asarray(surfaces(info), np.float64)
+    h2 = housing2(info).astype(np.float64)
+    o = np.asarray(o, np.float64).copy()
+    d = np.asarray(d, np.float64).copy()
+    count = len(surf)
+    mh = np.zeros((len(o), count))
+    mm = np.zeros((len(o), count))
+    mt = np.full((len(o), count), np.nan)
+    ior = info["elements"][:count, 2].astype(np.float64)
+    nxt = np.append(ior[1:], 1.0)
+    for i, (c, r2, sg, eta) in enumerate(surf):
+        u = d / np.linalg.norm(d, axis=1, keepdims=True)
+        L = np.stack([-o[:, 0], -o[:, 1], c - o[:, 2]], 1)
+        tca = (L * u).sum(1)
+        d2 = (L * L).sum(1) - tca * tca
+        mm[:, i] = (d2 - r2) / r2
+        t = tca + np.sqrt(np.abs(r2 - d2)) * sg
+        hit = o + u * t[:, None]
+        mh[:, i] = (hit[:, 0] ** 2 + hit[:, 1] ** 2 - h2[i]) / h2[i]
+        N = np.stack([-hit[:, 0], -hit[:, 1], c - hit[:, 2]], 1)
+        N = N / np.linalg.norm(N, axis=1, keepdims=True) * sg
+        c1 = -(u * N).sum(1)
+        cs2 = eta * eta * (1.0 - c1 * c1)
+        if ior[i] > nxt[i]:
+            mt[:, i] = cs2 - 1.0
+        k = eta * c1 - np.sqrt(np.abs(1.0 - cs2))
+        o, d = hit, u * eta + N * k[:, None]
+    return mh, mm, mt
+
+
+# ---- the oracle ----------------------------------------------------------------------------------------------------------
+def oracle_camera(oracle_lib, p, lens_text=None, image=None, ior=None):
+    """an OracleCamera updated with p; image: the bokeh image (default: the hexagon when p asks for one); ior: per-interface
+    indices (trace order) written into its lens table after the update -- a wavelength's table, as fuzz_cameras._oracle_spectral
+    writes it"""
+    oc = oracle_lib.OracleCamera()
+    if lens_text is not None:
+        oc.set_lens_text(lens_text)
+    if p.get("useImage"):
+        oc.set_bokeh_image(hexagon_bokeh() if image is None else image)
+    oc.update(**p)
+    if ior is not None:
+        le = oc._L.zo_lenses(oc._h)
+        for i in range(oc._L.zo_lens_count(oc._h)):
+            le[i].ior = float(ior[i])
+    return oc
+
+
+def _flags(oc, s, threads):
+    s = np.ascontiguousarray(s, F32)
+    return oc.create_rays(s, rng_states=ray_rng_states(len(s), seed=3), threads=threads)["flags"]
+
+
+def _bisect(oc, lo, hi, make, bit, threads):
+    """lo, hi: (m,) f32 brackets of one coordinate (lo < hi, both >= 0) whose flag `bit` differs; make(x) -> (m, 4) samples.
+    Bisection on the f32 bit patterns until hi is the float after lo."""
+    lo = np.ascontiguousarray(lo, F32).copy()
+    hi = np.ascontiguousarray(hi, F32).copy()
+    at_lo = (_flags(oc, make(lo), threads) >> bit) & 1
+    ilo, ihi = lo.view(np.int32).copy(), hi.view(np.int32).copy()
+    while True:
+        open_ = ihi - ilo > 1
+        if not open_.any():
+            break
+        mid = np.where(open_, ilo + (ihi - ilo) // 2, ilo).astype(np.int32)
+        fm = (_flags(oc, make(mid.view(F32)), threads) >> bit) & 1
+        go_hi = open_ & (fm == at_lo)
+        ilo = np.where(go_hi, mid, ilo)
+        ihi = np.where(open_ & ~go_hi, mid, ihi)
+    return ilo.view(F32), ihi.view(F32)
+
+
+def _ulps(x, k):
+    """x moved by k ulps (k may be negative), for x >= 0"""
+    return (np.asarray(x, F32).view(np.int32) + np.int32(k)).view(F32)
+
+
+def _clip_scan(oc, rs, p, screens, grid, threads):
+    """(pairs (E, 2, 4), axes (E,)) of the first-try edges found on `screens` seeded screen samples per axis: along lensx at fixed
+    (sx, sy, lensy), and along sx at fixed (sy, lensx, lensy) -- the axis on which a bokeh image's sampler (piecewise constant in
+    the lens sample) still moves the ray continuously"""
+    aspect = float(p["sensorHeight"]) / float(p["sensorWidth"])
+    pairs, axes = [], []
+    for axis, lo_x in ((2, 0.0), (0, -1.0)):
+        scr = np.stack([rs.uniform(-1, 1, screens), rs.uniform(-aspect, aspect, screens), rs.uniform(0, 1, screens),
+                        rs.uniform(0, 1, screens)], 1).astype(F32)
+        xs = (lo_x + (1.0 - lo_x) * (np.arange(grid, dtype=np.float64) + 0.5) / grid).astype(F32)
+        s = np.repeat(scr, grid, 0)
+        s[:, axis] = np.tile(xs, screens)
+        f = (_flags(oc, s, threads) & 1).reshape(screens, grid)
+        si, gi = np.nonzero(f[:, 1:] != f[:, :-1])
+        a, b = xs[gi], xs[gi + 1]
+        if axis == 0:                      # bisect |sx| on one side of 0 (the bisection runs on non-negative bit patterns)
+            keep = (a >= 0) == (b >= 0)
+            si, a, b = si[keep], a[keep], b[keep]
+        if not len(si):
+            continue
+        base = scr[si]
+        sign = np.where(b <= 0, F32(-1), F32(1)).astype(F32)   # a negative bracket is bisected on |sx|
+        lo_b, hi_b = np.minimum(a * sign, b * sign).astype(F32), np.maximum(a * sign, b * sign).astype(F32)
+
+        def make(x, base=base, axis=axis, sign=sign):
+            s = base.copy()
+            s[:, axis] = sign * x
+            return s
+        lo, hi = _bisect(oc, lo_b, hi_b, make, 0, threads)
+        pairs.append(np.stack([make(lo), make(hi)], 1))
+        axes.append(np.full(len(lo), axis))
+    if not pairs:
+        return np.zeros((0, 2, 4), F32), np.zeros(0, int)
+    return np.concatenate(pairs), np.concatenate(axes)
+
+
+def _lut_scan(oc, rs, p, lut_screens, threads):
+    """(pairs, axes) of the LUT-end edges: flag bit 6 along sx at fixed (sy, lensx, lensy), one per screen"""
+    keys, _ = oc.lut()
+    if not (p.get("kolbSamplingLUT", True) and len(keys) and lut_screens):
+        return np.zeros((0, 2, 4), F32), np.zeros(0, int)
+    hs = F32(F32(p["sensorWidth"]) * F32(0.5))
+    sy = rs.uniform(-1, 1, lut_screens).astype(F32) * F32(float(keys[-1]) / float(hs) * 0.9)
+    lens = rs.uniform(0, 1, (lut_screens, 2)).astype(F32)
+    top = F32(2.0 * float(keys[-1]) / float(hs))
+
+    def make_s(x):
+        return np.stack([x, sy, lens[:, 0], lens[:, 1]], 1).astype(F32)
+    lo, hi = _bisect(oc, np.zeros(lut_screens, F32), np.full(lut_screens, top, F32), make_s, 6, threads)
+    return np.stack([make_s(lo), make_s(hi)], 1), np.full(lut_screens, 0)
+
+
+def _label(oracle_lib, oc, info, p, pairs, threads):
+    """(kind, iface, flags (E, 2)) of every edge: where the pair's f32 first tries part"""
+    E = len(pairs)
+    pf = _flags(oc, pairs.reshape(-1, 4), threads).reshape(E, 2)
+    kind = np.full(E, KINDS.index("other"))
+    iface = np.full(E, -1)
+    if not E:
+        return kind, iface, pf
+    flat = pairs.reshape(-1, 4)
+    o0, d0 = kolb_start(oc, p, flat, np.zeros(len(flat), np.int32), np.zeros((len(flat), 4), np.uint32), oracle_lib)
+    o0, d0 = o0.reshape(E, 2, 3), d0.reshape(E, 2, 3)
+    mh, mm, mt = (m.reshape(E, 2, -1) for m in margins(info, o0.reshape(-1, 3), d0.reshape(-1, 3)))
+    jump = np.linalg.norm(d0[:, 0].astype(np.float64) - d0[:, 1], axis=1) > JUMP_REL * np.linalg.norm(d0[:, 0].astype(np.float64), axis=1)
+    for e in range(E):
+        if ((pf[e, 0] ^ pf[e, 1]) >> 6) & 1:
+            kind[e] = KINDS.index("lut_end")
+            continue
+        if jump[e] or not ((pf[e, 0] ^ pf[e, 1]) & 1):
+            continue
+        fail = 0 if pf[e, 0] & 1 else 1
+        ok, hits, _, _ = oc.trace_record(o0[e, fail], d0[e, fail])
+        assert not ok
+        k = len(hits)
+        cand = [(np.abs(mh[e, :, k]).min(), "housing", k), (np.abs(mm[e, :, k]).min(), "miss", k)]
+        if k >= 1 and np.isfinite(mt[e, 0, k - 1]):
+            cand.append((np.abs(mt[e, :, k - 1]).min(), "tir", k - 1))
+        _, kd, i = min(cand)
+        kind[e], iface[e] = KINDS.index(kd), i
+    return kind, iface, pf
+
+
+def edge_rays(oracle_lib, p, lens_text=None, image=None, ior=None, seed=0, stop_edges=500, nonstop_edges=200, lut_screens=256,
+              min_rays=1 << 15, max_rays=1 << 16, screens=1024, max_batches=8, grid=24, neighbours=4, threads=8):
+    """The edge rays of one camera (p: update() keyword arguments; lens_text / image / ior: see oracle_camera).
+
+    Clip edges are scanned in batches of `screens` screen samples per axis until the camera has stop_edges edges at its stop,
+    nonstop_edges housing edges at other interfaces and min_rays rays in all (or max_batches batches were scanned: a floor that
+    is out of reach shows in the result, the tests assert the floors); lut_screens LUT-end edges follow (one per screen, where
+    the camera has a LUT).  Beyond max_rays rays, edges are kept label by label in turn (a seeded order within a label), so the
+    rarest labels -- the stop, the LUT's end -- are kept whole.
+
+    Returns a dict of (N,) arrays: samples (N, 4) f32; edge (the index of its edge); offset (0 / 1: the two adjacent samples, < 0
+    and > 1: ulp neighbours beyond them); kind (a KINDS index); iface (-1 for lut_end / other); margin (f64 |h^2 - housing^2| /
+    housing^2 of the ray at its edge's interface, housing edges only, NaN elsewhere); band (relative guard band of that interface,
+    NaN where not a housing edge) -- and per edge: pairs (E, 2, 4) f32 samples, flags (E, 2) of the oracle's first try, kind_e and
+    iface_e."""
+    oc = oracle_camera(oracle_lib, p, lens_text, image, ior)
+    info = oc.lens_table()
+    stop = int(info["apertureElement"])
+    per_edge = 2 + 2 * neighbours
+    lut_n = lut_screens if (p.get("kolbSamplingLUT", True) and len(oc.lut()[0])) else 0
+    rs = np.random.RandomState(seed)
+    pairs, axes, kind, iface, pf = [], [], [], [], []
+    for _ in range(max_batches):
+        pr, ax = _clip_scan(oc, rs, p, screens, grid, threads)
+        kd, fc, fl = _label(oracle_lib, oc, info, p, pr, threads)
+        pairs.append(pr); axes.append(ax); kind.append(kd); iface.append(fc); pf.append(fl)
+        kd, fc = np.concatenate(kind), np.concatenate(iface)
+        hous = kd == KINDS.index("housing")
+        if (hous & (fc == stop)).sum() >= stop_edges and (hous & (fc != stop)).sum() >= nonstop_edges and \
+                (len(kd) + lut_n) * per_edge >= min_rays:
+            break
+    pr, ax = _lut_scan(oc, rs, p, lut_screens, threads)
+    kd, fc, fl = _label(oracle_lib, oc, info, p, pr, threads)
+    pairs.append(pr); axes.append(ax); kind.append(kd); iface.append(fc); pf.append(fl)
+    oc.close()
+    pairs, axes, kind, iface, pf = (np.concatenate(a) for a in (pairs, axes, kind, iface, pf))
+
+    # at most max_rays rays: edges taken label by label in turn
+    if len(pairs) * per_edge > max_rays:
+        lab = kind * 1000 + iface + 1
+        pools = [list(rs.permutation(np.nonzero(lab == v)[0])) for v in np.unique(lab)]
+        take = []
+        while len(take) < max_rays // per_edge:
+            for q in pools:
+                if q and len(take) < max_rays // per_edge:
+                    take.append(q.pop())
+        take = np.sort(np.array(take))
+        pairs, axes, kind, iface, pf = (a[take] for a in (pairs, axes, kind, iface, pf))
+    E = len(pairs)
+
+    # emit: the two adjacent samples and the ulp neighbours beyond them
+    offs = np.concatenate([np.arange(-neighbours, 0), [0, 1], np.arange(2, 2 + neighbours)])
+    S = np.repeat(pairs[:, 0:1, :], len(offs), 1).copy()
+    for j, k in enumerate(offs):
+        base = pairs[:, 0] if k <= 0 else pairs[:, 1]
+        step = k if k <= 0 else k - 1
+        for e in range(E):    # |x| moved away from the other end of the pair (pairs are ordered by |x|)
+            x = base[e, axes[e]]
+            S[e, j, axes[e]] = np.copysign(_ulps(abs(x), step), x)
+    samples = S.reshape(-1, 4)
+    edge = np.repeat(np.arange(E), len(offs))
+    offset = np.tile(offs, E)
+    kind_r = kind[edge]
+    iface_r = iface[edge]
+    margin = np.full(len(samples), np.nan)
+    band = np.full(len(samples), np.nan)
+    hous = kind_r == KINDS.index("housing")
+    if hous.any():
+        bands, _ = guard_bands(info)
+        oc = oracle_camera(oracle_lib, p, lens_text, image, ior)
+        idx = np.nonzero(hous)[0]
+        o, d = kolb_start(oc, p, samples[idx], np.zeros(len(idx), np.int32), np.zeros((len(idx), 4), np.uint32), oracle_lib)
+        oc.close()
+        m, _, _ = margins(info, o, d)
+        margin[idx] = np.abs(m[np.arange(len(idx)), iface_r[idx]])
+        band[idx] = bands[iface_r[idx]]
+    return dict(samples=np.ascontiguousarray(samples, F32), edge=edge, offset=offset, kind=kind_r, iface=iface_r, margin=margin,
+                band=band, pairs=pairs, flags=pf, kind_e=kind, iface_e=iface, info=info)
+
+
+def edge_tally(er):
+    """{label: number of EDGES} of an edge_rays result"""
+    labs = np.array([("%s(%d)" % (KINDS[k], i)) if i >= 0 else KINDS[k] for k, i in zip(er["kind_e"], er["iface_e"])])
+    return {str(lab): int((labs == lab).sum()) for lab in np.unique(labs)}
+
+
+def edge_counts(er):
+    """(stop, non-stop housing, LUT-end) edge counts"""
+    h = er["kind_e"] == KINDS.index("housing")
+    stop = int(er["info"]["apertureElement"])
+    return int((h & (er["iface_e"] == stop)).sum()), int((h & (er["iface_e"] != stop)).sum()), \
+        int((er["kind_e"] == KINDS.index("lut_end")).sum())
+
+
+def is_guarded(er):
+    return np.isin(er["kind"], [KINDS.index(k) for k in GUARDED])
+
+
+def label(er, i):
+    k = KINDS[er["kind"][i]]
+    return "%s(%d)" % (k, er["iface"][i]) if er["iface"][i] >= 0 else k
+
+
+def tally(er):
+    """{label: number of edge RAYS} of an edge_rays result (edge_tally counts edges)"""
+    labs = labels(er)
+    return {str(lab): int((labs == lab).sum()) for lab in np.unique(labs)}
+
+
+def labels(er):
+    """(N,) str label of every ray"""
+    return np.array([label(er, i) for i in range(len(er["edge"]))])

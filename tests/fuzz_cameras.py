@@ -43,6 +43,13 @@ REAR_ELEMENT_LENS = """# TESSAR with a strongly curved last surface: housing rad
 REAR_ELEMENT_CASES = [(-9.0, 20.0), (-8.6, 12.0), (9.0, 20.0), (-12.0, 30.0), (8.4, 9.0)]   # (radius, back focus)
 
 
+# hand-written prescriptions of 5 and 14 interfaces: no unrolled trace exists for them (the rolled generic trace runs)
+CUSTOM_LENS_5 = "40.0\t2.0\t1.6\t20.0\n-200.0\t3.0\t0.0\t20.0\n0\t5.0\t0\t12.0\n60.0\t2.0\t1.7\t14.0\n-60.0\t50.0\t0.0\t14.0\n"
+CUSTOM_LENS_14 = ("80.0\t3.0\t1.6\t40.0\n200.0\t1.0\t0.0\t40.0\n60.0\t3.0\t1.65\t36.0\n150.0\t1.0\t0.0\t36.0\n45.0\t4.0\t1.7\t30.0\n"
+                  "90.0\t6.0\t0.0\t28.0\n0\t6.0\t0\t20.0\n-90.0\t2.0\t1.6\t24.0\n120.0\t4.0\t1.7\t26.0\n-60.0\t1.0\t0.0\t26.0\n"
+                  "300.0\t3.0\t1.65\t28.0\n-120.0\t1.0\t0.0\t28.0\n500.0\t2.5\t1.6\t28.0\n-200.0\t60.0\t0.0\t28.0\n")
+
+
 def examples(name, default):
     """hypothesis example count of one fuzzer: its own variable, else ZOIC_FUZZ_EXAMPLES, else `default`"""
     return int(os.environ.get(name, os.environ.get("ZOIC_FUZZ_EXAMPLES", str(default))))

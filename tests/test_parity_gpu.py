@@ -12,7 +12,7 @@ import pytest
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, RAYTRACED, THINLENS, ZoicCamera, lens_path
 from zoic_amd.workloads import CONFIGS, camera_params, hexagon_bokeh, ray_count, ray_rng_states, synthetic_samples
 
-from fuzz_cameras import HOSTILE_SAMPLES, REAR_ELEMENT_CASES, REAR_ELEMENT_LENS, perturbed_prescription
+from fuzz_cameras import CUSTOM_LENS_5, CUSTOM_LENS_14, HOSTILE_SAMPLES, REAR_ELEMENT_CASES, REAR_ELEMENT_LENS, perturbed_prescription
 
 pytestmark = pytest.mark.gpu
 
@@ -395,12 +395,6 @@ def test_gpu_cdf_build_equals_host_and_oracle(gpu, oracle_lib, monkeypatch, shap
     got = g.create_rays(s, ray_index_base=base)
     ref = oc.create_rays(s, rng_states=ray_rng_states(n, 1, base))
     assert_bit_exact(got, ref)
-
-
-CUSTOM_LENS_5 = "40.0\t2.0\t1.6\t20.0\n-200.0\t3.0\t0.0\t20.0\n0\t5.0\t0\t12.0\n60.0\t2.0\t1.7\t14.0\n-60.0\t50.0\t0.0\t14.0\n"
-CUSTOM_LENS_14 = ("80.0\t3.0\t1.6\t40.0\n200.0\t1.0\t0.0\t40.0\n60.0\t3.0\t1.65\t36.0\n150.0\t1.0\t0.0\t36.0\n45.0\t4.0\t1.7\t30.0\n"
-                  "90.0\t6.0\t0.0\t28.0\n0\t6.0\t0\t20.0\n-90.0\t2.0\t1.6\t24.0\n120.0\t4.0\t1.7\t26.0\n-60.0\t1.0\t0.0\t26.0\n"
-                  "300.0\t3.0\t1.65\t28.0\n-120.0\t1.0\t0.0\t28.0\n500.0\t2.5\t1.6\t28.0\n-200.0\t60.0\t0.0\t28.0\n")
 
 
 # the first 10 rows of CUSTOM_LENS_14 (back focus on the last one), and the same with its cemented doublet made a singlet
