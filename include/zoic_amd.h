@@ -158,7 +158,7 @@ typedef struct zoic_counters { uint64_t succesRays, vignettedRays, totalInternal
  *   ZOIC_CDF_HOST=1    bokeh CDFs (bokehProbability) built by the host loop instead of bokeh_cdf.hip
  *   ZOIC_CELLS_HOST=1  bokeh cell records built by the host loop instead of build_cells_kernel
  * Kernel tuning constants are compile-time (-D, tools/build_variant.sh): ZOIC_MIN_SEARCHING, ZOIC_CHUNK_RAYS, ZOIC_GRID_BLOCKS,
- * ZOIC_GUARD_SCALE, ZOIC_RETRY_DEAD_MIN_SHARE, ZOIC_POOL_SLIM, ZOIC_TRACE_PREFETCH. */
+ * ZOIC_GUARD_SCALE, ZOIC_RETRY_DEAD_MIN_SHARE. */
 
 /* ---- library ------------------------------------------------------------------------------- */
 int         zoic_abi_version(void);

@@ -48,7 +48,7 @@ def _value(defs, text):
 
 def guard_constants():
     """kGuardScale, kGuardScaleFlat, kGuardMinRelBand, kGuardFloorRel and ZOIC_GUARD_ALL as lens_system.hpp defines them (the
-    default of every #ifndef ... #define; kGuardScaleFlat as its constexpr chooses with tables.hpp's ZOIC_FAST_STABLE_STOP)"""
+    default of every #ifndef ... #define; kGuardScaleFlat as its constexpr chooses with ZOIC_GUARD_SCALE_FLAT)"""
     defs = {}
     for name in ("tables.hpp", "lens_system.hpp"):
         with open(os.path.join(CSRC, name)) as f:

@@ -356,30 +356,6 @@ struct zoic_tile {
 void Mailbox::release()
 {
     (void)stop();
-#ifdef ZOIC_TILE_TIMING   // (tools/: -DZOIC_TILE_TIMING builds print where a tile batch's time went when the camera is destroyed)
-    if (dState) {
-        unsigned long long t[32];
-        if (hipMemcpy(t, dState->timing, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess) {
-            if (t[4]) std::fprintf(stderr, "rays per batch < 8 / 12 / 16 / 24 / more us: %llu %llu %llu %llu %llu; start < 6 / 8 / 12 / more us after the request: %llu %llu %llu %llu\n", t[16], t[17], t[18], t[19], t[20], t[24], t[25], t[26], t[27]);
-            if (t[4])
-                std::fprintf(stderr, "worker batches since the slot wave saw the request: start avg %.2f us (max %.2f), flag written avg %.2f us (max %.2f)\n",
-                             t[8] * 0.01 / t[4], t[9] * 0.01, t[10] * 0.01 / t[4], t[11] * 0.01);
-            if (t[4]) std::fprintf(stderr, "worker batches that started > 8 us after the request: %llu (mean batch index %.1f, %llu of them NOT the first batch after a wake-up); flagged > 25 us: %llu\n", t[12],
-                                   t[12] ? double(t[13]) / t[12] : 0.0, t[14], t[15]);
-            unsigned long long g[16] = {};
-            if (read_tile_dbg(g) == 0 && g[10])
-                std::fprintf(stderr, "RAYTRACED batches by rounds 0..7+: %llu %llu %llu %llu %llu %llu %llu %llu; with a listed ray: %llu (listed part %.2f us each); rounds part %.2f us per batch; "
-                             "open after round 0: %.2f rays per batch; batches with more than 8 open after round 0: %llu (their rounds part: %.2f us each)\n",
-                             g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[8] ? g[9] * 0.01 / g[8] : 0.0,
-                             g[10] * 0.01 / (g[0] + g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] ? g[0] + g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] : 1),
-                             double(g[12]) / (g[0] + g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] ? g[0] + g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] : 1), g[13], g[13] ? g[14] * 0.01 / g[13] : 0.0);
-            for (int o = 0; o < 8; o += 4)
-                if (t[o])
-                    std::fprintf(stderr, "tile timing (%s waves): %llu batches, input %.2f us, rays %.2f us, output %.2f us per batch\n", o ? "worker" : "slot", t[o],
-                                 t[o + 1] * 0.01 / t[o], t[o + 2] * 0.01 / t[o], t[o + 3] * 0.01 / t[o]);
-        }
-    }
-#endif
     for (auto &pair : ownTile) for (zoic_tile *&t : pair) if (t) { t->mem.release(); delete t; t = nullptr; }
     if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
     if (dState) { (void)hipFree(dState); dState = nullptr; }
@@ -1151,9 +1127,6 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
                 cam->updated = false; cam->params.valid = false; cam->fastVerdictValid = false;
                 return s;
             }
-#if defined(ZOIC_EXP_WHATIF) && ZOIC_EXP_WHATIF != 0
-            keep = true;   // timing-only what-if builds (kolb_pool_body.hpp): their rays are wrong on purpose, the check would send them to STRICT
-#endif
             cam->fastVerdict = keep; cam->fastVerdictValid = true;
         }
         cam->fastDomain = cam->fastVerdict;

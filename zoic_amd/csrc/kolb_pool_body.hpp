@@ -39,12 +39,6 @@
 
 #pragma STDC FP_CONTRACT OFF
 
-#ifndef ZOIC_EXP_WHATIF
-#define ZOIC_EXP_WHATIF 0   // TIMING-ONLY experiments (results are WRONG, never shipped; profiles/ab_r06/whatif.log; 5 / 6: the record stores, profiles/ab_r06/ab_store_whatif.log): 1 = the IMAGE kernels' retries sample the
-                            // disk instead of the image (no retry gathers), 2 = their first try does (no probe gather), 3 = no listed kernel is launched,
-                            // 4 = finish_dead_ray does not re-read its sample
-#endif
-
 #ifndef ZOIC_TWO_LEVEL_SEARCH
 #define ZOIC_TWO_LEVEL_SEARCH 3   // draws per lane per round of the TWO-LEVEL retry search (DEAD kernels, disk sampler, cameras with KolbTable::twoLevel): a draw is
                                   // only evaluated (disk mapping, direction, interface 0) when a per-ray bound cannot reject it.  0 compiles it out.
@@ -199,11 +193,7 @@ __device__ __forceinline__ bool finish_dead_ray(const KolbTable &T, const BokehT
                                                 const float4 *__restrict__ samples, const uint4 *__restrict__ states, uint64_t rayBase,
                                                 RayRecord *__restrict__ out, uint32_t idx)
 {
-#if ZOIC_EXP_WHATIF == 4
-    const float4 s = make_float4(__builtin_bit_cast(float, (idx & 0xffffu) | 0x3f000000u) - 0.75f, 0.3f, 0.0f, 0.0f);
-#else
     const float4 s = samples[idx];
-#endif
     const RaySetup rs = setup_ray<STRICT>(T, lutLds, s.x, s.y);
     Rng rng;
     if (states) { const uint4 r = states[idx]; rng = Rng{r.x, r.y, r.z, r.w}; }
@@ -214,59 +204,14 @@ __device__ __forceinline__ bool finish_dead_ray(const KolbTable &T, const BokehT
     return e.nanDraw;
 }
 
-
-// Debug build only (-DZOIC_PASS_STATS, tools/pass_stats.py): pass statistics summed over all waves.  Not part of the product build.
-#ifdef ZOIC_PASS_STATS
-static __device__ unsigned long long g_passStats[8];   // A passes, B passes, search iterations, sum looking lanes, traces, sum cand lanes, sum active lanes, finished
-static __device__ unsigned long long g_regionCycles[16];   // s_memtime cycles per region of the pass loop, summed over all waves
-#define ZOIC_PS_DECL unsigned long long ps[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rt[16] = {}, rtLast = __builtin_readcyclecounter();
-#ifdef ZOIC_PS_LIST   // the work list instead: [0] rays listed, [1] sum of their tries when listed, [2] rays the LISTED kernel finished, [3] sum of their final tries
-#define ZOIC_PS_ADD(I, V)
-#define ZOIC_PS_LISTADD(I, V) ps[I] += (V);
-#else
-#define ZOIC_PS_ADD(I, V) ps[I] += (V);
-#endif
-#define ZOIC_MARK(N) { const unsigned long long rtNow = __builtin_readcyclecounter(); rt[N] += rtNow - rtLast; rtLast = rtNow; }
-#define ZOIC_PS_FLUSH if (lane == 0) { for (int r = 0; r < 8; ++r) atomicAdd(&g_passStats[r], ps[r]); for (int r = 0; r < 16; ++r) atomicAdd(&g_regionCycles[r], rt[r]); }
-#else
-#define ZOIC_PS_DECL
-#define ZOIC_PS_ADD(I, V)
-#define ZOIC_MARK(N)
-#define ZOIC_PS_FLUSH
-#endif
-#ifndef ZOIC_PS_LISTADD
-#define ZOIC_PS_LISTADD(I, V)
-#endif
-
 // LDS per wave: the pool, 128 entries stored piece-major (arrays of 128 x 16 / 16 / 8 bytes: a push or pop is two
 // ds_write_b128 / ds_read_b128 and one b64, conflict-free), then the hand-over lists (128 ray indices each).
 // 128 entries: a pass starts with at most 63 pooled rays left behind and pushes at most 64.
-#ifndef ZOIC_POOL_SLIM
-#define ZOIC_POOL_SLIM 0   // 1: 40-byte entries: the exit-pupil scale / translation are looked up again when a ray is popped
-#endif
-#ifndef ZOIC_STORE_TRANSPOSED
-#define ZOIC_STORE_TRANSPOSED 2   // a fresh batch's records leave through an LDS transpose (two contiguous-KB stores per wave): 0 never, 1 every kernel, 2 the FAST IMAGE kernels
-                                  // [MI355X: -2 % on the fisheye (round 5: it is instructions on a pipe-bound kernel); on the image-sampler frame, whose waves wait for memory
-                                  // behind the DRAM write stream, +0.3-1 % on a fast pair of buffers and +2.8 % on a slow one: profiles/ab_r06/ab_store_whatif.log]
-                                  // [everywhere (=1), profiles/ab_r06/ab_transposed_configs.log: C2 -1.4 %, C4 -2.5 %, STRICT C3 -0.6 %, C5 +1.6 % (same kernel as C4's: it would need its own instantiation)]
-#endif
-#if ZOIC_STORE_TRANSPOSED && ZOIC_POOL_SLIM
-#error "ZOIC_STORE_TRANSPOSED stages in the upper half of pool1's float4 array: not with ZOIC_POOL_SLIM"
-#endif
-#ifndef ZOIC_STORE_NT
-#define ZOIC_STORE_NT 0   // experiments: 1 = the IMAGE kernels' records leave as non-temporal stores (they never come back; the bokeh table they evict does), 2 = every kernel's
-#endif
-#ifndef ZOIC_DEAD_WAVE_SAMPLER
-#define ZOIC_DEAD_WAVE_SAMPLER 0   // 1: phase A samples the lens even in waves of nothing but dead pixels (rounds 3-5; A/B: profiles/ab_r06/ab_dead_wave.log)
-#endif
-#ifndef ZOIC_PHASE_A_TEST0
-#define ZOIC_PHASE_A_TEST0 0   // 1: phase A always takes its own interface-0 test (rounds 3-5; A/B: profiles/ab_r06/ab_no_a0.log)
-#endif
 #ifndef ZOIC_SEARCH_DRAWS
 #define ZOIC_SEARCH_DRAWS 2   // lens draws the retry search of the IMAGE kernels samples per round (one wait for all their records); measured on C3: 1 -> 38.8, 2 -> 41.1, 3 -> 40.4, 4 -> 39.6 Grays/s
 #endif
 constexpr uint32_t kPoolEntries = 128;
-constexpr uint32_t kPoolWaveWords = kPoolEntries * (ZOIC_POOL_SLIM ? 10u : 12u);
+constexpr uint32_t kPoolWaveWords = kPoolEntries * 12u;
 constexpr uint32_t kPoolListWords = 128;
 // packed word of a pooled ray: bit 0 outside the LUT, bits 1-6 the ray's TIR tally (DEFER kernels), bits 8-12 tries,
 // bit 13 dead pixel, bit 14 retry-dead
@@ -279,9 +224,6 @@ constexpr uint32_t kPoolTriesShift = 8, kPoolDeadBit = 1u << 13, kPoolRetryDeadB
 #endif
 #ifndef ZOIC_POOL_ATTR_STRICT
 #define ZOIC_POOL_ATTR_STRICT __attribute__((amdgpu_waves_per_eu(4, 4)))
-#endif
-#ifndef ZOIC_POOL_PROBE_STRICT
-#define ZOIC_POOL_PROBE_STRICT 0   // the STRICT kernels spill when they also carry the probe of the next batch
 #endif
 
 __device__ __forceinline__ uint32_t mask_rank(unsigned long long m)   // exclusive prefix count of the lanes set in m
@@ -303,7 +245,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
     static_assert(!(GUARD && STRICT), "GUARD is a FAST mode");
     static_assert(!TWO || (DEAD && !IMAGE && kTwoLevelDraws > 0), "the two-level search belongs to the DEAD kernels of the disk sampler");
     constexpr bool DEFER = GUARD || DEAD;   // rays may leave the pass loop unfinished: TIR bumps are tallied per ray
-    constexpr bool PROBE = IMAGE && (!STRICT || ZOIC_POOL_PROBE_STRICT != 0);   // the next batch's first lens sample is requested a pass ahead
+    constexpr bool PROBE = IMAGE && !STRICT;   // the next batch's first lens sample is requested a pass ahead (the STRICT kernels spill when they also carry the probe)
     constexpr uint32_t kOut = static_cast<uint32_t>(kMaxTries) + 1u;   // tries of a ray that ran out (zoic.cpp:1927: tries <= 25)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0) {   // the other cursor block of this launch slot, for the launch after this one (kernels.hpp)
@@ -325,11 +267,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
     const float2 *lutLds = reinterpret_cast<const float2 *>(zoicDynLds);
     float4 *pool0 = reinterpret_cast<float4 *>(zoicDynLds + kLutLdsWords + ldsWords + wave * kPoolWaveWords);   // idx, o0x, o0y, packed
     uint4 *pool2 = reinterpret_cast<uint4 *>(pool0 + kPoolEntries);                                             // the ray's retry stream
-#if ZOIC_POOL_SLIM
-    float2 *pool1 = reinterpret_cast<float2 *>(pool2 + kPoolEntries);                                           // sn, cs
-#else
     float4 *pool1 = reinterpret_cast<float4 *>(pool2 + kPoolEntries);                                           // maxScale, translation, sn, cs
-#endif
     uint32_t *lists = reinterpret_cast<uint32_t *>(zoicDynLds + kLutLdsWords + ldsWords + kWavesPerBlock * kPoolWaveWords) +
                       wave * ((GUARD ? kPoolListWords : 0u) + (DEAD ? kPoolListWords : 0u));
     uint32_t *unsureLds = lists;                                  // GUARD: rays for the STRICT kernel
@@ -363,9 +301,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
     };
     const auto advance_batches = [&]() {   // b1 <- b2 (+ its probe), b2 <- the next request
         s1 = s2; base1 = base2; cnt1 = cnt2; have1 = have2;
-#if ZOIC_EXP_WHATIF != 2
         if constexpr (PROBE) { if (have1) probe = bokeh_cells_issue(B, bokehLds, T.bokehH, s1.z, s1.w); }
-#endif
         if (have1) request_batch();
     };
     request_batch();
@@ -378,18 +314,13 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
     // and letting the waves that are in their memory phases issue first gets those loads out earlier; without it the launch is
     // compute-dense and the waves inside the trace go first.
     constexpr bool memoryPhasesFirst = IMAGE;
-    ZOIC_PS_DECL
     for (;;) {
         const bool drain = !have1;                                          // no fresh sample left for this wave
-#ifdef ZOIC_PASS_STATS
-        const unsigned long long drainT0 = __builtin_readcyclecounter();
-#endif
         const bool fromPool = poolCnt >= 64u || (drain && poolCnt != 0u);
         if (!fromPool && drain) break;
-        ZOIC_PS_ADD(fromPool ? 1 : 0, 1)
         if (memoryPhasesFirst) __builtin_amdgcn_s_setprio(1);
         FastSurfaceTable fsurf = nullptr;
-        if constexpr (GUARD && (ZOIC_GUARD_PIN != 0)) fsurf = launder_table(kernarg_fast_surfaces());   // keeps the table's s_loads at their use (fast_optics.hpp)
+        if constexpr (GUARD) fsurf = launder_table(kernarg_fast_surfaces());   // keeps the table's s_loads at their use (fast_optics.hpp)
         else if constexpr (!STRICT) fsurf = kernarg_fast_surfaces();
         (void)fsurf;
 
@@ -414,16 +345,14 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             }
             else return interface0_clear_fast<GUARD>(load_surface<false>(fsurf, 0), oo, dd, near0);
         };
-        ZOIC_MARK(0)   // loop top, flushes of the previous pass
         if (!fromPool) {
             // phase A: set 64 fresh rays up and run the search's FIRST step for all of them (zoic.cpp:1853-1925)
             active = lane < cnt1;
             idx = base1 + lane;
-                const RaySetup rs = setup_ray<STRICT, TWO>(T, lutLds, s1.x, s1.y);
+            const RaySetup rs = setup_ray<STRICT, TWO>(T, lutLds, s1.x, s1.y);
             o0x = rs.o0x; o0y = rs.o0y; maxScale = rs.maxScale; translation = rs.translation; sn = rs.sn; cs = rs.cs;
             lutMiss = rs.flags; dead = rs.dead; rminq = rs.rminq;
             if constexpr (GUARD) unsure = active && T.useLUT && rs.lutEdge;
-                ZOIC_MARK(1)   // setup_ray
             tries = 0;
             o = V3{o0x, o0y, T.originShift};
             searching = GUARD ? (active && !unsure) : active;
@@ -435,16 +364,12 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             // plain: a sample in [0,1)^2 off the disk mapping's 0/0 centre -- for a dead pixel the sampler's (finite) point is never looked at
             bool plainSample = true;
             if (anyDead) plainSample = (u >= 0.0f) & (u < 1.0f) & (v >= 0.0f) & (v < 1.0f) & !((u == 0.5f) & (v == 0.5f));   // wave-uniform: most waves hold no dead pixel and skip these compares
-#if ZOIC_EXP_WHATIF == 2
-            if constexpr (PROBE) lens = concentric_disk_f32(u, v);
-#else
             if constexpr (PROBE) lens = bokeh_cells_finish<STRICT>(B, T.bokehW, T.bokehH, v, probe);
-#endif
             else {
                 // a wave of nothing but dead pixels with plain samples (the corners of a frame wider than the image circle: three quarters of C5's) needs no
                 // lens sample at all: ~35 instructions a ray of the ~250 such a ray costs [MI355X, profiles/ab_r06/ab_dead_wave.log]
                 lens = V2{0.0f, 0.0f};
-                if (ZOIC_DEAD_WAVE_SAMPLER != 0 || __ballot(active && !(dead && plainSample)) != 0ull) lens = sample_lens(u, v);
+                if (__ballot(active && !(dead && plainSample)) != 0ull) lens = sample_lens(u, v);
             }
             if (anyDead) {
                 if (dead && plainSample) lens = V2{0.0f, 0.0f};
@@ -466,7 +391,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             // dead-pixel exception C5 -3.5 %.
             bool near0 = false;
             bool pass0 = true;
-            if (ZOIC_PHASE_A_TEST0 != 0 || anyDead) pass0 = clears_rear(o, d, near0);
+            if (anyDead) pass0 = clears_rear(o, d, near0);
             if (searching) {
                 if (GUARD && near0) { unsure = true; searching = false; }   // too close to call: no decision is taken here
                 else if (pass0) { cand = true; searching = false; }
@@ -476,7 +401,6 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                     else if (DEAD && (lutMiss & kRetryDeadBit) != 0u) { toFinish = true; searching = false; }   // no retry can succeed
                 }
             }
-                ZOIC_MARK(2)   // first try: sampler finish, direction, interface 0
         } else {
             const uint32_t cnt = poolCnt < 64u ? poolCnt : 64u;
             poolCnt -= cnt;
@@ -486,20 +410,8 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             const uint4 e2 = pool2[slot];
             const uint32_t packed = __builtin_bit_cast(uint32_t, e0.w);
             idx = __builtin_bit_cast(uint32_t, e0.x); o0x = e0.y; o0y = e0.z;
-#if ZOIC_POOL_SLIM
-            const float2 e1 = pool1[slot];
-            sn = e1.x; cs = e1.y;
-            maxScale = 0.0f; translation = 0.0f;
-            if (T.useLUT) {   // the same lookup as setup_ray's, on the same operands: the same two values
-                float dist;
-                if constexpr (STRICT) dist = fabsf(ZOIC_SQRT_RN(o0x * o0x + o0y * o0y));
-                else dist = fsqrt_fast(o0x * o0x + o0y * o0y);
-                (void)lut_lookup_lds(lutLds, T.lutSize, dist, maxScale, translation);
-            }
-#else
             const float4 e1 = pool1[slot];
             maxScale = e1.x; translation = e1.y; sn = e1.z; cs = e1.w;
-#endif
             rng = Rng{e2.x, e2.y, e2.z, e2.w};
             tries = (packed >> kPoolTriesShift) & 31u;
             dead = (packed & kPoolDeadBit) != 0u;
@@ -509,17 +421,17 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             searching = active;
         }
 
-        if (fromPool) ZOIC_MARK(3)   // pool pop
         // ---- candidate search: RETRIES draw lens samples until one clears the rear element's housing (zoic.cpp:1927-1947) ----
         // Most rejected tries die at interface 0 (94 % of TESSAR retries, 91 % of wide-open PETZVAL retries, half of DOUBLE_GAUSS
         // retries); testing it alone costs a tenth of a whole try, so a lane keeps drawing -- tries and the ray's retry stream
         // advance exactly as in the reference's loop -- until a sample survives or it runs out of tries; the full trace then runs
         // once for the survivors.  The loop is wave-uniform: it goes on while enough lanes are looking to be worth the others'
-        // wait (any lane, once the wave has no fresh work left).
+        // wait (any lane, once the wave has no fresh work left).  Retry passes only: the lanes of a fresh batch that are still
+        // looking go to the pool as they are (tries == 0) and draw from there -- same rays, the per-ray retry streams see to that.
+        if (fromPool)
         for (;;) {
             const uint32_t looking = static_cast<uint32_t>(__popcll(__ballot(searching)));
             if (looking < (drain ? 1u : minSearching)) break;
-            ZOIC_PS_ADD(2, 1) ZOIC_PS_ADD(3, looking)
             if (searching) {
                 if (tries == 0) {               // first retry of this ray: seed its private xorshift128 stream
                     const uint4 *states = ZOIC_KARG(rngStates);
@@ -533,9 +445,6 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                     constexpr int kDraws = ZOIC_SEARCH_DRAWS;
                     Rng after[kDraws];
                     float vCol[kDraws];
-#if ZOIC_EXP_WHATIF == 1
-                    float uCol[kDraws];
-#endif
                     CellProbe probes[kDraws];
                     Rng r = rng;
 #pragma unroll
@@ -543,22 +452,14 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                         const float uj = rng_unit(xor128(r));   // zoic.cpp:1930
                         vCol[j] = rng_unit(xor128(r));
                         after[j] = r;
-#if ZOIC_EXP_WHATIF == 1
-                        probes[j] = CellProbe{make_uint4(0u, 0u, 0u, 0u), 0, 0u}; uCol[j] = uj;
-#else
                         probes[j] = bokeh_cells_issue(B, bokehLds, T.bokehH, uj, vCol[j]);
-#endif
                     }
                     bool open = true;
 #pragma unroll
                     for (int j = 0; j < kDraws; ++j) {
                         if (open) {
                             ++tries; rng = after[j];
-#if ZOIC_EXP_WHATIF == 1
-                            d = retry_direction(T, concentric_disk_f32(uCol[j], vCol[j]), o0x, o0y, maxScale, translation, sn, cs);
-#else
                             d = retry_direction(T, bokeh_cells_finish<STRICT>(B, T.bokehW, T.bokehH, vCol[j], probes[j]), o0x, o0y, maxScale, translation, sn, cs);
-#endif
                             bool near0;
                             const bool pass0 = clears_rear(o, d, near0);
                             if (GUARD && near0) { unsure = true; searching = false; open = false; }
@@ -614,19 +515,15 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             }
         }
 
-        ZOIC_MARK(4)   // retry search loop
         // ---- the fresh batches move up; issued here so that the sampler's dependent load above never waits for these loads ------
         if (!fromPool) advance_batches();
 
-        ZOIC_MARK(5)   // advance batches: probe issue + sample request
         // ---- one full trace for every lane that holds a candidate -------------------------------------------------------------
         bool ok = false;
         const V3 oStart = o, dStart = d;
         const bool firstTry = tries == 0;
         const unsigned long long candMask = __ballot(cand);
-        ZOIC_PS_ADD(6, __popcll(__ballot(active)))
         if (candMask != 0ull) {
-            ZOIC_PS_ADD(4, 1) ZOIC_PS_ADD(5, __popcll(candMask))
             if (memoryPhasesFirst) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3);
             uint32_t tirTry = 0;   // 0/1: this try ended in total internal reflection
             if constexpr (NS > 0) {
@@ -670,7 +567,6 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                 }
             }
         }
-        ZOIC_MARK(6)   // trace
         if (!memoryPhasesFirst) __builtin_amdgcn_s_setprio(0);
         // a lane that ran out at interface 0 hands out the untouched (o, d) of its last sample -- the reference's partial state
         // (the predicated trace scribbles over the registers of lanes that ride along)
@@ -687,24 +583,19 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             const uint32_t nv = static_cast<uint32_t>(__popcll(__ballot(finished && tries > static_cast<uint32_t>(kMaxTries))));
             vign += nv;                                                                       // zoic.cpp:1951-1957
             succ += static_cast<uint32_t>(__popcll(__ballot(finished))) - nv;
-            ZOIC_PS_ADD(7, __popcll(__ballot(finished)))
-#ifdef ZOIC_PS_LIST
-            if constexpr (GUARD) {
-                ZOIC_PS_LISTADD(0, __popcll(__ballot(dropU)))
-                for (uint32_t b = 0; b < 5u; ++b) ZOIC_PS_LISTADD(1, static_cast<unsigned long long>(__popcll(__ballot(dropU && ((tries >> b) & 1u)))) << b)
-            }
-#endif
         }
         {
             float w = (tries > static_cast<uint32_t>(kMaxTries)) ? 0.0f : 1.0f;
             if (T.exposureOn) w *= T.exposureMul;                                            // zoic.cpp:1981-1987
             const uint32_t flags = (tries > 0 ? 1u : 0u) | (tries << 1) | ((lutMiss & 1u) << 6);
-            constexpr bool kTransposed = (ZOIC_STORE_TRANSPOSED == 1) || (ZOIC_STORE_TRANSPOSED == 2 && IMAGE && !STRICT);
+            constexpr bool kTransposed = IMAGE && !STRICT;   // the FAST IMAGE kernels
             // Phase A holds 64 CONSECUTIVE rays in lane order and most of them finish here: their records are one contiguous 2 KB
             // block.  store_ray_record writes it as 2 x 64 half-sectors at a 32-byte stride per instruction; transposed through LDS --
             // the upper halves of pool0 / pool1 are free during a fresh batch (poolCnt < 64 and the push comes after this) -- each of
             // the two store instructions writes one contiguous KB (lane j: 16-byte piece j, then 64 + j), with the lanes of unfinished
             // rays masked off.  Phase B's rays are scattered: they keep the per-lane store.
+            // [MI355X, profiles/ab_r06/ab_store_whatif.log: where waves wait for memory behind the DRAM write stream +0.3-1 % on a fast pair of buffers, +2.8 % on a
+            // slow one; in every kernel (ab_transposed_configs.log) C2 -1.4 %, C4 -2.5 %, STRICT C3 -0.6 %: it is instructions on a pipe-bound kernel]
             if (kTransposed && !fromPool) {
                 float4 *stA = pool0 + 64, *stB = reinterpret_cast<float4 *>(pool1) + 64;
                 stA[lane] = make_float4(o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f);   // zoic.cpp:1960-1961
@@ -719,20 +610,9 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                 __builtin_amdgcn_wave_barrier();
             } else
             if (finished) {
-#if ZOIC_EXP_WHATIF == 5
-                const uint32_t at = idx & 0xffffu;   // timing only: every record into one 2 MB window (the write stream never reaches DRAM)
-#else
-                const uint32_t at = idx;
-#endif
-                if constexpr (ZOIC_STORE_NT == 2 || (ZOIC_STORE_NT == 1 && IMAGE))
-                    store_ray_record_nt(out, at, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);
-                else store_ray_record(out, at, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);   // zoic.cpp:1960-1961
+                store_ray_record(out, idx, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);   // zoic.cpp:1960-1961
             }
-#if ZOIC_EXP_WHATIF == 6
-            __builtin_amdgcn_s_waitcnt(0x0f70);      // timing only: vmcnt(0) right behind the record stores -- are their acknowledgements what a later wait pays for?
-#endif
         }
-        ZOIC_MARK(7)   // finish: counters + record store
         if constexpr (GUARD) {
             const unsigned long long m = __ballot(dropU);
             if (m != 0ull) {
@@ -757,21 +637,13 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                                       ((lutMiss & kRetryDeadBit) ? kPoolRetryDeadBit : 0u);
                     if constexpr (TWO) packed |= rminq << 16;
                     pool0[slot] = make_float4(__builtin_bit_cast(float, idx), o0x, o0y, __builtin_bit_cast(float, packed));
-#if ZOIC_POOL_SLIM
-                    pool1[slot] = make_float2(sn, cs);
-#else
                     pool1[slot] = make_float4(maxScale, translation, sn, cs);
-#endif
                 }
                 // the retry stream of a ray that has not drawn yet is seeded when it is popped (tries == 0): nothing to store
                 if (__ballot(keep && tries != 0u) != 0ull) { if (keep) pool2[poolCnt + mask_rank(m)] = make_uint4(rng.x, rng.y, rng.z, rng.w); }
                 poolCnt += static_cast<uint32_t>(__popcll(m));
             }
         }
-        ZOIC_MARK(8)   // hand-overs + pool push
-#ifdef ZOIC_PASS_STATS
-        if (drain) rt[9] += __builtin_readcyclecounter() - drainT0;   // [9]: the whole of every pass run without fresh work (the wave's tail)
-#endif
         // ---- hand-over lists: emptied in whole batches ---------------------------------------------------------------------
         if constexpr (GUARD) {
             if (unsureCnt >= 64u) {   // one atomic reserves exactly the entries written: no holes in the work list
@@ -817,7 +689,6 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
         for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
         tir += static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(t)));
     }
-    ZOIC_PS_FLUSH
     // ---- counters: the wave totals, one atomic per counter per wave -------------------------------------------------------
     DeviceCounters *counters = counter_set(ZOIC_KARG(counters));
     if (counters) {
@@ -899,10 +770,8 @@ int launch_kolb_pool_impl(const KolbTable &table, const BokehTables &bokeh, cons
             if (e != hipSuccess) return static_cast<int>(e);
             // the rays it listed (kolb_listed_body.hpp): the reference's arithmetic where a decision is too close to call;
             // workgroups beyond the list's length retire at once
-#if ZOIC_EXP_WHATIF != 3
             e = static_cast<hipError_t>(launch_kolb_listed(table, bokeh, sp, rp, rayBase + done, static_cast<uint32_t>(m), o, d_counters, redoCursor,
                                                            d_redoList, redoCount, grid, stream));
-#endif
         }
 #undef ZOIC_LAUNCH_POOL_BY_COUNT
 #undef ZOIC_LAUNCH_POOL
@@ -911,27 +780,6 @@ int launch_kolb_pool_impl(const KolbTable &table, const BokehTables &bokeh, cons
     }
     return 0;
 }
-
-#ifdef ZOIC_PASS_STATS
-static int read_pass_stats(unsigned long long *acc8, int reset)   // adds this translation unit's copy
-{
-    unsigned long long v[8];
-    hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_passStats), sizeof(v));
-    if (e != hipSuccess) return static_cast<int>(e);
-    for (int i = 0; i < 8; ++i) acc8[i] += v[i];
-    if (reset) { const unsigned long long z[8] = {}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_passStats), z, sizeof(z)); }
-    return static_cast<int>(e);
-}
-static int read_region_cycles(unsigned long long *acc16, int reset)
-{
-    unsigned long long v[16];
-    hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_regionCycles), sizeof(v));
-    if (e != hipSuccess) return static_cast<int>(e);
-    for (int i = 0; i < 16; ++i) acc16[i] += v[i];
-    if (reset) { const unsigned long long z[16] = {}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_regionCycles), z, sizeof(z)); }
-    return static_cast<int>(e);
-}
-#endif
 
 // cell records usable by the IMAGE kernels: present and small enough for LDS (tables.hpp)
 inline bool kolb_image_cells(const KolbTable &table, const BokehTables &bokeh)

@@ -14,9 +14,4 @@ int launch_kolb_pool_dead(const KolbTable &table, const BokehTables &bokeh, cons
     return launch_kolb_pool_impl<true, false>(table, bokeh, d_samples, d_rng, rayBase, n, out, d_counters, d_cursorPair, parity, mode, d_scratch, stream);
 }
 
-#ifdef ZOIC_PASS_STATS
-int read_pass_stats_dead(unsigned long long *acc8, int reset) { return read_pass_stats(acc8, reset); }
-int read_region_cycles_dead(unsigned long long *acc16, int reset) { return read_region_cycles(acc16, reset); }
-#endif
-
 }  // namespace zoic

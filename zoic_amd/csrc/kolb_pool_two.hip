@@ -17,9 +17,4 @@ int launch_kolb_pool_two(const KolbTable &table, const BokehTables &bokeh, const
 #endif
 }
 
-#ifdef ZOIC_PASS_STATS
-int read_pass_stats_two(unsigned long long *acc8, int reset) { return read_pass_stats(acc8, reset); }
-int read_region_cycles_two(unsigned long long *acc16, int reset) { return read_region_cycles(acc16, reset); }
-#endif
-
 }  // namespace zoic

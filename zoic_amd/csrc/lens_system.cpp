@@ -266,9 +266,6 @@ void LensSystem::fill_surfaces(KolbTable &t) const
         q.krScale = static_cast<float>(eta / (std::fabs(R) * R));
         const float relBand = eps * std::fabs(r.radius) / std::sqrt(s.housing2);   // relative to housing2
         const bool flat = relBand > kGuardMinRelBand;                                // near-planar: in practice the stop
-#if ZOIC_FAST_STABLE_STOP
-        if (flat) q.sign = 2.0f * r.radius;   // fast_hit takes this interface's root in its conjugate form (2R where the others carry sgn(R))
-#endif
         const float scaleHere = flat ? kGuardScaleFlat : guardScale;
 #if ZOIC_GUARD_ALL
         const float relAll = scaleHere * relBand > kGuardFloorRel ? scaleHere * relBand : kGuardFloorRel;

@@ -53,12 +53,6 @@
 
 namespace zoic {
 
-#ifdef ZOIC_TILE_TIMING
-// timing builds only: [0..7] batches by number of rounds (7 = seven or more), [8] batches with a listed ray, [9] ticks in the listed part, [10] ticks in
-// the rounds, [12] sum of rays open after round 0, [13] batches with more than 8 open after round 0, [14] their ticks in the rounds
-__device__ unsigned long long g_tileDbg[16];
-#endif
-
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -159,10 +153,6 @@ __device__ __forceinline__ void kolb_wave_rays(const KolbTable &T, const BokehTa
     }
     wave_lds_fence();
     uint32_t open = (cnt >= 32u ? 0xffffffffu : ((1u << cnt) - 1u)) & ~listedMask;   // wave-uniform: rays with tries to run
-#ifdef ZOIC_TILE_TIMING
-    const unsigned long long dbgT1 = wall_clock64();
-    uint32_t dbgRounds = 0, dbgOpen1 = 0;
-#endif
     // R = tries per LANE.  Measured with R = 2 where the unrolled FAST trace exists (lane t of a block: tries nextTry + t and nextTry + L + t,
     // round 0 covering tries 0 ... 7) [MI355X, profiles/ab_r05/tile_latency_v8.txt, _v9.txt]: a 4096-sample tile 29.1 -> 28.5 us, but a
     // 64-sample tile 17.3 -> 19.6 and the per-sample call 7.1 -> 8.6 us.  A lone wave is not waiting for its dependent instructions -- a wave64
@@ -172,10 +162,6 @@ __device__ __forceinline__ void kolb_wave_rays(const KolbTable &T, const BokehTa
     constexpr int R = 1;
     bool firstRound = true;
     while (open != 0u) {
-#ifdef ZOIC_TILE_TIMING
-        if (dbgRounds == 1u) dbgOpen1 = static_cast<uint32_t>(__builtin_popcount(open));
-        ++dbgRounds;
-#endif
         // ---- this round's lanes: L per open ray (4 in round 0, up to 32 / R for the stragglers) ----------------------------------------
         // (round 0 stays at four lanes per ray however few rays there are: a lane steps the ray's stream over the draws of the tries in
         // front of its own first, and 25 of those in front of a single sample's first round cost its median call 1.2 us for tries 95 % of
@@ -326,9 +312,6 @@ __device__ __forceinline__ void kolb_wave_rays(const KolbTable &T, const BokehTa
         open = stillOpen;
         wave_lds_fence();
     }
-#ifdef ZOIC_TILE_TIMING
-    const unsigned long long dbgT2 = wall_clock64();
-#endif
     // ---- retry-dead rays whose try 0 failed: the state of the last draw, one lane each ------------------------------------------------------
     if (deadEndMask != 0u) {
         uint32_t m = deadEndMask;
@@ -379,16 +362,6 @@ __device__ __forceinline__ void kolb_wave_rays(const KolbTable &T, const BokehTa
             }
         }
     }
-#ifdef ZOIC_TILE_TIMING
-    if (lane == 0u && cnt > 1u) {
-        const unsigned long long dbgT3 = wall_clock64();
-        atomicAdd(&g_tileDbg[dbgRounds < 7u ? dbgRounds : 7u], 1ull);
-        if (listedMask != 0u) { atomicAdd(&g_tileDbg[8], 1ull); atomicAdd(&g_tileDbg[9], dbgT3 - dbgT2); }
-        atomicAdd(&g_tileDbg[10], dbgT2 - dbgT1);
-        atomicAdd(&g_tileDbg[12], static_cast<unsigned long long>(dbgOpen1));
-        if (dbgOpen1 > 8u) { atomicAdd(&g_tileDbg[13], 1ull); atomicAdd(&g_tileDbg[14], dbgT2 - dbgT1); }
-    }
-#endif
     wave_lds_fence();
 }
 
@@ -544,9 +517,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
     uint32_t curSlot = kNoSlot, curPart = 0, partsTried = 0;   // the tile / ticket partition this wave draws from
     bool scanMask = false, leaving = false;                    // worker role: look at the work mask; the exit flag has been seen
     uint32_t idlePolls = 0;
-#ifdef ZOIC_TILE_TIMING
-    uint32_t lastWasHint = 0;
-#endif
     unsigned long long lastWake = 0;                           // worker role: the wake word last acted on (a posted one is never 0)
     while (watched) {
         if (wall_clock64() - start > kMailHardLifeTicks) break;   // safety net (never seen): the host reports a tile that is never answered
@@ -618,9 +588,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
                             const uint32_t per0 = (batches + parts - 1u) / parts, live = (batches + per0 - 1u) / per0;
                             store_dev(&st->tickets[slot].partMask, live >= 32u ? 0xffffffffu : ((1u << live) - 1u));
                         }
-#ifdef ZOIC_TILE_TIMING
-                        store_dev(reinterpret_cast<unsigned long long *>(st->jobs + slot) + 6, static_cast<unsigned long long>(now));
-#endif
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                     }
                     if (lane < parts) store_dev(&st->tickets[slot].part[lane].next, (static_cast<unsigned long long>(seq) << 32) | (lane == 0u ? 1ull : 0ull));
@@ -682,9 +649,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
                 lastWake = wk;
                 if ((wk >> 16) & 1ull) { leaving = true; scanMask = true; continue; }
                 curSlot = static_cast<uint32_t>(wk) & 63u; curPart = static_cast<uint32_t>(wk >> 8) & (kTileParts - 1u); partsTried = 0;
-#ifdef ZOIC_TILE_TIMING
-                lastWasHint = 2u;
-#endif
                 continue;
             }
             // the ticket and -- speculatively, in the same round trip -- the descriptor
@@ -738,10 +702,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
             jobBase = (static_cast<unsigned long long>(first_lane(c2.x)) << 32) | first_lane(c1.z);
             work = 2;
         }
-#ifdef ZOIC_TILE_TIMING
-        const unsigned long long tt0 = wall_clock64();
-        if (lastWasHint) --lastWasHint;   // 1: this batch is the first after a wake-up
-#endif
 
         // ---- the pass's samples: the slot's one sample in lane 0, or 64 consecutive rows of the tile --------------------------
         // (lane r holds ray r's sample; RAYTRACED shares the wave's lanes among the rays' tries afterwards, kolb_wave_rays)
@@ -779,9 +739,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
             rayBase = jobBase + first;
         }
 
-#ifdef ZOIC_TILE_TIMING
-        const unsigned long long tt1 = wall_clock64();
-#endif
         // ---- the rays (ONE site for both kinds of work) -------------------------------------------------------------------------
         if constexpr (MODEL == 0) {   // THINLENS, zoic.cpp:1771-1846: one ray per lane
             V3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 0.0f};
@@ -827,9 +784,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
         }
         const float *recStage = stage + ((MODEL != 0 && wide) ? kWideRecs : 0u);   // where the batch's records stand
 
-#ifdef ZOIC_TILE_TIMING
-        const unsigned long long tt2 = wall_clock64();
-#endif
         // ---- the answer -----------------------------------------------------------------------------------------------------------
         if (work == 1u) {
             if (lane == 0) {   // the one ray's record: ox oy oz dx | dy dz w flags
@@ -877,22 +831,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
         // its tile: no counter, no last wave, nobody waits for anybody on the device)
         __threadfence_system();
         if (lane == 0) store_sys(tileFlags + static_cast<size_t>(jobSlot) * kTileMaxBatches + batch, jobSeq);
-#ifdef ZOIC_TILE_TIMING
-        if (lane == 0) {
-            const unsigned long long tt3 = wall_clock64();
-            const int o = slotRole ? 0 : 4;
-            if (!slotRole) {
-                const unsigned long long tp = load_dev(reinterpret_cast<unsigned long long *>(st->jobs + jobSlot) + 6);
-                atomicAdd(&st->timing[8], tt0 - tp); atomicMax(&st->timing[9], tt0 - tp); atomicAdd(&st->timing[10], tt3 - tp); atomicMax(&st->timing[11], tt3 - tp);
-                if (tt0 - tp > 800ull) { atomicAdd(&st->timing[12], 1ull); atomicAdd(&st->timing[13], static_cast<unsigned long long>(batch)); if (lastWasHint == 0u) atomicAdd(&st->timing[14], 1ull); }
-                if (tt3 - tp > 2500ull) { atomicAdd(&st->timing[15], 1ull); }
-                const unsigned long long rt = tt2 - tt1, stt = tt0 - tp;   // histograms: the rays' time, the start's delay
-                atomicAdd(&st->timing[16 + (rt < 800ull ? 0 : rt < 1200ull ? 1 : rt < 1600ull ? 2 : rt < 2400ull ? 3 : 4)], 1ull);
-                atomicAdd(&st->timing[24 + (stt < 600ull ? 0 : stt < 800ull ? 1 : stt < 1200ull ? 2 : 3)], 1ull);
-            }
-            atomicAdd(&st->timing[o], 1ull); atomicAdd(&st->timing[o + 1], tt1 - tt0); atomicAdd(&st->timing[o + 2], tt2 - tt1); atomicAdd(&st->timing[o + 3], tt3 - tt2);
-        }
-#endif
     }
     for (int off = 32; off > 0; off >>= 1) { succ += __shfl_xor(succ, off, 64); vign += __shfl_xor(vign, off, 64); tir += __shfl_xor(tir, off, 64); }
     if (lane == 0) {
@@ -916,13 +854,6 @@ __global__ __launch_bounds__(kMailBlock) void mailbox_kernel(const KolbTable T, 
 }
 
 }  // namespace
-
-#ifdef ZOIC_TILE_TIMING
-int read_tile_dbg(unsigned long long *out16)
-{
-    return static_cast<int>(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tileDbg), 16 * sizeof(unsigned long long)));
-}
-#endif
 
 int launch_mailbox(const KolbTable &kolb, const ThinTable &thin, const BokehTables &bokeh, int model, int mode, void *d_mapped,
                    MailDeviceState *d_state, DeviceCounters *d_counters, uint32_t workerGroups, void *stream)
