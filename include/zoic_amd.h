@@ -17,7 +17,7 @@
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
  *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
- *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
+ *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
  *   - No entry point changes the calling thread's current HIP device.
@@ -53,7 +53,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_create_rays_spectral_device, zoic_camera_get_dispersion and
  *      zoic_camera_set_abbe_numbers (rays at a wavelength per ray: chromatic aberration); flag bit 7 of zoic_ray (wavelength rejected).
  *      Added later without a new number (additive): zoic_project_points_device, zoic_project_point and
- *      zoic_camera_set_reverse_projection (reverse projection; zoic_camera_reverse_ray answers only when opted in). */
+ *      zoic_camera_set_reverse_projection (reverse projection; zoic_camera_reverse_ray answers only when opted in).
+ *      Added later without a new number (additive): zoic_trace_back_rays_device and zoic_trace_back_ray (trace-back: camera rays
+ *      to the screen samples they land on). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -398,6 +400,53 @@ zoic_status zoic_project_points_device(zoic_camera *cam, uint64_t n, const float
 zoic_status zoic_project_point(const zoic_camera *cam, const zoic_vec3 *Po, float *Ps /* [2] */, uint32_t *flags);
 /* Off by default.  On: zoic_camera_reverse_ray answers with zoic_project_point (see there).  A _set_* call. */
 zoic_status zoic_camera_set_reverse_projection(zoic_camera *cam, int enable);
+
+/* ---- trace-back: camera rays to their screen samples (opt-in; csrc/traceback.hpp has the full definition) --------------------
+ * The reverse projection above answers for the CHIEF ray of a point.  These two calls answer for ONE PARTICULAR ray arriving at the
+ * front element: does it get through the housings and the stop, and on which screen sample does it land?  (What a light tracer, a
+ * splatter or a bidirectional integrator needs for depth of field; how lens points are drawn and weighted is the caller's.)
+ * Input: a camera ray as the forward calls write it -- zoic_ray origin and dir in the frame of the records, dir pointing away from the
+ * camera into the scene (dir.z < 0), any length; origin any point of the ray's line in front of the lens (a forward record's origin
+ * lies on the front surface; a light tracer passes its scene point and dir = point - lens point).  weight and flags are not read.
+ *   RAYTRACED  the ray is followed back through every interface, front to rear: the intersection the forward trace takes, the forward
+ *              kernels' housing / stop limits (the stop's holds min(housing, userApertureRadius)), Snell with the true ratio of the
+ *              media; the stop is the reference's sphere of |R| ~ 1e4 cm.  Ps = the point where it meets the sensor plane z = originShift,
+ *              divided by sensorWidth / 2 in x AND y (zoic.cpp:1853-1854).  Nothing is clipped at the sensor: the caller knows its frame
+ *              (|sx| <= 1, |sy| <= 1 / aspect).  Cameras outside the geometric domain of the FAST modes (see zoic_precision) trace no ray.
+ *   THINLENS   with useDof: the lens point P = the line's crossing of z = 0 must lie within apertureRadius (the forward path's disk
+ *              sampler overshoots that disk by up to 0.1 % on 0.06 % of its rays: those records are refused) and, with
+ *              opticalVignettingDistance > 0, pass the test of
+ *              zoic.cpp:1297-1305; Ps = the line's crossing of z = -focalDistance divided by focalDistance tan_fov.  Without DOF (a pinhole passes no generic ray) and for lensModel NONE: ZOIC_TRACE_BACK_MODEL
+ *              (zoic_project_point answers there).
+ * Flags: bit 0 traced back (the ray reaches the sensor unclipped; Ps written); bit 2 the sensor radius lies beyond the exit-pupil LUT's
+ * last key (as ZOIC_PROJECT_PAST_LUT); bits 8-11 when bit 0 is clear: the reason below; bits 16-21, for MISS / CLIPPED / TIR: the index
+ * (trace order, rear first: the order of zoic_lens_info) of the interface where the ray ended.  A ray that is not traced back gets
+ * Ps = (+0, +0).
+ * The arithmetic is f32 with correctly rounded square roots and reciprocals, the same on the host and on the device in every
+ * precision mode: zoic_trace_back_rays_device and zoic_trace_back_ray give the same bits for the same ray. */
+#define ZOIC_TRACED_BACK 0x1u
+#define ZOIC_TRACE_BACK_PAST_LUT 0x4u
+#define ZOIC_TRACE_BACK_REASON(flags) (((flags) >> 8) & 0xFu)
+#define ZOIC_TRACE_BACK_INTERFACE(flags) (((flags) >> 16) & 0x3Fu)
+enum {
+    ZOIC_TRACE_BACK_AWAY = 1,           /* dir.z >= 0, or the start point is not in front of the front element's cap (THINLENS: origin.z > 0) */
+    ZOIC_TRACE_BACK_MISS = 2,           /* the ray misses an interface's sphere */
+    ZOIC_TRACE_BACK_CLIPPED = 3,        /* outside an interface's housing, the stop or the thin lens's aperture / vignetting test */
+    ZOIC_TRACE_BACK_TIR = 4,            /* total internal reflection */
+    ZOIC_TRACE_BACK_NON_FINITE = 5,     /* a NaN or infinite coordinate, dir = 0, or Ps overflows */
+    ZOIC_TRACE_BACK_MODEL = 6,          /* lensModel NONE, or THINLENS without useDof */
+    ZOIC_TRACE_BACK_OUTSIDE_DOMAIN = 7  /* RAYTRACED camera outside the geometric domain */
+};
+/* n zoic_ray records (device memory, 16-byte aligned) -> n (sx, sy) pairs (device memory, 8-byte aligned) and, unless d_flags is NULL,
+ * n flag words (device memory).  d_rays may be the buffer zoic_create_rays_device wrote, on the same stream, without a copy.
+ * Asynchronous on `stream`, with the threading contract of zoic_project_points_device; touches no counter and no retry stream.
+ * ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL, misaligned or non-device pointer; ZOIC_ERR_NO_DEVICE on
+ * a tables-only camera; n = 0 returns ZOIC_OK. */
+zoic_status zoic_trace_back_rays_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_screen /* n x 2 */,
+                                        uint32_t *d_flags /* may be NULL */, void *stream);
+/* The host build of the same code for one ray (no GPU round trip; works on a ZOIC_DEVICE_NONE camera).  flags may be NULL. */
+zoic_status zoic_trace_back_ray(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps /* [2] */,
+                                uint32_t *flags /* may be NULL */);
 
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins

@@ -1,0 +1,372 @@
+"""Trace-back without a GPU: the C-ABI declares and exports the two calls, the gfx950 kernel keeps its budget, and the host build of
+csrc/traceback.hpp (zoic_trace_back_ray on a tables-only camera; the same header compiled here with clang++) takes the oracle's forward
+records back to the samples they were made from, agrees with an f64 restatement written from the definition (traceback_ref.py) and
+refuses what it must.
+
+Round trip: frame 192 x 108 x 2 of synthetic_samples with ray_rng_states (41 472 rays), forward records from the oracle (the STRICT
+kernel's bits), rays of weight > 0.  Edge rays (left out): f64 clearance |1 - h^2 / housing2| below 1e-2 at the stop or below 1e-4 at
+any other interface; at most 2 % of the live rays.  Measured with traceback_ref.py alone, before the library was looked at:
+
+    configuration   live rays   edge share   non-edge rays the f64 trace rejects   E_ref max / p99
+    C2 (Tessar)       33 655      0.45 %                    0                      1.20e-6 / 6.3e-7
+    C3 (dbl. Gauss)   41 447      0.01 %                    0                      1.37e-6 / 7.5e-7
+    C4 (fisheye)      41 472      0.98 %                    0                      1.15e-6 / 6.5e-7
+    C5 (Petzval)       8 722      0.31 %                    0                      4.4e-7  / 3.0e-7
+    triplet f/2.5     31 715      0.10 %                    0                      1.35e-6 / 7.5e-7     (C2's parameters, the triplet's file)
+    C1 (thin lens)    41 472      0.01 %                   26                      2.0e-7  / 1.2e-7     (see test_thin_lens_round_trip)
+    C1 + vignetting   20 165      0.03 %                   26                      1.2e-7  / 6.9e-8
+
+E_ref = |Ps of the f64 trace-back - the sample the record was made from|: the forward f32 path's own noise seen through an exact
+trace-back.  The library is held to 4 x E_ref against the f64 trace (max and p99, computed here from the values just measured) and
+to 5 x max E_ref for the round trip.  Measured for the library: |lib - f64| / E_ref = 0.60 ... 0.89 (max) and 0.55 ... 1.00 (p99), round
+trip 1.18 ... 1.76 x max E_ref."""
+import ctypes
+import functools
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from zoic_amd import _capi
+from zoic_amd.camera import ZoicCamera, ZoicError
+from zoic_amd.workloads import camera_params
+
+import traceback_cases as tc
+from traceback_ref import AWAY, CLIPPED, MISS, MODEL, NON_FINITE, OUTSIDE_DOMAIN, TIR, TraceBack
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
+NEW = ("zoic_trace_back_rays_device", "zoic_trace_back_ray")
+EDGE_CAP = 0.02
+
+
+def _camera(p):
+    return tc.update(ZoicCamera(device=-1), p)
+
+
+_lib_trace, _reason, _iface = tc.lib_trace, tc.reason, tc.iface
+
+
+_CACHE = {}
+
+
+def round_trip(oracle_lib, name):
+    """the live forward records of `name`, their f64 trace-back and its yardstick (cached: several tests build on it)"""
+    if name not in _CACHE:
+        p = tc.params_of(name)
+        s, o, d, w = tc.oracle_records(oracle_lib, p)
+        live = w > 0
+        cam = _camera(p)
+        T = TraceBack(cam.info(), p)
+        o, d, smp = o[live], d[live], s[live, :2].astype(np.float64)
+        ref = T.trace(o, d)
+        edge = T.edge(ref)
+        good = ~edge & ref["traced"]
+        e_ref = np.abs(ref["ps"] - smp).max(1)
+        _CACHE[name] = dict(p=p, cam=cam, T=T, o=o, d=d, smp=smp, ref=ref, edge=edge, e_ref=e_ref,
+                            e_max=float(e_ref[good].max()), e_p99=float(np.percentile(e_ref[good], 99)))
+    return _CACHE[name]
+
+
+def test_abi_declares_and_exports_trace_back_calls():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    lib = ctypes.CDLL(_capi.LIB_PATH)
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _capi.SYMBOLS, name
+        assert hasattr(lib, name), name
+    assert _capi.load().zoic_abi_version() == 5
+
+
+def test_trace_back_kernel_budget():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import code_object_regs
+    finally:
+        sys.path.pop(0)
+    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "trace_back_kernel" in k}
+    assert res, "trace_back_kernel not in the library"
+    for k, v in res.items():
+        print(k, v)
+        assert v["scratch"] == 0, (k, v)
+        assert v["vgpr_spill"] == 0, (k, v)
+        assert v["lds"] == 0, (k, v)
+
+
+def _compare(R, require_decisions):
+    cam, ref, edge = R["cam"], R["ref"], R["edge"]
+    ps, fl = _lib_trace(cam, R["o"], R["d"])
+    ok = (fl & 1) == 1
+    n_live = len(edge)
+    print("live %d  edge %.2f %%  E_ref max %.3g p99 %.3g" % (n_live, 100.0 * edge.mean(), R["e_max"], R["e_p99"]))
+    assert n_live >= 8192 and edge.mean() <= EDGE_CAP, edge.mean()
+    bad_ref, bad_lib = ~edge & ~ref["traced"], ~edge & ~ok
+    print("non-edge rays refused: f64 %d, library %d; the worst clearance among them %s" % (
+        bad_ref.sum(), bad_lib.sum(), ref["clearance"][bad_ref | bad_lib].min() if (bad_ref | bad_lib).any() else None))
+    if require_decisions:
+        assert not bad_ref.any(), (bad_ref.sum(), np.unique(ref["reason"][bad_ref]), ref["clearance"][bad_ref].min())
+        assert not bad_lib.any(), (bad_lib.sum(), np.unique(_reason(fl[bad_lib])))
+    both = ~edge & ref["traced"] & ok
+    assert both.sum() >= 0.97 * n_live
+    err = np.abs(ps.astype(np.float64) - ref["ps"]).max(1)[both]
+    rt = np.abs(ps.astype(np.float64) - R["smp"]).max(1)[both]
+    print("|lib - f64| max %.3g p99 %.3g (%.2f / %.2f of E_ref); round trip max %.3g (%.2f of max E_ref)" % (
+        err.max(), np.percentile(err, 99), err.max() / R["e_max"], np.percentile(err, 99) / R["e_p99"], rt.max(), rt.max() / R["e_max"]))
+    assert err.max() <= 4.0 * R["e_max"], (err.max(), R["e_max"])
+    assert np.percentile(err, 99) <= 4.0 * R["e_p99"], (np.percentile(err, 99), R["e_p99"])
+    assert rt.max() <= 5.0 * R["e_max"], (rt.max(), R["e_max"])
+    # whatever the library refuses it reports as nothing: Ps = (+0, +0)
+    assert (ps[~ok].view(np.uint32) == 0).all()
+    return fl, ok
+
+
+@pytest.mark.parametrize("name", list(tc.KOLB))
+def test_round_trip_against_the_oracle(oracle_lib, name):
+    _compare(round_trip(oracle_lib, name), require_decisions=True)
+
+
+@pytest.mark.parametrize("name", list(tc.THIN))
+def test_thin_lens_round_trip(oracle_lib, name):
+    """The three comparisons (yardstick, accuracy, round trip) on the forward records both traces take back, and the library's decision
+    equal to the f64 trace's on every non-edge record.
+
+    Not every non-edge forward record of the thin lens IS taken back, and that is the forward path's doing: the reference's disk
+    sampler turns its sample with the parabola fast_cos / fast_sin (cos^2 + sin^2 up to 1.001997), so 26 of the 41 472 live records of
+    C1 (0.06 %), and 26 of 20 165 with opticalVignettingDistance = 8, have their lens point outside |P| <= apertureRadius, the worst
+    at clearance -1.85e-3.  The definition's disk refuses them CLIPPED, in f64 and in the library alike.  Their number is held below
+    0.2 % of the frame's rays: the overshoot ring 1 < |P|^2 / apertureRadius^2 <= 1.001997 is at most that share of the sampled disk."""
+    R = round_trip(oracle_lib, name)
+    fl, ok = _compare(R, require_decisions=False)
+    keep = ~R["edge"]
+    assert np.array_equal(ok[keep], R["ref"]["traced"][keep])
+    refused = keep & ~ok
+    assert (_reason(fl[refused]) == CLIPPED).all() and refused.sum() <= 2e-3 * tc.N, refused.sum()
+    assert (R["ref"]["clearance"][refused] > -2.1e-3).all()   # within the sampler's overshoot, 1 - 1.001997
+
+
+@pytest.mark.parametrize("name", list(tc.THIN))
+def test_thin_lens_aperture_by_hand(oracle_lib, name):
+    R = round_trip(oracle_lib, name)
+    cam, T = R["cam"], R["T"]
+    ar = float(cam.info()["apertureRadius"])
+    rng = np.random.default_rng(1)
+    m = 2048
+    # |P|^2 / apertureRadius^2: the first half inside, the second outside, a quarter of each close to the limit (outside the 1e-4 band)
+    rad = ar * np.concatenate([rng.uniform(0.0, 0.9999, 3 * m // 8), rng.uniform(0.995, 0.9999, m // 8),
+                               rng.uniform(1.0001, 1.005, m // 8), rng.uniform(1.0001, 4.0, 3 * m // 8)]) ** 0.5
+    az = rng.uniform(0, 2 * np.pi, m)
+    P = np.stack([rad * np.cos(az), rad * np.sin(az), np.zeros(m)], 1)
+    F = np.stack([rng.uniform(-40, 40, m), rng.uniform(-25, 25, m), np.full(m, -float(R["p"]["focalDistance"]))], 1)
+    d = (F - P).astype(np.float32)
+    back = rng.uniform(0.0, 30.0, m)[:, None]   # the start point anywhere on the line in front of the lens
+    o = (P + tc.unit(F - P) * back).astype(np.float32)
+    ref = T.trace(o, d)
+    keep = ~T.edge(ref)
+    assert keep.mean() >= 0.98
+    ps, fl = _lib_trace(cam, o, d)
+    ok = (fl & 1) == 1
+    assert np.array_equal(ok[keep], ref["traced"][keep])
+    inside = np.arange(m) < m // 2
+    if name == "C1":
+        assert ok[keep & inside].all() and not ok[keep & ~inside].any()
+    else:   # (the vignetting test removes rays inside the aperture too)
+        assert ok[keep & inside].any() and not ok[keep & ~inside].any()
+    assert (_reason(fl[keep & ~ok]) == CLIPPED).all()
+    assert np.abs(ps[keep & ok] - ref["ps"][keep & ok]).max() <= 4.0 * R["e_max"] * max(1.0, np.abs(ref["ps"][keep & ok]).max())
+
+
+def test_rejections_match_the_f64_trace(oracle_lib):
+    R = round_trip(oracle_lib, "C3")   # the double Gauss
+    cam, T, info = R["cam"], R["T"], R["cam"].info()
+    pick = np.flatnonzero(~R["edge"])[::8]
+    fam = tc.rejection_families(info, R["o"][pick], R["d"][pick])
+    front, stop = info["lensCount"] - 1, info["apertureElement"]
+    for name, (o, d) in fam.items():
+        ref = T.trace(o, d)
+        keep = ~T.decision_edge(ref)
+        assert keep.mean() >= 0.99, (name, keep.mean())
+        ps, fl = _lib_trace(cam, o, d)
+        ok = (fl & 1) == 1
+        assert np.array_equal(ok[keep], ref["traced"][keep]), name
+        no = keep & ~ok
+        assert np.array_equal(_reason(fl[no]), ref["reason"][no]), name
+        ended = no & np.isin(ref["reason"], (MISS, CLIPPED, TIR))
+        assert np.array_equal(_iface(fl[ended]), ref["iface"][ended]), name
+        assert (ps[~ok].view(np.uint32) == 0).all(), name
+        if name == "shifted":
+            # A record that met the front element off centre can be shifted half a radius and still pass, or be clipped one interface
+            # further in: the f64 trace says which, ray by ray (the comparisons above).  Measured for this set: 89.1 % of the
+            # shifted rays are refused, 92.8 % of those at the front interface, all of them MISS or CLIPPED.
+            at_front = (_iface(fl[no]) == front).mean()
+            print("shifted: %.1f %% refused, %.1f %% of them at the front interface" % (100.0 * no.sum() / keep.sum(), 100.0 * at_front))
+            assert no.sum() >= 0.8 * keep.sum() and np.isin(_reason(fl[no]), (MISS, CLIPPED)).all() and at_front >= 0.9
+        elif name == "tilted":
+            where = set(_iface(fl[no & (_reason(fl) == CLIPPED)]).tolist())
+            print("tilted rays are clipped at interfaces", sorted(where))
+            assert len(where) >= 3 and stop in where, where
+        else:
+            assert (_reason(fl[keep]) == AWAY).all(), name
+    o, d = tc.non_finite_rays()
+    ps, fl = _lib_trace(cam, o, d)
+    assert (_reason(fl) == NON_FINITE).all() and (fl & 1 == 0).all() and (ps.view(np.uint32) == 0).all(), fl
+    assert (T.trace(o, d)["reason"] == NON_FINITE).all()
+
+
+def test_past_lut_flag_against_the_lut_keys():
+    """flag bit 2 against info()['lutKeys']: set exactly where the sensor radius of a traced ray lies beyond the last key.  The Tessar
+    scaled to focalLength 20 has an image circle well beyond the LUT's 3.875 cm, so random lines land on both sides of it."""
+    p = dict(tc.params_of("C2"), focalLength=20.0)
+    cam = _camera(p)
+    info = cam.info()
+    T = TraceBack(info, p)
+    last = float(info["lutKeys"][-1])
+    o, d = tc.random_lines(info, 20000)
+    ref = T.trace(o, d)
+    ps, fl = _lib_trace(cam, o, d)
+    radius = np.hypot(ref["ps"][:, 0], ref["ps"][:, 1]) * T.half_sensor
+    keep = ref["traced"] & ~T.decision_edge(ref) & ((fl & 1) == 1) & (np.abs(radius - last) > 1e-4 * last)
+    beyond = radius > last
+    print("traced %d, of them beyond the last key (%.3f cm): %d" % (keep.sum(), last, (keep & beyond).sum()))
+    assert (keep & beyond).sum() >= 64 and (keep & ~beyond).sum() >= 64
+    assert np.array_equal((fl[keep] & 4) != 0, beyond[keep])
+    assert np.array_equal(ref["past_lut"][keep], beyond[keep])
+    assert ((fl[(fl & 1) == 0] & 4) == 0).all()                      # never on a ray that is not traced back
+    cam.close()
+    # without the LUT the bit is never set
+    cam2 = _camera(dict(p, kolbSamplingLUT=False))
+    _, fl2 = _lib_trace(cam2, o[keep & beyond][:64], d[keep & beyond][:64])
+    assert (fl2 & 1).any() and ((fl2 & 4) == 0).all()
+    cam2.close()
+
+
+def test_model_and_domain_reasons():
+    ray = ((0.05, 0.02, -3.0), (0.01, -0.02, -1.0))
+    for over, why in ((dict(lensModel=_capi.LENS_NONE), MODEL), (dict(focalLength=-10.0), OUTSIDE_DOMAIN)):
+        p = dict(camera_params("C3"), **over)
+        cam = _camera(p)
+        sx, sy, f = cam.trace_back_ray(*ray)
+        assert f & 1 == 0 and _reason(f) == why and np.array([sx, sy], np.float32).view(np.uint32).tolist() == [0, 0], (over, hex(f))
+        assert TraceBack(cam.info(), p).trace([ray[0]], [ray[1]])["reason"][0] == why
+        cam.close()
+    p = dict(camera_params("C1"), useDof=False)
+    cam = _camera(p)
+    sx, sy, f = cam.trace_back_ray(*ray)
+    assert f & 1 == 0 and _reason(f) == MODEL and np.array([sx, sy], np.float32).view(np.uint32).tolist() == [0, 0]
+    cam.close()
+
+
+@pytest.mark.parametrize("name", ["C2", "C3"])
+def test_scale_and_placement_invariance(oracle_lib, name):
+    R = round_trip(oracle_lib, name)
+    cam, T = R["cam"], R["T"]
+    o, d = tc.dyadic_lines(cam.info(), 1024)
+    ref = T.trace(o, d)
+    keep = ref["traced"] & ~T.decision_edge(ref)
+    assert keep.sum() >= 512
+    o, d = o[keep], d[keep]
+    base_ps, base_fl = _lib_trace(cam, o, d)
+    assert (base_fl & 1 == 1).all()
+    for move in (0.0, 10.0, 1.0e4):
+        om = o + move * d
+        assert np.array_equal(om.astype(np.float32).astype(np.float64), om)   # the moved start point is exact: the same line
+        for scale in (1.0e-3, 2.0 ** -10, 1.0, 2.0 ** 10, 1.0e3):
+            ps, fl = _lib_trace(cam, om, (d * scale).astype(np.float32))
+            assert np.array_equal(fl, base_fl), (move, scale)
+            assert np.abs(ps.astype(np.float64) - base_ps).max() <= 4.0 * R["e_max"], (move, scale, np.abs(ps - base_ps).max())
+
+
+DRIVER = r"""
+#include "traceback.hpp"
+extern "C" int zt_trace(int model, float tanFov, int count, const float *radius, const float *thickness, const float *ior, const float *aperture,
+                        int apertureElement, float userApertureRadius, float originShift, float sensorWidth, int useLUT, int lutSize, int domain,
+                        float apertureRadius, float focalDistance, int useDof, float ovDistance, float ovRadius,
+                        long n, const float *o, const float *d, float *screen, unsigned *flags)
+{
+    zoic::TraceBackTable T;
+    zoic::fill_traceback_table(T, model, tanFov, count, radius, thickness, ior, aperture, apertureElement, userApertureRadius, originShift,
+                               sensorWidth, useLUT != 0, lutSize, domain != 0, apertureRadius, focalDistance, useDof != 0, ovDistance, ovRadius);
+    for (long i = 0; i < n; ++i)
+        flags[i] = zoic::trace_back_ray(T, o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2], screen[2 * i], screen[2 * i + 1]);
+    return 0;
+}
+"""
+
+
+def _clangxx():
+    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
+        if c and os.path.exists(c):
+            return c
+    pytest.fail("no clang++ to build the host driver of csrc/traceback.hpp")
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    d = tmp_path_factory.mktemp("tbdriver")
+    src, so = d / "driver.cpp", d / "driver.so"
+    src.write_text(DRIVER)
+    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
+                           "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(so)])
+    return ctypes.CDLL(str(so))
+
+
+def _drive(driver, cam, p, o, d):
+    info = cam.info()
+    n = info["lensCount"]
+    el = [np.ascontiguousarray(info["elements"][:, k], dtype=np.float32) for k in range(4)]
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    scr = np.zeros((len(o), 2), np.float32)
+    fl = np.zeros(len(o), np.uint32)
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    F = ctypes.c_float
+    driver.zt_trace(int(p["lensModel"]), F(info["tan_fov"]), n, P(el[0]), P(el[1]), P(el[2]), P(el[3]), info["apertureElement"],
+                    F(info["userApertureRadius"]), F(info["originShift"]), F(p["sensorWidth"]),
+                    int(bool(p["kolbSamplingLUT"]) and len(info["lutKeys"]) > 0), len(info["lutKeys"]), int(not info["fastRunsStrict"]),
+                    F(info["apertureRadius"]), F(p["focalDistance"]), int(bool(p["useDof"])), F(p.get("opticalVignettingDistance", 0.0)),
+                    F(p.get("opticalVignettingRadius", 1.0)), ctypes.c_long(len(o)), P(o), P(d), P(scr), P(fl))
+    return scr, fl
+
+
+@pytest.mark.parametrize("name", ["C3", "C4", "C1-vignetting"])
+def test_host_build_gives_the_library_bits(oracle_lib, driver, name):
+    R = round_trip(oracle_lib, name)
+    cam = R["cam"]
+    sets = [(R["o"][::4], R["d"][::4]), tc.non_finite_rays(), tc.random_lines(cam.info(), 4096)]
+    if name in tc.KOLB:
+        sets += list(tc.rejection_families(cam.info(), R["o"][::16], R["d"][::16]).values())
+    seen = set()
+    for o, d in sets:
+        scr, fl = _drive(driver, cam, R["p"], o, d)
+        ps, lf = _lib_trace(cam, o, d)
+        assert np.array_equal(lf, fl)
+        assert np.array_equal(ps.view(np.uint32), scr.view(np.uint32))
+        seen |= set(_reason(fl[fl & 1 == 0]).tolist())
+    assert len(seen) >= (4 if name in tc.KOLB else 2), seen
+
+
+def test_errors():
+    lib = _capi.load()
+    o, d = _capi.Vec3(0.05, 0.02, -3.0), _capi.Vec3(0.0, 0.0, -1.0)
+    ps = (ctypes.c_float * 2)()
+    f = ctypes.c_uint32()
+    assert lib.zoic_trace_back_ray(None, ctypes.byref(o), ctypes.byref(d), ps, ctypes.byref(f)) == 1
+    assert lib.zoic_trace_back_rays_device(None, 4, None, None, None, None) == 1
+    fresh = ZoicCamera(device=-1)
+    with pytest.raises(ZoicError) as e:
+        fresh.trace_back_ray((0.05, 0.02, -3.0), (0.0, 0.0, -1.0))
+    assert e.value.status_name == "ZOIC_ERR_NOT_UPDATED"
+    fresh.close()
+    cam = _camera(camera_params("C2"))
+    assert lib.zoic_trace_back_ray(cam._h, None, ctypes.byref(d), ps, None) == 1
+    assert lib.zoic_trace_back_ray(cam._h, ctypes.byref(o), None, ps, None) == 1
+    assert lib.zoic_trace_back_ray(cam._h, ctypes.byref(o), ctypes.byref(d), None, None) == 1
+    assert lib.zoic_trace_back_ray(cam._h, ctypes.byref(o), ctypes.byref(d), ps, None) == 0   # flags may be NULL
+    with pytest.raises(ZoicError) as e:   # a tables-only camera has no device
+        cam.trace_back(np.zeros((4, 8), np.float32))
+    assert e.value.status_name == "ZOIC_ERR_NO_DEVICE"
+    assert lib.zoic_trace_back_rays_device(cam._h, 0, None, None, None, None) != 0   # (no device comes before n = 0, as for the other batch calls)
+    cam.close()

@@ -1,0 +1,132 @@
+"""Ray sets shared by tests/test_traceback_cpu.py and tests/test_traceback_gpu.py: the configurations, the forward records the
+oracle writes for a small frame, and the families of rays a trace-back must refuse."""
+import ctypes
+
+import numpy as np
+
+from zoic_amd import _capi
+from zoic_amd.camera import lens_path
+from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states, synthetic_samples
+
+W, H, SPP = 192, 108, 2          # 41 472 rays
+N = W * H * SPP
+# name -> (benchmark configuration, parameter overrides)
+KOLB = {"C2": ("C2", {}), "C3": ("C3", {}), "C4": ("C4", {}), "C5": ("C5", {}),
+        "triplet": ("C2", dict(lensDataPath=lens_path("triplet_f2.5.dat")))}
+THIN = {"C1": ("C1", {}), "C1-vignetting": ("C1", dict(opticalVignettingDistance=8.0, opticalVignettingRadius=1.0))}
+CONFIGS = dict(KOLB, **THIN)
+
+
+def params_of(name):
+    cfg, over = CONFIGS[name]
+    return dict(camera_params(cfg), **over)
+
+
+def update(cam, p):
+    """update a ZoicCamera or an OracleCamera with p (the procedural bokeh image where p asks for one)"""
+    if p.get("useImage"):
+        cam.set_bokeh_image(hexagon_bokeh())
+    cam.update(**p)
+    return cam
+
+
+def frame_samples():
+    return synthetic_samples(N, W, H, SPP), ray_rng_states(N)
+
+
+def oracle_records(oracle_lib, p):
+    """the forward records of the frame (the STRICT kernel's bits): samples (N,4), origin (N,3), dir (N,3), weight (N,)"""
+    s, st = frame_samples()
+    oc = update(oracle_lib.OracleCamera(), p)
+    r = oc.create_rays(s, rng_states=st)
+    out = s, r["origin"].T.copy(), r["dir"].T.copy(), r["weight"].copy()
+    oc.close()
+    return out
+
+
+def unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def rejection_families(info, o, d, seed=3):
+    """Rays made from live forward records (o, d: (m,3)) of a RAYTRACED camera that a trace-back must refuse, by family:
+    name -> (origin (k,3) f32, dir (k,3) f32).  `shifted`: moved 2 cm out along the ray, then sideways by 0.5 ... 3 front housing radii;
+    `tilted`: the direction turned by 2 ... 45 degrees about an axis across the optical axis; `negated`: dir = -dir; `behind`: the
+    start point 0.3 ... 2 cm back along the ray, inside the lens."""
+    rng = np.random.default_rng(seed)
+    m = len(o)
+    o = o.astype(np.float64)
+    d = unit(d.astype(np.float64))
+    rf = float(info["elements"][info["lensCount"] - 1, 3]) * 0.5
+    az = rng.uniform(0, 2 * np.pi, m)
+    side = np.stack([np.cos(az), np.sin(az), np.zeros(m)], 1)
+    shifted = o + 2.0 * d + side * (rng.uniform(0.5, 3.0, m) * rf)[:, None]
+    ang = np.radians(rng.uniform(2.0, 45.0, m))
+    axis = np.stack([-np.sin(az), np.cos(az), np.zeros(m)], 1)
+    tilted = d * np.cos(ang)[:, None] + np.cross(axis, d) * np.sin(ang)[:, None] + axis * ((axis * d).sum(1) * (1 - np.cos(ang)))[:, None]
+    behind = o - d * rng.uniform(0.3, 2.0, m)[:, None]
+    f = np.float32
+    return {"shifted": (shifted.astype(f), d.astype(f)), "tilted": (o.astype(f), tilted.astype(f)),
+            "negated": (o.astype(f), (-d).astype(f)), "behind": (behind.astype(f), d.astype(f))}
+
+
+def non_finite_rays():
+    """(origin, dir) pairs with a NaN / inf coordinate or dir = 0: all kTbNonFinite"""
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    o = np.array([[nan, 0, -1], [0, inf, -1], [0, 0, -inf], [0, 0, -1], [0, 0, -1], [0, 0, -1], [0.1, 0.1, -1], [0.1, 0.1, -1]], np.float32)
+    d = np.array([[0, 0, -1], [0, 0, -1], [0, 0, -1], [nan, 0, -1], [0, -inf, -1], [0, 0, nan], [0, 0, 0], [-0.0, 0.0, -0.0]], np.float32)
+    return o, d
+
+
+def random_lines(info, m, seed=11):
+    """m random lines towards the front element: start points up to 200 cm out, aimed at points up to 1.5 housing radii off axis"""
+    rng = np.random.default_rng(seed)
+    n = int(info["lensCount"])
+    rf = float(info["elements"][n - 1, 3]) * 0.5 if n else 1.0
+    r, a = rf * 1.5 * np.sqrt(rng.uniform(0, 1, m)), rng.uniform(0, 2 * np.pi, m)
+    target = np.stack([r * np.cos(a), r * np.sin(a), np.zeros(m)], 1)
+    depth = 10.0 ** rng.uniform(-1, 2.3, m)
+    start = np.stack([rng.normal(0, 0.4, m) * depth, rng.normal(0, 0.4, m) * depth, -depth], 1)
+    d = (start - target) * (10.0 ** rng.uniform(-3, 3, m))[:, None]
+    return start.astype(np.float32), d.astype(np.float32)
+
+
+def dyadic_lines(info, m, seed=5):
+    """Lines whose moved start points are exact in f32: origin = (x0, y0, z0) with x0, y0 multiples of 2^-12 inside 0.6 front housing
+    radii and z0 a whole number of cm in front of the lens, dir = (a / 256, b / 256, -1).  origin + t dir is then exactly representable
+    for t = 10 and t = 10000 too, so every variant describes the SAME line."""
+    rng = np.random.default_rng(seed)
+    n = int(info["lensCount"])
+    rf = float(info["elements"][n - 1, 3]) * 0.5
+    r, a = 0.6 * rf * np.sqrt(rng.uniform(0, 1, m)), rng.uniform(0, 2 * np.pi, m)
+    xy = np.round(np.stack([r * np.cos(a), r * np.sin(a)], 1) * 4096.0) / 4096.0
+    z0 = -float(np.ceil(abs(rf) + 1.0))
+    o = np.concatenate([xy, np.full((m, 1), z0)], 1)
+    d = np.concatenate([rng.integers(-24, 25, (m, 2)) / 256.0, np.full((m, 1), -1.0)], 1)
+    return o, d
+
+
+def lib_trace(cam, o, d):
+    """zoic_trace_back_ray on every ray: (ps (m,2) float32, flags (m,) uint32)"""
+    lib, h = _capi.load(), cam._h
+    ps = np.zeros((len(o), 2), np.float32)
+    fl = np.zeros(len(o), np.uint32)
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    V = ctypes.POINTER(_capi.Vec3)
+    po, pd = o.ctypes.data, d.ctypes.data
+    pp, pf = ps.ctypes.data, fl.ctypes.data
+    fn = lib.zoic_trace_back_ray
+    for i in range(len(o)):
+        rc = fn(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pd + 12 * i, V), ctypes.cast(pp + 8 * i, ctypes.POINTER(ctypes.c_float)),
+                ctypes.cast(pf + 4 * i, ctypes.POINTER(ctypes.c_uint32)))
+        assert rc == 0, rc
+    return ps, fl
+
+
+def reason(f):
+    return (np.asarray(f).astype(np.int64) >> 8) & 15
+
+
+def iface(f):
+    return (np.asarray(f).astype(np.int64) >> 16) & 63

@@ -121,6 +121,8 @@ SYMBOLS = {
     "zoic_project_points_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
     "zoic_project_point": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_camera_set_reverse_projection": (C.c_int, [_vp, C.c_int]),
+    "zoic_trace_back_rays_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
+    "zoic_trace_back_ray": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
     "zoic_host_free": (None, [_vp]),
     "zoic_host_register": (C.c_int, [_vp, C.c_size_t]),

@@ -450,6 +450,61 @@ class ZoicCamera:
         self._check(self._lib.zoic_project_points_device(self._h, n, points.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
         return out, flags
 
+    def trace_back_ray(self, origin, dir):
+        """Trace-back of one camera ray on the host (zoic_trace_back_ray): (sx, sy, flags).  origin / dir in the frame of the records
+        the forward calls write, dir pointing into the scene (any length).  flags bit 0: the ray reaches the sensor unclipped; bit 2:
+        beyond the exit-pupil LUT; bits 8-11: why not; bits 16-21: the interface where it ended (csrc/traceback.hpp).  Works on a
+        tables-only camera (device=-1)."""
+        o = _capi.Vec3(*[float(v) for v in origin])
+        d = _capi.Vec3(*[float(v) for v in dir])
+        ps = (C.c_float * 2)(0.0, 0.0)
+        f = C.c_uint32(0)
+        self._check(self._lib.zoic_trace_back_ray(self._h, C.byref(o), C.byref(d), ps, C.byref(f)))
+        return float(ps[0]), float(ps[1]), int(f.value)
+
+    def trace_back(self, rays, out=None, flags=None, stream=None):
+        """Trace-back of n camera rays (zoic_trace_back_rays_device): returns (screen (n,2) float32, flags (n,) int32).
+
+        rays: an (n,8) float32 device tensor of zoic_ray records, or the dict a create_rays call on device tensors returned (its
+                     "rays" buffer is read in place) -> asynchronous on `stream` (default: torch's current stream); out / flags:
+                     optional (n,2) float32 and (n,) int32 tensors on the rays' device to write into.
+        numpy in  -> (n,) zoic_ray records (or the dict of a numpy create_rays call) or an (n,8) float32 array: copied to the camera's
+                     device through torch, the call waits and returns numpy arrays (out and flags must be None there)."""
+        import torch
+        if isinstance(rays, dict):
+            rays = rays["rays"]
+        if not _is_torch(rays):
+            if out is not None or flags is not None:
+                raise ValueError("out and flags are for torch rays")
+            a = np.asarray(rays)
+            if a.dtype == np.dtype(_capi.RAY_DTYPE):
+                a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32")
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                self._check(self._lib.zoic_trace_back_rays_device(self._h, a.shape[0], None, None, None, None))
+            dev = torch.device("cuda", self.device)
+            scr, fl = self.trace_back(torch.from_numpy(a).to(dev))
+            torch.cuda.synchronize(dev)
+            return scr.cpu().numpy(), fl.cpu().numpy()
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+            raise ValueError("rays must be a contiguous (n,8) float32 device tensor")
+        if rays.device.index != self.device:
+            raise ValueError("rays live on cuda:%s but this camera is bound to device %d" % (rays.device.index, self.device))
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
+        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rays.device:
+            raise ValueError("out must be a contiguous (n,2) float32 tensor on the rays' device")
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != rays.device:
+            raise ValueError("flags must be a contiguous (n,) int32 tensor on the rays' device")
+        st = stream if stream is not None else torch.cuda.current_stream(rays.device).cuda_stream
+        self._check(self._lib.zoic_trace_back_rays_device(self._h, n, rays.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
+        return out, flags
+
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
         """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1).
 

@@ -36,6 +36,7 @@
 #include "mailbox.hpp"
 #include "spectral.hpp"
 #include "reverse.hpp"
+#include "traceback.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
 
@@ -290,6 +291,7 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     std::vector<float> abbeOverride;             // zoic_camera_set_abbe_numbers: V-numbers in file order (empty: the prescription's own)
     ReverseTable reverse{};                      // reverse.hpp: the projection table of the tables above (filled by every successful update)
     bool reverseOn = false;                      // zoic_camera_set_reverse_projection: zoic_camera_reverse_ray answers with it
+    TraceBackTable traceBack{};                  // traceback.hpp: the trace-back table of the tables above (filled by every successful update)
 
     TidState *tid_state(uint16_t tid);
     CallContext *lease_context(hipError_t &err);
@@ -781,6 +783,27 @@ void fill_reverse(zoic_camera *cam)
                        L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain);
 }
 
+// the trace-back's table (traceback.hpp) of the camera's current tables
+void fill_traceback(zoic_camera *cam)
+{
+    const zoic_params &p = cam->params.p;
+    const LensSystem &L = cam->lens;
+    if (p.lensModel != ZOIC_RAYTRACED) {
+        fill_traceback_table(cam->traceBack, p.lensModel == ZOIC_THINLENS ? 0 : 2, cam->tanFov, 0, nullptr, nullptr, nullptr, nullptr, -1, 0.0f,
+                             0.0f, 0.0f, false, 0, false, cam->apertureRadius, p.focalDistance, p.useDof != 0, p.opticalVignettingDistance,
+                             p.opticalVignettingRadius);
+        return;
+    }
+    const int n = static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces));
+    float radius[kMaxSurfaces], thickness[kMaxSurfaces], ior[kMaxSurfaces], aperture[kMaxSurfaces];
+    for (int i = 0; i < n; ++i) {
+        radius[i] = L.rows[i].radius; thickness[i] = L.rows[i].thickness; ior[i] = L.rows[i].ior; aperture[i] = L.rows[i].aperture;
+    }
+    fill_traceback_table(cam->traceBack, 1, cam->tanFov, n, radius, thickness, ior, aperture, L.apertureElement, L.userApertureRadius,
+                         L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain, 0.0f, 0.0f,
+                         false, 0.0f, 0.0f);
+}
+
 // device (or managed) memory: what the batch projection may read and write
 bool is_device_memory(const void *ptr)
 {
@@ -1116,6 +1139,7 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
         t.seed = cam->seed;
     }
     fill_reverse(cam);   // (RAYTRACED: fastDomain is still the geometric test here; the self-check below may narrow it)
+    fill_traceback(cam);
     cam->updated = true;
     // the FAST modes are kept only for a camera they are good for (fast_self_check above; the geometric test comes first).
     // The verdict depends on the lens tables, the LUT and the bokeh tables only: an update that rebuilt none of them (exposure,
@@ -1817,6 +1841,32 @@ zoic_status zoic_project_points_device(zoic_camera *cam, uint64_t n, const float
     if (!is_device_memory(d_points) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
         return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points, d_screen and d_flags must be device memory");
     const int rc = launch_project_points(cam->reverse, d_points, n, d_screen, d_flags, stream);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_ray(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps, uint32_t *flags)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!origin || !dir || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir and Ps must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    const uint32_t f = trace_back_ray(cam->traceBack, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0], Ps[1]);
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_rays_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_screen, uint32_t *d_flags, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
+    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    if (!is_device_memory(d_rays) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_screen and d_flags must be device memory");
+    const int rc = launch_trace_back(cam->traceBack, d_rays, n, d_screen, d_flags, stream);
     if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
     return ZOIC_OK;
 }
