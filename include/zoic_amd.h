@@ -389,7 +389,8 @@ enum {
     ZOIC_PROJECT_NO_ROOT = 2,        /* no chief ray: a sphere missed or total internal reflection on every candidate (or Ps overflows) */
     ZOIC_PROJECT_NON_FINITE = 3,     /* a NaN or infinite coordinate */
     ZOIC_PROJECT_MODEL_NONE = 4,     /* lensModel NONE */
-    ZOIC_PROJECT_OUTSIDE_DOMAIN = 5  /* RAYTRACED camera outside the geometric domain above */
+    ZOIC_PROJECT_OUTSIDE_DOMAIN = 5, /* RAYTRACED camera outside the geometric domain above */
+    ZOIC_PROJECT_WAVELENGTH = 6      /* the spectral calls below: the point's wavelength is outside [360, 830] nm or NaN */
 };
 /* n points (packed float3, device memory, 4-byte aligned) -> n (sx, sy) pairs (device memory, 8-byte aligned) and, unless d_flags is
  * NULL, n flag words (device memory).  Works whatever zoic_camera_set_reverse_projection says.  Asynchronous on `stream`.
@@ -435,7 +436,8 @@ enum {
     ZOIC_TRACE_BACK_TIR = 4,            /* total internal reflection */
     ZOIC_TRACE_BACK_NON_FINITE = 5,     /* a NaN or infinite coordinate, dir = 0, or Ps overflows */
     ZOIC_TRACE_BACK_MODEL = 6,          /* lensModel NONE, or THINLENS without useDof */
-    ZOIC_TRACE_BACK_OUTSIDE_DOMAIN = 7  /* RAYTRACED camera outside the geometric domain */
+    ZOIC_TRACE_BACK_OUTSIDE_DOMAIN = 7, /* RAYTRACED camera outside the geometric domain */
+    ZOIC_TRACE_BACK_WAVELENGTH = 8      /* the spectral calls below: the ray's wavelength is outside [360, 830] nm or NaN */
 };
 /* n zoic_ray records (device memory, 16-byte aligned) -> n (sx, sy) pairs (device memory, 8-byte aligned) and, unless d_flags is NULL,
  * n flag words (device memory).  d_rays may be the buffer zoic_create_rays_device wrote, on the same stream, without a copy.
@@ -447,6 +449,38 @@ zoic_status zoic_trace_back_rays_device(zoic_camera *cam, uint64_t n, const zoic
 /* The host build of the same code for one ray (no GPU round trip; works on a ZOIC_DEVICE_NONE camera).  flags may be NULL. */
 zoic_status zoic_trace_back_ray(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps /* [2] */,
                                 uint32_t *flags /* may be NULL */);
+
+/* ---- the backward paths at a wavelength per item (opt-in; csrc/backward_spectral.hpp has the full definition) ----------------
+ * zoic_create_rays_spectral_device traces every ray at a wavelength of its own; these four calls are zoic_trace_back_* and
+ * zoic_project_point* for such rays and points, so that a light tracer, a splatter or a bidirectional integrator meets the camera the
+ * forward pass rendered with: a spectral record traced back at its wavelength returns to its sample, and a point splatted in blue and in
+ * red lands on the two pixels the forward pass puts it on (lateral colour).
+ *   Index   the medium behind interface i has n_i(lambda) = n_d,i + B_i (1/lambda^2 - 1/lambda_d^2) in the forward kernels' own f32
+ *           operations (csrc/spectral.hpp spectral_dl, spectral_ior), n_d and B as zoic_camera_get_dispersion reports them (a
+ *           zoic_camera_set_abbe_numbers override is honoured, from the next call on); in front of the front element exactly 1.0f.
+ *   Ratio   every interface takes the true ratio of its two media, as the d-line calls' tables do: trace-back n_front / n_rear,
+ *           projection n_rear / n_front towards the front and n_front / n_rear towards the rear, each ONE correctly rounded f32 division.
+ *           On the device that is the compiler's IEEE division (v_div_scale / v_rcp / FMA refinement / v_div_fmas / v_div_fixup: the
+ *           library is built without fast-math), on the host divss: the same bits (csrc/backward_spectral.hpp, "Division").
+ *   The d-line's own: geometry, housings, the stop limit, the sensor plane (originShift), the focal-length rescale, the LUT flag, the
+ *           domain gate, the cap test, the projection's paraxial first guess, every step that reads no index.  The camera is focused at
+ *           587.5618 nm, as on the forward side.
+ *   At wavelength 587.5618f every index is n_d exactly: Ps and flags equal the d-line calls' bit for bit, for every input.
+ *   A wavelength outside [360, 830] nm, or NaN, rejects that item alone, before anything else is looked at: Ps = (+0, +0), bit 0 clear,
+ *           reason ZOIC_TRACE_BACK_WAVELENGTH / ZOIC_PROJECT_WAVELENGTH.  THINLENS and NONE cameras ignore the wavelength apart from
+ *           that: their answers are the d-line calls'.
+ * d_wavelengths: n f32 (nm), device memory, 4-byte aligned.  Every other argument, the error codes, the stream semantics and the
+ * threading contract are those of the d-line call of the same name; no counter and no retry stream is touched; host and device give the
+ * same bits for the same item in every precision mode.  zoic_camera_reverse_ray is unchanged (the d-line projection). */
+zoic_status zoic_trace_back_rays_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths /* n */,
+                                                 float *d_screen /* n x 2 */, uint32_t *d_flags /* may be NULL */, void *stream);
+zoic_status zoic_trace_back_ray_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm,
+                                         float *Ps /* [2] */, uint32_t *flags /* may be NULL */);
+zoic_status zoic_project_points_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */,
+                                                const float *d_wavelengths /* n */, float *d_screen /* n x 2 */,
+                                                uint32_t *d_flags /* may be NULL */, void *stream);
+zoic_status zoic_project_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, float *Ps /* [2] */,
+                                        uint32_t *flags /* may be NULL */);
 
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins

@@ -17,6 +17,9 @@ THINLENS, RAYTRACED, LENS_NONE = 0, 1, 2
 PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_UNCHECKED = 0, 1, 2
 FRAME_RECORDS, FRAME_PAYLOAD, FRAME_PAYLOAD_SPARSE, FRAME_PAYLOAD_AUTO = 0, 1, 2, 3
 TILE_MAX_SAMPLES = 65536
+# reasons the spectral backward calls add (bits 8-11 of their flag words): the item's wavelength is outside [360, 830] nm or NaN
+TRACE_BACK_WAVELENGTH = 8
+PROJECT_WAVELENGTH = 6
 
 STATUS_NAMES = ["ZOIC_OK", "ZOIC_ERR_INVALID_ARGUMENT", "ZOIC_ERR_LENS_PATH", "ZOIC_ERR_LENS_COLUMNS",
                 "ZOIC_ERR_LENS_PARSE", "ZOIC_ERR_MULTI_APERTURE", "ZOIC_ERR_NO_APERTURE", "ZOIC_ERR_TOO_MANY_LENSES",
@@ -123,6 +126,10 @@ SYMBOLS = {
     "zoic_camera_set_reverse_projection": (C.c_int, [_vp, C.c_int]),
     "zoic_trace_back_rays_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
     "zoic_trace_back_ray": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32)]),
+    "zoic_trace_back_rays_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "zoic_trace_back_ray_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
+    "zoic_project_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "zoic_project_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
     "zoic_host_free": (None, [_vp]),
     "zoic_host_register": (C.c_int, [_vp, C.c_size_t]),

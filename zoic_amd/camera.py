@@ -403,34 +403,55 @@ class ZoicCamera:
         """Opt in (True) or out (False, the default) of answering reverse_ray / camera_reverse_ray with the projection."""
         self._check(self._lib.zoic_camera_set_reverse_projection(self._h, 1 if enable else 0))
 
-    def project_point(self, Po):
+    def _wavelength_tensor(self, wavelengths, n, like):
+        """the (n,) float32 wavelength tensor of a batch call, validated as create_rays(..., wavelengths=) validates its own"""
+        import torch
+        if not _is_torch(wavelengths):
+            raise TypeError("torch items need a torch wavelength tensor")
+        if wavelengths.dtype != torch.float32 or tuple(wavelengths.shape) != (n,) or not wavelengths.is_contiguous() or wavelengths.device != like.device:
+            raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the items' device")
+        return wavelengths
+
+    def project_point(self, Po, wavelength=None):
         """Reverse projection of one point on the host (zoic_project_point): (sx, sy, flags).  Po in the frame of the records the
         forward calls write.  flags bit 0: projected; bit 1: the chief ray is clipped; bit 2: beyond the exit-pupil LUT; bits 8-11:
-        the reason a point is not projected (csrc/reverse.hpp).  Works on a tables-only camera (device=-1)."""
+        the reason a point is not projected (csrc/reverse.hpp).  Works on a tables-only camera (device=-1).
+        wavelength (nm): the projection through the glass at that wavelength (zoic_project_point_spectral, csrc/backward_spectral.hpp);
+        outside [360, 830] or NaN: not projected, reason _capi.PROJECT_WAVELENGTH."""
         po = _capi.Vec3(*[float(v) for v in Po])
         ps = (C.c_float * 2)(0.0, 0.0)
         f = C.c_uint32(0)
+        if wavelength is not None:
+            self._check(self._lib.zoic_project_point_spectral(self._h, C.byref(po), float(wavelength), ps, C.byref(f)))
+            return float(ps[0]), float(ps[1]), int(f.value)
         self._check(self._lib.zoic_project_point(self._h, C.byref(po), ps, C.byref(f)))
         return float(ps[0]), float(ps[1]), int(f.value)
 
-    def project_points(self, points, out=None, flags=None, stream=None):
+    def project_points(self, points, out=None, flags=None, stream=None, wavelengths=None):
         """Reverse projection of (n,3) float32 points (zoic_project_points_device): returns (screen (n,2) float32, flags (n,) int32).
 
         numpy in  -> the points are copied to the camera's device through torch, the call waits and returns numpy arrays (out and
                      flags must be None there).
         torch device tensor in -> asynchronous on `stream` (default: torch's current stream); out / flags: optional (n,2) float32 and
-                     (n,) int32 tensors on the points' device to write into."""
+                     (n,) int32 tensors on the points' device to write into.
+        wavelengths: (n,) float32 (nm), numpy with numpy points, a device tensor with device points: every point projected at its own
+                     wavelength (zoic_project_points_spectral_device); None: the d-line call."""
         import torch
         if not _is_torch(points):
             if out is not None or flags is not None:
                 raise ValueError("out and flags are for torch points")
+            if wavelengths is not None and _is_torch(wavelengths):
+                raise TypeError("numpy points need numpy wavelengths")
             a = np.ascontiguousarray(points, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != 3:
                 raise ValueError("points must be (n, 3)")
             if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                if wavelengths is not None:
+                    self._check(self._lib.zoic_project_points_spectral_device(self._h, a.shape[0], None, None, None, None, None))
                 self._check(self._lib.zoic_project_points_device(self._h, a.shape[0], None, None, None, None))
             dev = torch.device("cuda", self.device)
-            scr, fl = self.project_points(torch.from_numpy(a).to(dev))
+            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            scr, fl = self.project_points(torch.from_numpy(a).to(dev), wavelengths=tw)
             torch.cuda.synchronize(dev)
             return scr.cpu().numpy(), fl.cpu().numpy()
         if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
@@ -447,35 +468,50 @@ class ZoicCamera:
         if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != points.device:
             raise ValueError("flags must be a contiguous (n,) int32 tensor on the points' device")
         st = stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream
+        if wavelengths is not None:
+            w = self._wavelength_tensor(wavelengths, n, points)
+            self._check(self._lib.zoic_project_points_spectral_device(self._h, n, points.data_ptr(), w.data_ptr(), out.data_ptr(), flags.data_ptr(),
+                                                                      C.c_void_p(st)))
+            return out, flags
         self._check(self._lib.zoic_project_points_device(self._h, n, points.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
         return out, flags
 
-    def trace_back_ray(self, origin, dir):
+    def trace_back_ray(self, origin, dir, wavelength=None):
         """Trace-back of one camera ray on the host (zoic_trace_back_ray): (sx, sy, flags).  origin / dir in the frame of the records
         the forward calls write, dir pointing into the scene (any length).  flags bit 0: the ray reaches the sensor unclipped; bit 2:
         beyond the exit-pupil LUT; bits 8-11: why not; bits 16-21: the interface where it ended (csrc/traceback.hpp).  Works on a
-        tables-only camera (device=-1)."""
+        tables-only camera (device=-1).
+        wavelength (nm): the trace through the glass at that wavelength (zoic_trace_back_ray_spectral, csrc/backward_spectral.hpp);
+        outside [360, 830] or NaN: not traced back, reason _capi.TRACE_BACK_WAVELENGTH."""
         o = _capi.Vec3(*[float(v) for v in origin])
         d = _capi.Vec3(*[float(v) for v in dir])
         ps = (C.c_float * 2)(0.0, 0.0)
         f = C.c_uint32(0)
+        if wavelength is not None:
+            self._check(self._lib.zoic_trace_back_ray_spectral(self._h, C.byref(o), C.byref(d), float(wavelength), ps, C.byref(f)))
+            return float(ps[0]), float(ps[1]), int(f.value)
         self._check(self._lib.zoic_trace_back_ray(self._h, C.byref(o), C.byref(d), ps, C.byref(f)))
         return float(ps[0]), float(ps[1]), int(f.value)
 
-    def trace_back(self, rays, out=None, flags=None, stream=None):
+    def trace_back(self, rays, out=None, flags=None, stream=None, wavelengths=None):
         """Trace-back of n camera rays (zoic_trace_back_rays_device): returns (screen (n,2) float32, flags (n,) int32).
 
         rays: an (n,8) float32 device tensor of zoic_ray records, or the dict a create_rays call on device tensors returned (its
                      "rays" buffer is read in place) -> asynchronous on `stream` (default: torch's current stream); out / flags:
                      optional (n,2) float32 and (n,) int32 tensors on the rays' device to write into.
         numpy in  -> (n,) zoic_ray records (or the dict of a numpy create_rays call) or an (n,8) float32 array: copied to the camera's
-                     device through torch, the call waits and returns numpy arrays (out and flags must be None there)."""
+                     device through torch, the call waits and returns numpy arrays (out and flags must be None there).
+        wavelengths: (n,) float32 (nm), numpy with numpy rays, a device tensor with device rays -- for the records of
+                     create_rays(samples, wavelengths=w), the same w: every ray traced back at its own wavelength
+                     (zoic_trace_back_rays_spectral_device); None: the d-line call."""
         import torch
         if isinstance(rays, dict):
             rays = rays["rays"]
         if not _is_torch(rays):
             if out is not None or flags is not None:
                 raise ValueError("out and flags are for torch rays")
+            if wavelengths is not None and _is_torch(wavelengths):
+                raise TypeError("numpy rays need numpy wavelengths")
             a = np.asarray(rays)
             if a.dtype == np.dtype(_capi.RAY_DTYPE):
                 a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
@@ -483,9 +519,12 @@ class ZoicCamera:
             if a.ndim != 2 or a.shape[1] != 8:
                 raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32")
             if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                if wavelengths is not None:
+                    self._check(self._lib.zoic_trace_back_rays_spectral_device(self._h, a.shape[0], None, None, None, None, None))
                 self._check(self._lib.zoic_trace_back_rays_device(self._h, a.shape[0], None, None, None, None))
             dev = torch.device("cuda", self.device)
-            scr, fl = self.trace_back(torch.from_numpy(a).to(dev))
+            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            scr, fl = self.trace_back(torch.from_numpy(a).to(dev), wavelengths=tw)
             torch.cuda.synchronize(dev)
             return scr.cpu().numpy(), fl.cpu().numpy()
         if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
@@ -502,6 +541,11 @@ class ZoicCamera:
         if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != rays.device:
             raise ValueError("flags must be a contiguous (n,) int32 tensor on the rays' device")
         st = stream if stream is not None else torch.cuda.current_stream(rays.device).cuda_stream
+        if wavelengths is not None:
+            w = self._wavelength_tensor(wavelengths, n, rays)
+            self._check(self._lib.zoic_trace_back_rays_spectral_device(self._h, n, rays.data_ptr(), w.data_ptr(), out.data_ptr(), flags.data_ptr(),
+                                                                       C.c_void_p(st)))
+            return out, flags
         self._check(self._lib.zoic_trace_back_rays_device(self._h, n, rays.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
         return out, flags
 

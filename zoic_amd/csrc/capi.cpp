@@ -36,6 +36,7 @@
 #include "mailbox.hpp"
 #include "spectral.hpp"
 #include "reverse.hpp"
+#include "backward_spectral.hpp"
 #include "traceback.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
@@ -802,6 +803,15 @@ void fill_traceback(zoic_camera *cam)
     fill_traceback_table(cam->traceBack, 1, cam->tanFov, n, radius, thickness, ior, aperture, L.apertureElement, L.userApertureRadius,
                          L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain, 0.0f, 0.0f,
                          false, 0.0f, 0.0f);
+}
+
+// the dispersion of the camera's lens in the backward tables' order (backward_spectral.hpp); as on the forward side it is taken at
+// the call, so a zoic_camera_set_abbe_numbers override needs no update
+void fill_backward(const zoic_camera *cam, BackwardDispersion &D)
+{
+    SpectralTable W;
+    fill_spectral(cam, W);
+    fill_backward_dispersion(D, W);
 }
 
 // device (or managed) memory: what the batch projection may read and write
@@ -1867,6 +1877,72 @@ zoic_status zoic_trace_back_rays_device(zoic_camera *cam, uint64_t n, const zoic
     if (!is_device_memory(d_rays) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
         return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_screen and d_flags must be device memory");
     const int rc = launch_trace_back(cam->traceBack, d_rays, n, d_screen, d_flags, stream);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_project_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, float *Ps, uint32_t *flags)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!Po || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "Po and Ps must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    BackwardDispersion D;
+    fill_backward(cam, D);
+    const uint32_t f = project_point_spectral(cam->reverse, D, wavelength_nm, Po->x, Po->y, Po->z, Ps[0], Ps[1]);
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_project_points_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points, const float *d_wavelengths, float *d_screen,
+                                                uint32_t *d_flags, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_points || (reinterpret_cast<uintptr_t>(d_points) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points must be non-NULL and 4-byte aligned");
+    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
+    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
+    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    if (!is_device_memory(d_points) || !is_device_memory(d_wavelengths) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points, d_wavelengths, d_screen and d_flags must be device memory");
+    BackwardDispersion D;
+    fill_backward(cam, D);
+    const int rc = launch_project_points_spectral(cam->reverse, D, d_points, d_wavelengths, n, d_screen, d_flags, stream);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_ray_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm, float *Ps,
+                                         uint32_t *flags)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!origin || !dir || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir and Ps must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    BackwardDispersion D;
+    fill_backward(cam, D);
+    const uint32_t f = trace_back_ray_spectral(cam->traceBack, D, wavelength_nm, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0],
+                                               Ps[1]);
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_rays_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths, float *d_screen,
+                                                 uint32_t *d_flags, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
+    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
+    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    if (!is_device_memory(d_rays) || !is_device_memory(d_wavelengths) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_wavelengths, d_screen and d_flags must be device memory");
+    BackwardDispersion D;
+    fill_backward(cam, D);
+    const int rc = launch_trace_back_spectral(cam->traceBack, D, d_rays, d_wavelengths, n, d_screen, d_flags, stream);
     if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
     return ZOIC_OK;
 }

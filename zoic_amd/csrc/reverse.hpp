@@ -62,7 +62,8 @@ namespace zoic {
 
 constexpr uint32_t kRevProjected = 1u, kRevClipped = 2u, kRevPastLut = 4u;
 constexpr uint32_t kRevReasonShift = 8u;
-enum : uint32_t { kRevBehind = 1u, kRevNoRoot = 2u, kRevNonFinite = 3u, kRevModelNone = 4u, kRevOutsideDomain = 5u };
+enum : uint32_t { kRevBehind = 1u, kRevNoRoot = 2u, kRevNonFinite = 3u, kRevModelNone = 4u, kRevOutsideDomain = 5u,
+                  kRevWavelength = 6u };   // (kRevWavelength: the spectral calls only, backward_spectral.hpp)
 constexpr int kRevMaxIter = 12;
 constexpr float kRevTol = 9.5367431640625e-07f;   // 2^-20: the distance by which the exit ray may miss the point, per max(|Q - P|, front radius)
 
@@ -108,9 +109,10 @@ struct RevRay { float x, z, ur, uz; };   // meridional state: height, z relative
 // One interface: intersection, housing clip, refraction, for a ray travelling towards +z (FWD) or -z.  The sphere in its vertex
 // form, c (x^2 + z^2) + 2 z = 0 (z relative to the vertex, c = 1 / R): the root on the vertex side (zoic.cpp:986, the larger
 // sgn(R) z of the two) in the form without cancellation.  `shift` moves z into this interface's frame.  With TAN the tangent
-// (d/ds of every state component) is carried alongside.  Returns false on a sphere miss or total internal reflection.
-template <bool TAN, bool FWD>
-ZOIC_HD bool rev_interface(const RevSurface &S, float shift, RevRay &r, RevRay &d, bool &clipped)
+// (d/ds of every state component) is carried alongside.  M gives the ratio of the two media in the direction of travel (RevDLine:
+// S.etaF / S.etaR).  Returns false on a sphere miss or total internal reflection.
+template <bool TAN, bool FWD, class Medium>
+ZOIC_HD bool rev_interface(const RevSurface &S, Medium &M, int j, float shift, RevRay &r, RevRay &d, bool &clipped)
 {
     const float c = S.curv;
     const float zr = r.z + shift;
@@ -131,7 +133,7 @@ ZOIC_HD bool rev_interface(const RevSurface &S, float shift, RevRay &r, RevRay &
     const float sg = FWD ? -1.0f : 1.0f;
     const float nx = sg * (c * hx), nz = sg * fmaf(c, hz, 1.0f);
     const float cosi = -fmaf(r.ur, nx, r.uz * nz);
-    const float eta = FWD ? S.etaF : S.etaR, eta2 = eta * eta;
+    const float eta = FWD ? M.eta_front(j, S) : M.eta_rear(j, S), eta2 = eta * eta;
     const float k2 = fmaf(eta2, cosi * cosi, 1.0f - eta2);
     if (!(k2 >= 0.0f)) return false;
     const float sk = rev_sqrt(k2);
@@ -162,18 +164,29 @@ ZOIC_HD int rev_uniform(int j)
 #endif
 }
 
+// Where an interface's eta comes from: the d-line table (RevDLine), or the indices of its two media at the point's own wavelength
+// (RevSpectral, backward_spectral.hpp).  at_stop() starts a pass at the stop; then eta_front(j, S) is called for j = stop-1 ... 0, or
+// eta_rear(j, S) for j = stop ... count-1.
+struct RevDLine {
+    ZOIC_HD void at_stop() {}
+    ZOIC_HD float eta_front(int, const RevSurface &S) { return S.etaF; }
+    ZOIC_HD float eta_rear(int, const RevSurface &S) { return S.etaR; }
+};
+
 // G(s): the ray leaving the stop's centre towards the front at sin(angle) = s, traced through the front group; G = the signed
 // distance of Q = (rQ, zq) (zq relative to the front vertex) from the line of its exit ray, dG its derivative, scale = the larger
 // component of Q - P (P the exit point).  False if the ray does not get out, or leaves away from Q.
-ZOIC_HD bool rev_front(const ReverseTable &T, float rQ, float zq, float s, float &G, float &dG, float &scale)
+template <class Medium>
+ZOIC_HD bool rev_front(const ReverseTable &T, Medium &M, float rQ, float zq, float s, float &G, float &dG, float &scale)
 {
     const float uz = rev_sqrt(fmaf(-s, s, 1.0f));
     RevRay r{0.0f, 0.0f, s, uz};
     RevRay d{0.0f, 0.0f, 1.0f, -s * rev_rcp(uz)};
     bool clipped = false;
+    M.at_stop();
     for (int jj = T.stop - 1; jj >= 0; --jj) {
         const int j = rev_uniform(jj);
-        if (!rev_interface<true, true>(T.surf[j], -T.surf[j + 1].dz, r, d, clipped)) return false;
+        if (!rev_interface<true, true>(T.surf[j], M, j, -T.surf[j + 1].dz, r, d, clipped)) return false;
     }
     const float a = rQ - r.x, b = zq - r.z;   // Q - P
     if (!(fmaf(r.ur, a, r.uz * b) > 0.0f)) return false;
@@ -184,7 +197,8 @@ ZOIC_HD bool rev_front(const ReverseTable &T, float rQ, float zq, float s, float
 }
 
 // the projection of one point: returns the flag word, writes sx, sy
-ZOIC_HD uint32_t project_point(const ReverseTable &T, float px, float py, float pz, float &sx, float &sy)
+template <class Medium = RevDLine>
+ZOIC_HD uint32_t project_point(const ReverseTable &T, float px, float py, float pz, float &sx, float &sy, Medium M = Medium())
 {
     sx = 0.0f; sy = 0.0f;
     if (T.model != 0 && T.model != 1) return kRevModelNone << kRevReasonShift;
@@ -232,7 +246,7 @@ ZOIC_HD uint32_t project_point(const ReverseTable &T, float px, float py, float 
     float sNeg = 0.0f, sPos = 0.0f, sGood = 0.0f, G = 0.0f, dG = 0.0f, scale = 0.0f;
     bool havePos = false, done = false;
     for (int it = 0; it < kRevMaxIter; ++it) {
-        if (!rev_front(T, rQ, zq, s, G, dG, scale)) {
+        if (!rev_front(T, M, rQ, zq, s, G, dG, scale)) {
             s = 0.5f * (s + sGood);   // no ray out there: back towards the last height that had one (the axis at first)
             continue;
         }
@@ -254,16 +268,18 @@ ZOIC_HD uint32_t project_point(const ReverseTable &T, float px, float py, float 
     // the back group: from the stop's centre towards the rear (the stop's own refraction first), then the sensor plane
     RevRay r{0.0f, 0.0f, -s, -rev_sqrt(fmaf(-s, s, 1.0f))}, dummy{0.0f, 0.0f, 0.0f, 0.0f};
     bool clipped = false;
+    M.at_stop();
     for (int jj = T.stop; jj < T.count; ++jj) {
         const int j = rev_uniform(jj);
-        if (!rev_interface<false, false>(T.surf[j], jj == T.stop ? 0.0f : T.surf[j].dz, r, dummy, clipped)) return kRevNoRoot << kRevReasonShift;
+        if (!rev_interface<false, false>(T.surf[j], M, j, jj == T.stop ? 0.0f : T.surf[j].dz, r, dummy, clipped)) return kRevNoRoot << kRevReasonShift;
     }
     // clipped in front of the stop? (the front group once more along the final ray, no tangent)
     {
         RevRay f{0.0f, 0.0f, s, rev_sqrt(fmaf(-s, s, 1.0f))};
+        M.at_stop();
         for (int jj = T.stop - 1; jj >= 0; --jj) {
             const int j = rev_uniform(jj);
-            if (!rev_interface<false, true>(T.surf[j], -T.surf[j + 1].dz, f, dummy, clipped)) return kRevNoRoot << kRevReasonShift;
+            if (!rev_interface<false, true>(T.surf[j], M, j, -T.surf[j + 1].dz, f, dummy, clipped)) return kRevNoRoot << kRevReasonShift;
         }
     }
     const float t = (T.sensorZ - r.z) * rev_rcp(r.uz);

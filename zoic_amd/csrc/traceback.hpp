@@ -62,7 +62,8 @@ namespace zoic {
 
 constexpr uint32_t kTbTraced = 1u, kTbPastLut = 4u;
 constexpr uint32_t kTbReasonShift = 8u, kTbInterfaceShift = 16u;
-enum : uint32_t { kTbAway = 1u, kTbMiss = 2u, kTbClipped = 3u, kTbTir = 4u, kTbNonFinite = 5u, kTbModel = 6u, kTbOutsideDomain = 7u };
+enum : uint32_t { kTbAway = 1u, kTbMiss = 2u, kTbClipped = 3u, kTbTir = 4u, kTbNonFinite = 5u, kTbModel = 6u, kTbOutsideDomain = 7u,
+                  kTbWavelength = 8u };   // (kTbWavelength: the spectral calls only, backward_spectral.hpp)
 constexpr float kTbMaxFloat = 3.4028235e38f;
 // the start point may lie behind the front element's cap by this share of the front housing radius: a forward record's origin lies ON
 // that surface, to the rounding of the forward trace
@@ -120,8 +121,16 @@ ZOIC_HD uint32_t tb_end(uint32_t reason, int interface) { return (reason << kTbR
 
 ZOIC_HD bool tb_finite(float a, float b, float c) { return fabsf(a) <= kTbMaxFloat && fabsf(b) <= kTbMaxFloat && fabsf(c) <= kTbMaxFloat; }
 
+// Where an interface's eta comes from: the d-line table (TbDLine), or the indices of its two media at the ray's own wavelength
+// (TbSpectral, backward_spectral.hpp).  eta(j, S) is called once per interface, front to rear.
+struct TbDLine {
+    ZOIC_HD float eta(int, const TbSurface &S) { return S.eta; }
+};
+
 // the trace-back of one ray: returns the flag word, writes sx, sy
-ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy)
+template <class Medium = TbDLine>
+ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy,
+                                Medium M = Medium())
 {
     sx = 0.0f; sy = 0.0f;
     if (T.model != 0 && T.model != 1) return kTbModel << kTbReasonShift;
@@ -196,7 +205,7 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
         // the unit normal on the sphere, (c x, c y, 1 + c z): it points towards +z, against the ray
         const float nx = c * hx, ny = c * hy, nz = fmaf(c, hz, 1.0f);
         const float cosi = -fmaf(ux, nx, fmaf(uy, ny, uz * nz));
-        const float eta = S.eta, eta2 = eta * eta;
+        const float eta = M.eta(j, S), eta2 = eta * eta;
         const float k2 = fmaf(eta2, cosi * cosi, 1.0f - eta2);
         if (!(k2 >= 0.0f)) return tb_end(kTbTir, iface);
         const float g = fmaf(eta, cosi, -tb_sqrt(k2));
