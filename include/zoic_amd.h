@@ -16,7 +16,7 @@
  * thread with no sample in flight, and camera_create_ray concurrently from every render thread, zoic.cpp:1752):
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
- *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
+ *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
  *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
@@ -55,7 +55,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_project_points_device, zoic_project_point and
  *      zoic_camera_set_reverse_projection (reverse projection; zoic_camera_reverse_ray answers only when opted in).
  *      Added later without a new number (additive): zoic_trace_back_rays_device and zoic_trace_back_ray (trace-back: camera rays
- *      to the screen samples they land on). */
+ *      to the screen samples they land on).
+ *      Added later without a new number (additive): zoic_ray_differentials_spectral_device (traced ray differentials of spectral
+ *      records, with the derivative with respect to the wavelength). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -248,7 +250,8 @@ zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_cam
  * The result is the derivative of the path the record took (not a finite difference; the unit-square sample is not held fixed).
  * The arithmetic is the same in every precision mode: STRICT and FAST cameras give bitwise-equal differentials on rays whose
  * tries agree.  Not covered (their derivative fields stay the reference's): zoic_camera_create_ray and the tiles (resident
- * kernel), zoic_create_rays_host, zoic_frame_*; chromatic aberration. */
+ * kernel), zoic_create_rays_host, zoic_frame_*.  The records of zoic_create_rays_spectral_device have a call of their own:
+ * zoic_ray_differentials_spectral_device, below. */
 typedef struct zoic_ray_differential { zoic_vec3 dOdx, dOdy, dDdx, dDdy; } zoic_ray_differential;   /* 48 bytes */
 /* The differentials of rays zoic_create_rays_device made: pass what that call was given (d_samples, d_rng_states,
  * ray_index_base) and what it wrote (d_rays).  The camera must not be updated between the two calls.  dsx = dsy = 1 returns the
@@ -274,11 +277,34 @@ zoic_status zoic_create_rays_arnold_differentials(zoic_camera *cam, uint64_t n, 
  * RAYTRACED: the model above (STRICT: the reference's arithmetic on the per-ray indices; at lambda = 587.5618 the records are
  * zoic_create_rays_device's bit for bit; FAST modes: decision-safe as there).  THINLENS and NONE ignore the wavelength: their records
  * (or NONE's error) are zoic_create_rays_device's.  A wavelength outside [360, 830] or NaN rejects that ray only: origin = dir = +0.0,
- * weight 0, flags == 0x80 (bit 7), and no counter counts it.  zoic_ray_differentials_device is NOT valid for these records: it
- * replays the d-line trace.  ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer;
+ * weight 0, flags == 0x80 (bit 7), and no counter counts it.  The differentials of these records come from
+ * zoic_ray_differentials_spectral_device (zoic_ray_differentials_device replays the d-line trace).  ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer;
  * n = 0 returns ZOIC_OK. */
 zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
                                              const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream);
+/* ---- traced ray differentials of spectral records (opt-in; csrc/differentials_spectral.hpp has the full definition) ----------
+ * The differentials above for the path a spectral record took: the accepted try is replayed and traced with every interface's
+ * eta = n_i(lambda) / n_i+1(lambda) at the ray's own wavelength (one correctly rounded division, in every precision mode: STRICT and
+ * FAST cameras give bitwise-equal results on rays whose tries agree).  At lambda = 587.5618, and on a lens without V-numbers at any
+ * valid wavelength, d_out is zoic_ray_differentials_device's bit for bit.
+ * d_chromatic (optional) receives the derivative of the same path with respect to the wavelength, PER NANOMETRE, with the sensor
+ * point and the lens point L held fixed: dO/dlambda and dD/dlambda, after the final flip like the other tangents.  Its only source is
+ * the indices' slope, dn_i/dlambda = -2 B_i / lambda^3; dsx / dsy never scale it.  It is traced in f64 (an achromat's crown and flint
+ * contributions cancel in it) and returned as f32.  A hero-wavelength renderer shifts its companion
+ * wavelengths' rays with it, a footprint estimate widens by it for colour fringes.
+ * THINLENS ignores the wavelength (d_out as zoic_ray_differentials_device, +0.0 in d_chromatic); NONE gives zeros.  A record of
+ * weight 0 (among them the rejected ones, flags 0x80) gets +0.0 everywhere, and so does every row whose wavelength HERE is outside
+ * [360, 830] or NaN, whatever its record says.  The dispersion table is read at the call: a zoic_camera_set_abbe_numbers override
+ * holds from the next call on (use the one the records were made with). */
+/* zoic_ray_differentials_device for the records of zoic_create_rays_spectral_device: pass what that call was given
+ * (d_samples, d_wavelengths, d_rng_states, ray_index_base) and what it wrote (d_rays).
+ * d_chromatic: NULL, or n x 2 zoic_vec3 (dO/dlambda, dD/dlambda per nm; device memory, 8-byte aligned).
+ * Stream semantics, threading contract and the other pointers' alignment as zoic_ray_differentials_device; d_wavelengths 4-byte
+ * aligned.  ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for a NULL or misaligned pointer (d_wavelengths may not
+ * be NULL); n = 0 returns ZOIC_OK. */
+zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples,
+        const float *d_wavelengths, const uint32_t *d_rng_states, uint64_t ray_index_base, const zoic_ray *d_rays,
+        float dsx, float dsy, zoic_ray_differential *d_out, zoic_vec3 *d_chromatic, void *stream);
 /* The dispersion table of the camera's lens (works on a ZOIC_DEVICE_NONE camera): returns the surface count and writes up to
  * `capacity` entries, trace order (rear first), of n_d (after the 0 -> 1.0 fix, zoic.cpp:937-940), V (the override if one is set)
  * and B (nm^2) into the arrays that are not NULL; -1 for a NULL camera or a negative capacity. */

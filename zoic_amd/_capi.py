@@ -103,6 +103,7 @@ SYMBOLS = {
     "zoic_create_rays_arnold_differentials": (C.c_int, [_vp, _u64, C.POINTER(CameraInput), C.POINTER(CameraOutput), _u64]),
     "zoic_ray_differentials_device": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.c_float, C.c_float, _vp, _vp]),
     "zoic_create_rays_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "zoic_ray_differentials_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "zoic_camera_get_dispersion": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "zoic_camera_set_abbe_numbers": (C.c_int, [_vp, C.c_int, _vp]),
     "zoic_camera_create_ray": (C.c_int, [_vp, C.POINTER(CameraInput), C.POINTER(CameraOutput), C.c_uint16]),

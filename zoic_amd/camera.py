@@ -563,14 +563,22 @@ class ZoicCamera:
                        int(ray_index_base)))
         return outs
 
-    def ray_differentials(self, samples, rays, dsx=1.0, dsy=1.0, rng_states=None, ray_index_base=0, out=None, stream=None):
+    def ray_differentials(self, samples, rays, dsx=1.0, dsy=1.0, rng_states=None, ray_index_base=0, out=None, stream=None,
+                          wavelengths=None, chromatic=False):
         """Traced ray differentials (zoic_ray_differentials_device) of rays create_rays made from device tensors.
 
         samples, rng_states, ray_index_base: what that create_rays call was given; rays: the (n,8) float32 record tensor it returned
         (or its result dict).  The camera must not have been updated in between.  Returns an (n,12) float32 device tensor, columns
         dOdx, dOdy, dDdx, dDdy (x y z each), scaled by dsx / dsy (1: the raw Jacobian columns); asynchronous on `stream` (default:
-        torch's current stream).  Rays of weight 0 get zeros."""
+        torch's current stream).  Rays of weight 0 get zeros.
+        wavelengths: None (the d-line call above, untouched) or the (n,) float32 device tensor create_rays(..., wavelengths=) was
+        given: the differentials of those spectral records (zoic_ray_differentials_spectral_device); rows whose wavelength is
+        outside [360, 830] or NaN get zeros.  chromatic=True (needs wavelengths) returns (diffs, chroma): chroma is an (n,6) float32
+        tensor, dO/dlambda and dD/dlambda per nanometre with the sensor point and the lens point held fixed (never scaled by dsx /
+        dsy; csrc/differentials_spectral.hpp)."""
         import torch
+        if chromatic and wavelengths is None:
+            raise ValueError("chromatic=True needs wavelengths")
         if isinstance(rays, dict):
             rays = rays["rays"]
         if not _is_torch(samples) or not _is_torch(rays):
@@ -592,6 +600,13 @@ class ZoicCamera:
         if tuple(out.shape) != (n, 12) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != samples.device:
             raise ValueError("out must be a contiguous (n,12) float32 tensor on the samples' device")
         st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        if wavelengths is not None:
+            w = self._wavelength_tensor(wavelengths, n, samples)
+            chroma = torch.empty((n, 6), dtype=torch.float32, device=samples.device) if chromatic else None
+            self._check(self._lib.zoic_ray_differentials_spectral_device(
+                self._h, n, samples.data_ptr(), w.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(), float(dsx), float(dsy),
+                out.data_ptr(), chroma.data_ptr() if chromatic else None, C.c_void_p(st)))
+            return (out, chroma) if chromatic else out
         self._check(self._lib.zoic_ray_differentials_device(self._h, n, samples.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(),
                                                             float(dsx), float(dsy), out.data_ptr(), C.c_void_p(st)))
         return out

@@ -32,6 +32,7 @@
 
 #include "../../include/zoic_amd.h"
 #include "differentials.hpp"
+#include "differentials_spectral.hpp"
 #include "kernels.hpp"
 #include "mailbox.hpp"
 #include "spectral.hpp"
@@ -1362,6 +1363,37 @@ zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const
     fill_spectral(cam, W);
     const int rc = launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, rays,
                                         cam->dCounters, cam->kernel_mode(), st);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
+                                                   const uint32_t *d_rng_states, uint64_t ray_index_base, const zoic_ray *d_rays, float dsx,
+                                                   float dsy, zoic_ray_differential *d_out, zoic_vec3 *d_chromatic, void *stream)
+{
+    static_assert(sizeof(zoic_vec3) == 12, "zoic_vec3 layout");
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_samples || (reinterpret_cast<uintptr_t>(d_samples) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be non-NULL and 16-byte aligned");
+    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
+    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_out must be non-NULL and 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_chromatic) & 7u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_chromatic must be 8-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int model = cam->params.p.lensModel;
+    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no derivative
+        ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
+        if (d_chromatic) ZOIC_HIP(hipMemsetAsync(d_chromatic, 0, n * 2u * sizeof(zoic_vec3), st));
+        return ZOIC_OK;
+    }
+    SpectralTable W;
+    fill_spectral(cam, W);
+    const int rc = launch_ray_differentials_spectral(model, cam->kolb, W, cam->thin, cam->bokehDev, d_samples, d_wavelengths, d_rng_states,
+                                                     ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy,
+                                                     reinterpret_cast<float *>(d_out), reinterpret_cast<float *>(d_chromatic), st);
     if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
     return ZOIC_OK;
 }

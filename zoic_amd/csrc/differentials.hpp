@@ -27,7 +27,8 @@
 // tries agree.  Transfer and refraction terms: Igehy 1999, "Tracing Ray Differentials", applied to the reference's own formulas.
 //
 // Out of scope (the reference's derivative fields are kept there): tiles and the per-sample zoic_camera_create_ray (the resident
-// kernel, mailbox.hip), zoic_create_rays_host, zoic_frame_* / ShardedFrame and the Arnold node shim; chromatic aberration.
+// kernel, mailbox.hip), zoic_create_rays_host, zoic_frame_* / ShardedFrame and the Arnold node shim.  The records of
+// zoic_create_rays_spectral_device: differentials_spectral.hpp.
 //
 // Host- and device-callable (ZOIC_HD): a host driver checks the tangents against finite differences
 // (tests/test_differentials_cpu.py).
