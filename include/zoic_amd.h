@@ -16,7 +16,7 @@
  * thread with no sample in flight, and camera_create_ray concurrently from every render thread, zoic.cpp:1752):
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
- *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
+ *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_create_rays_hero_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
  *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
@@ -57,7 +57,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_trace_back_rays_device and zoic_trace_back_ray (trace-back: camera rays
  *      to the screen samples they land on).
  *      Added later without a new number (additive): zoic_ray_differentials_spectral_device (traced ray differentials of spectral
- *      records, with the derivative with respect to the wavelength). */
+ *      records, with the derivative with respect to the wavelength).
+ *      Added later without a new number (additive): zoic_create_rays_hero_device (k wavelengths through one lens point per sample),
+ *      ZOIC_HERO_MAX_WAVELENGTHS; flag bit 8 of zoic_ray (ZOIC_RAY_COMPANION_LOST). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -141,7 +143,8 @@ typedef struct zoic_camera_output {
 /* Batch output: one 32-byte record per ray (the fields of AtCameraOutput that zoic writes, zoic.cpp:1752-1990).
  * flags: bit0 = retried (tries > 0  => the caller sets dOdy=origin, dDdy=dir, zoic.cpp:1974-1977),
  *        bits1-5 = tries (0..26; 26 => weight 0, zoic.cpp:1951-1953), bit6 = outside the exit-pupil LUT (fenced UB),
- *        bit7 = wavelength rejected (zoic_create_rays_spectral_device: the record is all zero but for flags == 0x80). */
+ *        bit7 = wavelength rejected (zoic_create_rays_spectral_device: the record is all zero but for flags == 0x80),
+ *        bit8 = companion lost (zoic_create_rays_hero_device only: ZOIC_RAY_COMPANION_LOST). */
 typedef struct zoic_ray {
     float ox, oy, oz;   /* output.origin */
     float dx, dy, dz;   /* output.dir    */
@@ -282,6 +285,46 @@ zoic_status zoic_create_rays_arnold_differentials(zoic_camera *cam, uint64_t n, 
  * n = 0 returns ZOIC_OK. */
 zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
                                              const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream);
+/* ---- hero-wavelength rays: k wavelengths through ONE lens point per sample (opt-in; csrc/hero.hpp has the full definition) ------
+ * A spectral renderer carries a hero wavelength and a few companions per camera sample.  k spectral calls on the same samples run k
+ * retry loops, and where a try passes at one wavelength and is clipped or totally reflected at another the colours of one sample
+ * leave through different lens points.  This call runs the retry loop once, at the hero's wavelength, and sends the companions
+ * through the hero's lens point.
+ *   d_wavelengths : n x k f32 (nm) in device memory, 4-byte aligned, sample-major, the hero first: d_wavelengths[i*k + j]
+ *   d_rays        : n x k zoic_ray records in device memory, 16-byte aligned, sample-major: record (i, j) at d_rays[i*k + j]
+ *   every other argument as zoic_create_rays_spectral_device's; 1 <= k <= ZOIC_HERO_MAX_WAVELENGTHS.
+ * Column 0 (the hero) is the record zoic_create_rays_spectral_device writes for sample i at d_wavelengths[i*k], bit for bit: ray i
+ * draws its retries from the stream keyed by ray_index_base + i (i, not i*k) or from d_rng_states[i], and the camera's counters move
+ * exactly as that call moves them.  With k = 1 the call IS that call.
+ * Columns j >= 1 (the companions) of a hero with weight != 0: the hero's accepted try fixes the start -- the sensor point and the lens
+ * point after the exit-pupil transform, the (o, d) the hero's trace began with -- and that start is traced ONCE through every
+ * interface at d_wavelengths[i*k + j], with the trace the hero's tries use in the camera's precision mode (STRICT: the reference's
+ * arithmetic on the per-ray indices; FAST modes: decision-safe, a trace that meets a clip inside a guard band is taken again in
+ * STRICT arithmetic from the same start; a fastRunsStrict camera runs STRICT).  A companion that comes through gets origin and dir after
+ * the final flip, the hero's weight and the hero's flags (tries, retried bit, LUT bit; bit 8 clear).  One that misses an interface, is
+ * clipped at a housing or the stop, or is totally reflected gets origin = dir = +0.0, weight 0 and flags = the hero's flags |
+ * ZOIC_RAY_COMPANION_LOST; no retry is drawn for it.  A companion at the hero's own wavelength is the hero's record bit for bit.
+ * Companions of a hero with weight 0 (out of tries, a dead pixel) get +0.0 everywhere and flags = the hero's flags | bit 8.  So do
+ * those of a hero whose weight comes from the reference's NaN ray (a draw on the disk's centre on a ray no retry can save, 2e-15 per
+ * draw: its record is NaN and there is no start to share).
+ * Companions touch no counter (their total reflections are not counted) and advance no retry stream.
+ * A companion wavelength outside [360, 830] or NaN rejects that column only (all zero, flags == 0x80); an invalid hero wavelength
+ * rejects the whole row (all k records zero with flags == 0x80) and nothing is counted for it.
+ * THINLENS ignores the wavelengths: every valid column holds the record zoic_create_rays_device writes for sample i (bit 8 clear),
+ * invalid columns and rows are rejected as above, and the counters are those of one spectral call on column 0.  NONE: that call's error.
+ * Asynchronous on `stream`, with the threading contract of zoic_create_rays_device.  One exception, THINLENS with k > 1 only: the
+ * thin-lens records are staged in ONE buffer per camera (n x 32 bytes, kept until zoic_camera_destroy), so such calls of one camera
+ * run one after the other on the device whatever their streams, and a call with a larger n than any before waits on the host for the
+ * previous one before it grows the buffer.  Results do not depend on it.  RAYTRACED calls use no scratch and never wait for each other.  ZOIC_ERR_INVALID_ARGUMENT for k = 0 or
+ * k > ZOIC_HERO_MAX_WAVELENGTHS (checked first, on every camera) and for a NULL or misaligned pointer (d_rng_states may be NULL);
+ * ZOIC_ERR_NO_DEVICE on a tables-only camera; ZOIC_ERR_NOT_UPDATED before an update; n = 0 returns ZOIC_OK.
+ * Not covered: the tiles, the Arnold-layout calls, zoic_create_rays_host, zoic_frame_*.  The differentials of a companion record come
+ * from zoic_ray_differentials_spectral_device called with per-row d_rng_states and that column's wavelengths. */
+#define ZOIC_HERO_MAX_WAVELENGTHS 8
+#define ZOIC_RAY_COMPANION_LOST 0x100u   /* zoic_ray flags bit 8 */
+zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples,
+                                         const float *d_wavelengths, const uint32_t *d_rng_states, uint64_t ray_index_base,
+                                         zoic_ray *d_rays, void *stream);
 /* ---- traced ray differentials of spectral records (opt-in; csrc/differentials_spectral.hpp has the full definition) ----------
  * The differentials above for the path a spectral record took: the accepted try is replayed and traced with every interface's
  * eta = n_i(lambda) / n_i+1(lambda) at the ray's own wavelength (one correctly rounded division, in every precision mode: STRICT and

@@ -20,6 +20,9 @@ TILE_MAX_SAMPLES = 65536
 # reasons the spectral backward calls add (bits 8-11 of their flag words): the item's wavelength is outside [360, 830] nm or NaN
 TRACE_BACK_WAVELENGTH = 8
 PROJECT_WAVELENGTH = 6
+# zoic_create_rays_hero_device: the most wavelengths per sample, and the flag bit (8) of a companion that did not come through
+HERO_MAX_WAVELENGTHS = 8
+RAY_COMPANION_LOST = 0x100
 
 STATUS_NAMES = ["ZOIC_OK", "ZOIC_ERR_INVALID_ARGUMENT", "ZOIC_ERR_LENS_PATH", "ZOIC_ERR_LENS_COLUMNS",
                 "ZOIC_ERR_LENS_PARSE", "ZOIC_ERR_MULTI_APERTURE", "ZOIC_ERR_NO_APERTURE", "ZOIC_ERR_TOO_MANY_LENSES",
@@ -103,6 +106,7 @@ SYMBOLS = {
     "zoic_create_rays_arnold_differentials": (C.c_int, [_vp, _u64, C.POINTER(CameraInput), C.POINTER(CameraOutput), _u64]),
     "zoic_ray_differentials_device": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.c_float, C.c_float, _vp, _vp]),
     "zoic_create_rays_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "zoic_create_rays_hero_device": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp]),
     "zoic_ray_differentials_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "zoic_camera_get_dispersion": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "zoic_camera_set_abbe_numbers": (C.c_int, [_vp, C.c_int, _vp]),

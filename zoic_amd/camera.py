@@ -31,6 +31,8 @@ _INT = ("useImage", "lensModel", "kolbSamplingLUT", "useDof")
 
 FLAG_RETRIED = 1
 FLAG_LUT_MISS = 64
+HERO_MAX_WAVELENGTHS = _capi.HERO_MAX_WAVELENGTHS   # zoic_create_rays_hero_device: wavelengths per sample
+RAY_COMPANION_LOST = _capi.RAY_COMPANION_LOST       # flag bit 8 of a companion record: lost at the hero's lens point
 
 
 def lens_path(name):
@@ -57,6 +59,15 @@ def rays_to_dict(rays):
     """(n,) zoic_ray records -> convenience views (planes are copies: ox oy oz dx dy dz weight)."""
     planes = np.stack([rays[k] for k in ("ox", "oy", "oz", "dx", "dy", "dz", "weight")]).astype(np.float32, copy=False)
     flags = rays["flags"].astype(np.uint8)
+    return dict(rays=rays, planes=planes, origin=planes[0:3], dir=planes[3:6], weight=planes[6], flags=flags,
+                tries=((flags >> 1) & 31).astype(np.int32))
+
+
+def hero_rays_to_dict(rays):
+    """(n, k) zoic_ray records of create_rays_hero -> the views of rays_to_dict with the (n, k) axes last; flags keep all their bits
+    (uint32: bit 8 is RAY_COMPANION_LOST)."""
+    planes = np.stack([rays[k] for k in ("ox", "oy", "oz", "dx", "dy", "dz", "weight")]).astype(np.float32, copy=False)
+    flags = rays["flags"].astype(np.uint32)
     return dict(rays=rays, planes=planes, origin=planes[0:3], dir=planes[3:6], weight=planes[6], flags=flags,
                 tries=((flags >> 1) & 31).astype(np.int32))
 
@@ -342,6 +353,67 @@ class ZoicCamera:
                                                                int(ray_index_base), rays.data_ptr(), C.c_void_p(st)))
         out.update(origin=rays[:, 0:3].t(), dir=rays[:, 3:6].t(), weight=rays[:, 6], planes=rays[:, 0:7].t(),
                    flags=rays[:, 7].view(torch.int32))
+        return out
+
+    def create_rays_hero(self, samples, wavelengths, rng_states=None, ray_index_base=0, out=None, stream=None):
+        """Hero-wavelength rays (zoic_create_rays_hero_device): k wavelengths through one lens point per sample.
+
+        samples: (n, 4) float32; wavelengths: (n, k) float32 in nm, the hero in column 0, 1 <= k <= HERO_MAX_WAVELENGTHS.  Column 0 of
+        the result is create_rays(samples, wavelengths=wavelengths[:, 0]); column j >= 1 is the hero's accepted start traced at
+        wavelengths[:, j], or a lost record (zeros, weight 0, the hero's flags | RAY_COMPANION_LOST).
+        torch device tensors in -> asynchronous on `stream` (default: torch's current stream); returns a dict with rays = (n, k, 8)
+                     float32 tensor (word 7 holds the flag word's bits) and strided views: origin, dir (3, n, k), planes (7, n, k),
+                     weight (n, k), flags (n, k) int32.
+        numpy in  -> samples, wavelengths and rng_states are copied to the camera's device through torch, the call waits and returns
+                     numpy arrays of those shapes with a structured (n, k) rays (out must be None there).
+        """
+        import torch
+        if not _is_torch(samples):
+            if _is_torch(wavelengths) or (rng_states is not None and _is_torch(rng_states)):
+                raise TypeError("numpy samples need numpy wavelengths and rng_states")
+            if out is not None:
+                raise ValueError("out is for torch samples")
+            s = np.ascontiguousarray(samples, dtype=np.float32)
+            if s.ndim != 2 or s.shape[1] != 4:
+                raise ValueError("samples must be (n, 4)")
+            w = np.ascontiguousarray(wavelengths, dtype=np.float32)
+            if w.ndim != 2 or w.shape[0] != s.shape[0]:
+                raise ValueError("wavelengths must be (n, k)")
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                self._check(self._lib.zoic_create_rays_hero_device(self._h, s.shape[0], w.shape[1], None, None, None, int(ray_index_base), None, None))
+            dev = torch.device("cuda", self.device)
+            tr = None if rng_states is None else torch.from_numpy(np.ascontiguousarray(rng_states, dtype=np.uint32).view(np.int32)).to(dev)
+            res = self.create_rays_hero(torch.from_numpy(s).to(dev), torch.from_numpy(w).to(dev), tr, ray_index_base, None, None)
+            torch.cuda.synchronize(dev)
+            rays = np.ascontiguousarray(res["rays"].cpu().numpy()).view(_capi.RAY_DTYPE).reshape(w.shape)
+            return hero_rays_to_dict(rays)
+        if not _is_torch(wavelengths):
+            raise TypeError("torch samples need a torch wavelength tensor")
+        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
+            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
+        if samples.device.index != self.device:
+            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
+        n = samples.shape[0]
+        if (wavelengths.dtype != torch.float32 or wavelengths.dim() != 2 or wavelengths.shape[0] != n or not wavelengths.is_contiguous()
+                or wavelengths.device != samples.device):
+            raise ValueError("wavelengths must be a contiguous (n,k) float32 tensor on the samples' device")
+        k = wavelengths.shape[1]
+        if out is None:
+            out = dict(rays=torch.empty((n, k, 8), dtype=torch.float32, device=samples.device))
+        rays = out["rays"]
+        if tuple(rays.shape) != (n, k, 8) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
+            raise ValueError("out['rays'] must be a contiguous (n,k,8) float32 tensor on the samples' device")
+        rs_ptr = None
+        if rng_states is not None:
+            if (not _is_torch(rng_states) or rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4)
+                    or not rng_states.is_contiguous() or rng_states.device != samples.device):
+                raise ValueError("rng_states must be a contiguous (n,4) int32/uint32 tensor on the samples' device")
+            rs_ptr = rng_states.data_ptr()
+        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        self._check(self._lib.zoic_create_rays_hero_device(self._h, n, k, samples.data_ptr(), wavelengths.data_ptr(), rs_ptr,
+                                                           int(ray_index_base), rays.data_ptr(), C.c_void_p(st)))
+        out.update(origin=rays[:, :, 0:3].permute(2, 0, 1), dir=rays[:, :, 3:6].permute(2, 0, 1), weight=rays[:, :, 6],
+                   planes=rays[:, :, 0:7].permute(2, 0, 1), flags=rays[:, :, 7].view(torch.int32))
         return out
 
     def dispersion(self):

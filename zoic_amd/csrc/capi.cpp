@@ -36,6 +36,7 @@
 #include "kernels.hpp"
 #include "mailbox.hpp"
 #include "spectral.hpp"
+#include "hero.hpp"
 #include "reverse.hpp"
 #include "backward_spectral.hpp"
 #include "traceback.hpp"
@@ -111,6 +112,15 @@ struct LaunchSlot {
     bool recorded = false;
     hipStream_t lastStream = nullptr;   // a launch on the same stream is ordered behind the previous one: no event wait needed
     DeviceBuffer<uint32_t> redo;        // the Kolb launch's scratch (kolb_scratch_dwords): work list of decision-safe FAST
+};
+
+// zoic_create_rays_hero_device on a THINLENS camera: the thin-lens kernel's n records, before hero.hip spreads them over the
+// columns.  One buffer per camera: a call holds `m` while it enqueues, and its stream waits for the previous user's `done`.
+struct HeroStage {
+    std::mutex m;
+    DeviceBuffer<RayRecord> rays;
+    hipEvent_t done = nullptr;          // created at first use
+    bool recorded = false;
 };
 
 // Private scratch of ONE host-buffer call in flight: leased from the camera's pool for the duration of the call.
@@ -279,6 +289,7 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     unsigned int *dWorkCursor = nullptr;    // kLaunchSlots sets of partition cursors
     LaunchSlot slots[kLaunchSlots];
     std::atomic<unsigned> nextSlot{0};
+    HeroStage heroStage;
     std::mutex poolM;
     std::vector<CallContext *> freeContexts;
     std::vector<std::unique_ptr<CallContext>> contexts;
@@ -941,6 +952,8 @@ void zoic_camera_destroy(zoic_camera *cam)
             if (cam->slots[i].done) (void)hipEventDestroy(cam->slots[i].done);
             cam->slots[i].redo.release();
         }
+        if (cam->heroStage.done) (void)hipEventDestroy(cam->heroStage.done);
+        cam->heroStage.rays.release();
         cam->dCdfRow.release(); cam->dCdfColumn.release(); cam->dRowIdx.release(); cam->dColIdx.release(); cam->dPyramid.release(); cam->dBokehCells.release();
         cam->dProbeU.release(); cam->dProbeV.release(); cam->dProbeOk.release(); cam->dFastProbe.release(); cam->dFastProbeRays.release();
         if (cam->dProbeTir) (void)hipFree(cam->dProbeTir);
@@ -1363,6 +1376,55 @@ zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const
     fill_spectral(cam, W);
     const int rc = launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, rays,
                                         cam->dCounters, cam->kernel_mode(), st);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples, const float *d_wavelengths,
+                                         const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream)
+{
+    static_assert(ZOIC_HERO_MAX_WAVELENGTHS == kHeroMaxWavelengths && ZOIC_RAY_COMPANION_LOST == kHeroCompanionLost, "hero constants");
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (k == 0 || k > ZOIC_HERO_MAX_WAVELENGTHS) return fail(ZOIC_ERR_INVALID_ARGUMENT, "k must be 1 ... ZOIC_HERO_MAX_WAVELENGTHS");
+    // one wavelength per sample: the spectral call itself (its argument checks, its kernel, its counters)
+    if (k == 1) return zoic_create_rays_spectral_device(cam, n, d_samples, d_wavelengths, d_rng_states, ray_index_base, d_rays, stream);
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
+    if (reinterpret_cast<uintptr_t>(d_samples) & 15u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be 16-byte aligned");
+    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
+    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    RayRecord *rays = reinterpret_cast<RayRecord *>(d_rays);
+    if (cam->params.p.lensModel != ZOIC_RAYTRACED) {
+        // THINLENS (and NONE's error): the n records of zoic_create_rays_device into the camera's staging buffer, then spread over the
+        // columns with the invalid wavelengths rejected
+        HeroStage &H = cam->heroStage;
+        std::lock_guard<std::mutex> lk(H.m);
+        if (!H.done) ZOIC_HIP(hipEventCreateWithFlags(&H.done, hipEventDisableTiming));
+        if (H.rays.cap < n) {   // growing the buffer frees the old one: its previous user must be over
+            if (H.recorded) ZOIC_HIP(hipEventSynchronize(H.done));
+            ZOIC_HIP(H.rays.reserve(n));
+        }
+        if (H.recorded) ZOIC_HIP(hipStreamWaitEvent(st, H.done, 0));
+        zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, H.rays.ptr, st);
+        int rc = 0;
+        if (s == ZOIC_OK) rc = launch_hero_replicate(H.rays.ptr, d_wavelengths, n, k, rays, cam->dCounters, cam->thin.useDof != 0, st);
+        // whatever was queued reads or writes the buffer: its next user waits behind it
+        const hipError_t re = hipEventRecord(H.done, st);
+        if (re == hipSuccess) H.recorded = true;
+        if (s != ZOIC_OK) return s;
+        if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        ZOIC_HIP(re);
+        return ZOIC_OK;
+    }
+    SpectralTable W;
+    fill_spectral(cam, W);
+    const int rc = launch_kolb_hero(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, k, rays,
+                                    cam->dCounters, cam->kernel_mode(), st);
     if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
     return ZOIC_OK;
 }
