@@ -17,7 +17,7 @@
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
  *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_create_rays_hero_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
- *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
+ *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian (and their _spectral forms), zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
  *   - No entry point changes the calling thread's current HIP device.
@@ -59,7 +59,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_ray_differentials_spectral_device (traced ray differentials of spectral
  *      records, with the derivative with respect to the wavelength).
  *      Added later without a new number (additive): zoic_create_rays_hero_device (k wavelengths through one lens point per sample),
- *      ZOIC_HERO_MAX_WAVELENGTHS; flag bit 8 of zoic_ray (ZOIC_RAY_COMPANION_LOST). */
+ *      ZOIC_HERO_MAX_WAVELENGTHS; flag bit 8 of zoic_ray (ZOIC_RAY_COMPANION_LOST).
+ *      Added later without a new number (additive): zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian and their
+ *      _spectral forms (the trace-back with its Jacobian dPs / d(origin, dir)). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -550,6 +552,41 @@ zoic_status zoic_project_points_spectral_device(zoic_camera *cam, uint64_t n, co
                                                 uint32_t *d_flags /* may be NULL */, void *stream);
 zoic_status zoic_project_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, float *Ps /* [2] */,
                                         uint32_t *flags /* may be NULL */);
+
+/* ---- the trace-back Jacobian: dPs / d(origin, dir) (opt-in; csrc/traceback_jacobian.hpp has the full definition) ---------------
+ * The trace-back calls above answer WHERE a ray lands.  These four answer how that place moves with the ray, which is what lets a
+ * trace-back carry energy: a light tracer or a splatter divides by |det dPs/d(omega)| at a fixed origin, a bidirectional connection to
+ * a point on the front element needs dPs/d(origin).  For a ray that is traced back (bit 0 of its flags)
+ *       J = d(sx, sy) / d(origin.x, origin.y, origin.z, dir.x, dir.y, dir.z)
+ * 2 x 6, row-major: the six derivatives of sx, then the six of sy.  dir is differentiated as given, at any length.
+ *   Map        J is the derivative of the exact map of the trace-back: the move along the line to the front vertex plane, the
+ *              normalisation, at every interface the hit, the normal and Snell, then the sensor plane; tangents after Igehy's transfer
+ *              and refraction, carried along the one trace (four of them: the rays are a 4-dimensional manifold).
+ *   Identities J_o . dir = 0 and J_d . dir = 0 (J_o, J_d: the first and the last three columns): moving the origin along the line
+ *              changes nothing, scaling dir changes nothing.  The cap test, the LUT flag and the clip decisions have no derivative.
+ *   THINLENS   (with useDof) the closed form: with tau = -(origin.z + focalDistance) / dir.z and I = 1 / (focalDistance tan_fov),
+ *              d sx/d origin.x = I, d sx/d origin.z = -(dir.x / dir.z) I, d sx/d dir.x = tau I, d sx/d dir.z = -tau (dir.x / dir.z) I.
+ *   Spectral   the wavelength is held fixed (no tangent); an invalid one gives ZOIC_TRACE_BACK_WAVELENGTH.  At 587.5618f the spectral
+ *              calls give the d-line calls' bits.
+ * Ps and flags are those of zoic_trace_back_ray / zoic_trace_back_ray_spectral bit for bit, for every input.  A ray that is not traced
+ * back gets Ps = (+0, +0) and twelve +0.0.  J is not clipped: an entry of a ray of extreme scale may be infinite, and one that is not a
+ * number is written as the quiet NaN 0x7fc00000.
+ * The arithmetic is the trace-back's (f32, correctly rounded square roots, reciprocals and divisions), the same on the host and on the
+ * device in every precision mode: the device calls and the host calls give the same bits for the same ray, J included.
+ * d_jacobian: n x 12 floats, device memory, 16-byte aligned.  Every other argument, the error codes (ZOIC_ERR_NOT_UPDATED before an
+ * update; ZOIC_ERR_INVALID_ARGUMENT for a NULL, misaligned or non-device pointer, before any launch; ZOIC_ERR_NO_DEVICE on a tables-only
+ * camera; n = 0 returns ZOIC_OK), the stream semantics and the threading contract are those of zoic_trace_back_rays_device /
+ * zoic_trace_back_rays_spectral_device; no counter and no retry stream is touched. */
+zoic_status zoic_trace_back_jacobian_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_screen /* n x 2 */,
+                                            uint32_t *d_flags /* may be NULL */, float *d_jacobian /* n x 12 */, void *stream);
+/* The host build of the same code for one ray (works on a ZOIC_DEVICE_NONE camera).  flags may be NULL. */
+zoic_status zoic_trace_back_ray_jacobian(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps /* [2] */,
+                                         uint32_t *flags /* may be NULL */, float *J /* [12] */);
+zoic_status zoic_trace_back_jacobian_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths /* n */,
+                                                     float *d_screen /* n x 2 */, uint32_t *d_flags /* may be NULL */,
+                                                     float *d_jacobian /* n x 12 */, void *stream);
+zoic_status zoic_trace_back_ray_jacobian_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm,
+                                                  float *Ps /* [2] */, uint32_t *flags /* may be NULL */, float *J /* [12] */);
 
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins

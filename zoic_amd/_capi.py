@@ -133,6 +133,10 @@ SYMBOLS = {
     "zoic_trace_back_ray": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_trace_back_rays_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zoic_trace_back_ray_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
+    "zoic_trace_back_jacobian_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "zoic_trace_back_ray_jacobian": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(C.c_float)]),
+    "zoic_trace_back_jacobian_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zoic_trace_back_ray_jacobian_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(C.c_float)]),
     "zoic_project_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zoic_project_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),

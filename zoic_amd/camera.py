@@ -72,6 +72,34 @@ def hero_rays_to_dict(rays):
                 tries=((flags >> 1) & 31).astype(np.int32))
 
 
+def solid_angle_measure(jac, dirs, basis=None):
+    """dPs/d(omega) of traced-back rays: det(J_d |d| [e1 e2]), signed, shape (n,) -- what a splatter divides by.
+
+    jac: (n,2,6) Jacobians of ZoicCamera.trace_back_jacobian (or one (2,6)); dirs: the (n,3) directions they were taken at, at the
+    length they were given (J_d is the derivative with respect to dir as given, so a step d(omega) of the unit direction is a step
+    |d| d(omega) of dir).  numpy in, numpy out (float64); torch in, torch out (the inputs' dtype and device).  No kernel.
+
+    (e1, e2) is any right-handed orthonormal basis of the plane across d (e1 x e2 = d / |d|).  The result does not depend on the
+    choice of basis: with a, b the two rows of J_d, det([a; b] [e1 e2]) = (a x b) . (e1 x e2) = (a x b) . d / |d|, which is what is
+    evaluated when basis is None; another right-handed basis is the first turned about d, a factor of determinant 1.
+    basis: optional (e1, e2), each (n,3), to evaluate the determinant with that basis literally."""
+    if _is_torch(jac):
+        import torch
+        J = jac.reshape(-1, 2, 6)[:, :, 3:6]
+        d = dirs.reshape(-1, 3).to(J.dtype)
+        if basis is None:
+            return (torch.linalg.cross(J[:, 0], J[:, 1]) * d).sum(1) * torch.linalg.norm(d, dim=1)
+        E = torch.stack([basis[0].reshape(-1, 3).to(J.dtype), basis[1].reshape(-1, 3).to(J.dtype)], 2)
+        return torch.linalg.det(J @ E) * (d * d).sum(1)
+    J = np.asarray(jac, np.float64).reshape(-1, 2, 6)[:, :, 3:6]
+    d = np.asarray(dirs, np.float64).reshape(-1, 3)
+    if basis is None:
+        return (np.cross(J[:, 0], J[:, 1]) * d).sum(1) * np.linalg.norm(d, axis=1)
+    E = np.stack([np.asarray(basis[0], np.float64).reshape(-1, 3), np.asarray(basis[1], np.float64).reshape(-1, 3)], 2)
+    A = J @ E
+    return (A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]) * (d * d).sum(1)
+
+
 class PinnedArray:
     """A numpy array over page-locked host memory (zoic_host_alloc): buffers of this kind let create_rays' host path
     run as an asynchronous two-stream pipeline.  Keep the object alive as long as the array is used."""
@@ -620,6 +648,82 @@ class ZoicCamera:
             return out, flags
         self._check(self._lib.zoic_trace_back_rays_device(self._h, n, rays.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
         return out, flags
+
+    def trace_back_ray_jacobian(self, origin, dir, wavelength=None):
+        """Trace-back of one camera ray on the host with its Jacobian (zoic_trace_back_ray_jacobian): (sx, sy, flags, J (2,6) float32).
+        sx, sy and flags are trace_back_ray's bit for bit; J = d(sx, sy) / d(origin.xyz, dir.xyz), dir differentiated as given
+        (csrc/traceback_jacobian.hpp); all zero for a ray that is not traced back.  Works on a tables-only camera (device=-1).
+        wavelength (nm): the trace at that wavelength, held fixed (zoic_trace_back_ray_jacobian_spectral)."""
+        o = _capi.Vec3(*[float(v) for v in origin])
+        d = _capi.Vec3(*[float(v) for v in dir])
+        ps = (C.c_float * 2)(0.0, 0.0)
+        f = C.c_uint32(0)
+        jac = np.zeros((2, 6), np.float32)
+        pj = jac.ctypes.data_as(C.POINTER(C.c_float))
+        if wavelength is not None:
+            self._check(self._lib.zoic_trace_back_ray_jacobian_spectral(self._h, C.byref(o), C.byref(d), float(wavelength), ps, C.byref(f), pj))
+        else:
+            self._check(self._lib.zoic_trace_back_ray_jacobian(self._h, C.byref(o), C.byref(d), ps, C.byref(f), pj))
+        return float(ps[0]), float(ps[1]), int(f.value), jac
+
+    def trace_back_jacobian(self, rays, wavelengths=None, out=None, flags=None, jacobian=None, stream=None):
+        """Trace-back of n camera rays with the Jacobian of each (zoic_trace_back_jacobian_device): returns (screen (n,2) float32,
+        flags (n,) int32, jac (n,2,6) float32).  screen and flags are trace_back's bit for bit; jac[i] = d(sx, sy) / d(origin.xyz,
+        dir.xyz) of ray i (csrc/traceback_jacobian.hpp), all zero where bit 0 of its flags is clear.  solid_angle_measure(jac, dirs)
+        turns it into the dPs/d(omega) a splatter divides by.
+
+        rays, wavelengths, stream: as trace_back takes them (device tensors, the dict of a create_rays call, or numpy).
+        out / flags / jacobian: optional (n,2) float32, (n,) int32 and (n,2,6) float32 tensors on the rays' device to write into
+        (torch rays only)."""
+        import torch
+        if isinstance(rays, dict):
+            rays = rays["rays"]
+        if not _is_torch(rays):
+            if out is not None or flags is not None or jacobian is not None:
+                raise ValueError("out, flags and jacobian are for torch rays")
+            if wavelengths is not None and _is_torch(wavelengths):
+                raise TypeError("numpy rays need numpy wavelengths")
+            a = np.asarray(rays)
+            if a.dtype == np.dtype(_capi.RAY_DTYPE):
+                a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32")
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                if wavelengths is not None:
+                    self._check(self._lib.zoic_trace_back_jacobian_spectral_device(self._h, a.shape[0], None, None, None, None, None, None))
+                self._check(self._lib.zoic_trace_back_jacobian_device(self._h, a.shape[0], None, None, None, None, None))
+            dev = torch.device("cuda", self.device)
+            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            scr, fl, jac = self.trace_back_jacobian(torch.from_numpy(a).to(dev), wavelengths=tw)
+            torch.cuda.synchronize(dev)
+            return scr.cpu().numpy(), fl.cpu().numpy(), jac.cpu().numpy()
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+            raise ValueError("rays must be a contiguous (n,8) float32 device tensor")
+        if rays.device.index != self.device:
+            raise ValueError("rays live on cuda:%s but this camera is bound to device %d" % (rays.device.index, self.device))
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
+        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rays.device:
+            raise ValueError("out must be a contiguous (n,2) float32 tensor on the rays' device")
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != rays.device:
+            raise ValueError("flags must be a contiguous (n,) int32 tensor on the rays' device")
+        if jacobian is None:
+            jacobian = torch.empty((n, 2, 6), dtype=torch.float32, device=rays.device)
+        if tuple(jacobian.shape) != (n, 2, 6) or jacobian.dtype != torch.float32 or not jacobian.is_contiguous() or jacobian.device != rays.device:
+            raise ValueError("jacobian must be a contiguous (n,2,6) float32 tensor on the rays' device")
+        st = stream if stream is not None else torch.cuda.current_stream(rays.device).cuda_stream
+        if wavelengths is not None:
+            w = self._wavelength_tensor(wavelengths, n, rays)
+            self._check(self._lib.zoic_trace_back_jacobian_spectral_device(self._h, n, rays.data_ptr(), w.data_ptr(), out.data_ptr(),
+                                                                           flags.data_ptr(), jacobian.data_ptr(), C.c_void_p(st)))
+            return out, flags, jacobian
+        self._check(self._lib.zoic_trace_back_jacobian_device(self._h, n, rays.data_ptr(), out.data_ptr(), flags.data_ptr(),
+                                                              jacobian.data_ptr(), C.c_void_p(st)))
+        return out, flags, jacobian
 
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
         """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1).

@@ -40,6 +40,7 @@
 #include "reverse.hpp"
 #include "backward_spectral.hpp"
 #include "traceback.hpp"
+#include "traceback_jacobian.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
 
@@ -2037,6 +2038,70 @@ zoic_status zoic_trace_back_rays_spectral_device(zoic_camera *cam, uint64_t n, c
     BackwardDispersion D;
     fill_backward(cam, D);
     const int rc = launch_trace_back_spectral(cam->traceBack, D, d_rays, d_wavelengths, n, d_screen, d_flags, stream);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_ray_jacobian(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps, uint32_t *flags, float *J)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!origin || !dir || !Ps || !J) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir, Ps and J must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    const uint32_t f = trace_back_ray_jacobian(cam->traceBack, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0], Ps[1], J);
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_jacobian_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_screen, uint32_t *d_flags,
+                                            float *d_jacobian, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
+    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
+    if (!d_jacobian || (reinterpret_cast<uintptr_t>(d_jacobian) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_jacobian must be non-NULL and 16-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    if (!is_device_memory(d_rays) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)) || !is_device_memory(d_jacobian))
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_screen, d_flags and d_jacobian must be device memory");
+    const int rc = launch_trace_back_jacobian(cam->traceBack, d_rays, n, d_screen, d_flags, d_jacobian, stream);
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_ray_jacobian_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm,
+                                                  float *Ps, uint32_t *flags, float *J)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!origin || !dir || !Ps || !J) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir, Ps and J must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    BackwardDispersion D;
+    fill_backward(cam, D);
+    const uint32_t f = trace_back_ray_jacobian_spectral(cam->traceBack, D, wavelength_nm, origin->x, origin->y, origin->z, dir->x, dir->y,
+                                                        dir->z, Ps[0], Ps[1], J);
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+zoic_status zoic_trace_back_jacobian_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths,
+                                                     float *d_screen, uint32_t *d_flags, float *d_jacobian, void *stream)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
+    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
+    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
+    if (!d_jacobian || (reinterpret_cast<uintptr_t>(d_jacobian) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_jacobian must be non-NULL and 16-byte aligned");
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    if (!is_device_memory(d_rays) || !is_device_memory(d_wavelengths) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)) ||
+        !is_device_memory(d_jacobian))
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_wavelengths, d_screen, d_flags and d_jacobian must be device memory");
+    BackwardDispersion D;
+    fill_backward(cam, D);
+    const int rc = launch_trace_back_jacobian_spectral(cam->traceBack, D, d_rays, d_wavelengths, n, d_screen, d_flags, d_jacobian, stream);
     if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
     return ZOIC_OK;
 }
