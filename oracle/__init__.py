@@ -77,6 +77,8 @@ def lib():
         L.zo_camera_set_lens_text.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.zo_camera_update.argtypes = [vp, C.POINTER(Params)]; L.zo_camera_update.restype = C.c_int
         L.zo_create_rays.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+        L.zo_create_rays_starts.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+        L.zo_trace_rays.argtypes = [vp, C.c_size_t, vp, vp, vp]
         L.zo_create_rays_mt.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_int]
         for name, rt in [("zo_lens_count", C.c_int), ("zo_aperture_element", C.c_int),
                          ("zo_user_aperture_radius", C.c_float), ("zo_origin_shift", C.c_float),
@@ -199,6 +201,31 @@ class OracleCamera:
         if frs is not None:
             out["first_retry_states"] = frs
         return out
+
+    def create_rays_starts(self, samples, rng_states):
+        """create_rays with per-ray states, plus starts (n, 6) float32: the (origin, dir) handed to each ray's last
+        traceThroughLensElements call (RAYTRACED; the accepted try's start where the weight is not 0)"""
+        s = np.ascontiguousarray(samples, dtype=np.float32)
+        n = s.shape[0]
+        rs = np.ascontiguousarray(rng_states, dtype=np.uint32)
+        assert s.shape == (n, 4) and rs.shape == (n, 4)
+        planes = np.zeros((7, n), dtype=np.float32)
+        flags = np.zeros(n, dtype=np.uint8)
+        starts = np.zeros((n, 6), dtype=np.float32)
+        self._L.zo_create_rays_starts(self._h, n, s.ctypes.data, planes.ctypes.data, flags.ctypes.data, rs.ctypes.data, starts.ctypes.data)
+        return dict(origin=planes[0:3], dir=planes[3:6], weight=planes[6], flags=flags, planes=planes, tries=(flags >> 1).astype(np.int32),
+                    starts=starts)
+
+    def trace_rays(self, starts):
+        """traceThroughLensElements on n (origin, dir) pairs, starts (n, 6) float32, with the current lens table: ok (n,) bool and
+        ends (n, 6) float32"""
+        st = np.ascontiguousarray(starts, dtype=np.float32)
+        n = st.shape[0]
+        assert st.shape == (n, 6)
+        ok = np.zeros(n, dtype=np.uint8)
+        ends = np.zeros((n, 6), dtype=np.float32)
+        self._L.zo_trace_rays(self._h, n, st.ctypes.data, ok.ctypes.data, ends.ctypes.data)
+        return ok.astype(bool), ends
 
     # ---- tables -----------------------------------------------------------
     def lens_table(self):

@@ -589,6 +589,29 @@ int zo_trace_record(zo_camera *cam, zo_v3 *origin, zo_v3 *dir, zo_v3 *hits, int 
     return traceThroughLensElements(origin, dir, &cam->lens, hits, nhits);
 }
 
+/* zo_trace_record without the hit dump, n rays at a time, with the camera's CURRENT lens table (a test that wrote other indices into
+ * zo_lenses traces with those) */
+void zo_trace_rays(zo_camera *cam, size_t n, const float *starts, uint8_t *ok, float *ends)
+{
+    for (size_t i = 0; i < n; ++i) {
+        zo_v3 o = V3(starts[6 * i + 0], starts[6 * i + 1], starts[6 * i + 2]);
+        zo_v3 d = V3(starts[6 * i + 3], starts[6 * i + 4], starts[6 * i + 5]);
+        ok[i] = (uint8_t)traceThroughLensElements(&o, &d, &cam->lens, NULL, NULL);
+        ends[6 * i + 0] = o.x; ends[6 * i + 1] = o.y; ends[6 * i + 2] = o.z;
+        ends[6 * i + 3] = d.x; ends[6 * i + 4] = d.y; ends[6 * i + 5] = d.z;
+    }
+}
+
+/* Diagnostic hook (tests only; never alters a result): while g_start_probe points at two vectors, every traceThroughLensElements call
+ * of camera_create_ray's RAYTRACED branch leaves the (origin, dir) it is handed there, BEFORE the call: after the ray, the start of
+ * its last try (zo_create_rays_starts). */
+static __thread zo_v3 *g_start_probe = NULL;
+static inline int trace_try(zo_v3 *origin, zo_v3 *dir, zo_lensdata *ld)
+{
+    if (g_start_probe) { g_start_probe[0] = *origin; g_start_probe[1] = *dir; }
+    return traceThroughLensElements(origin, dir, ld, NULL, NULL);
+}
+
 /* traceThroughLensElementsForFocalLength, zoic.cpp:1161-1228 */
 static float traceThroughLensElementsForFocalLength(zo_lensdata *ld)
 {
@@ -900,7 +923,7 @@ void zo_create_ray(zo_camera *camera, const zo_input *input, zo_output *output, 
             output->dir.x = (lens.x * ld->lenses[0].aperture) - output->origin.x;
             output->dir.y = (lens.y * ld->lenses[0].aperture) - output->origin.y;
             output->dir.z = -ld->lenses[0].thickness;
-            while (!traceThroughLensElements(&output->origin, &output->dir, ld, NULL, NULL) && tries <= maxtries) {
+            while (!trace_try(&output->origin, &output->dir, ld) && tries <= maxtries) {
                 output->origin = kolb_origin_original;
                 float u = (float)((double)zo_xor128(rng) / 4294967296.0);   /* :1881 f64 divide, f32 argument */
                 float v = (float)((double)zo_xor128(rng) / 4294967296.0);
@@ -945,7 +968,7 @@ void zo_create_ray(zo_camera *camera, const zo_input *input, zo_output *output, 
             output->dir.x = lens.x - output->origin.x;
             output->dir.y = lens.y - output->origin.y;
             output->dir.z = -ld->lenses[0].thickness;
-            while (!traceThroughLensElements(&output->origin, &output->dir, ld, NULL, NULL) && tries <= maxtries) {
+            while (!trace_try(&output->origin, &output->dir, ld) && tries <= maxtries) {
                 output->origin = kolb_origin_original;
                 float u = (float)((double)zo_xor128(rng) / 4294967296.0);   /* :1930 */
                 float v = (float)((double)zo_xor128(rng) / 4294967296.0);
@@ -1044,6 +1067,23 @@ void zo_create_rays(zo_camera *cam, size_t n, const float *in4, float *planes, u
                 else s[0] = s[1] = s[2] = s[3] = 0;
             }
         }
+    }
+}
+
+/* zo_create_rays with per-ray states, and the start of each ray's last try beside its record: starts = n x (origin, dir), the pair
+ * handed to the last traceThroughLensElements call of the RAYTRACED branch, recorded before the call (zeros for the other lens
+ * models).  It is the accepted try's start where the ray ends with weight != 0. */
+void zo_create_rays_starts(zo_camera *cam, size_t n, const float *in4, float *planes, uint8_t *flags,
+                           const uint32_t *rng_states, float *starts)
+{
+    for (size_t i = 0; i < n; ++i) {
+        zo_rng r = { rng_states[4 * i], rng_states[4 * i + 1], rng_states[4 * i + 2], rng_states[4 * i + 3] };
+        zo_v3 start[2] = { { 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f } };
+        g_start_probe = start;
+        one_ray(cam, n, i, in4, planes, flags, &r, NULL);
+        g_start_probe = NULL;
+        starts[6 * i + 0] = start[0].x; starts[6 * i + 1] = start[0].y; starts[6 * i + 2] = start[0].z;
+        starts[6 * i + 3] = start[1].x; starts[6 * i + 4] = start[1].y; starts[6 * i + 5] = start[1].z;
     }
 }
 

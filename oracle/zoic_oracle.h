@@ -104,6 +104,12 @@ void zo_create_ray(zo_camera *, const zo_input *in, zo_output *out, zo_rng *rng,
 void zo_create_rays(zo_camera *, size_t n, const float *in4, float *planes, uint8_t *flags,
                     const uint32_t *rng_states, uint32_t *first_retry_states);
 
+/* zo_create_rays with per-ray states (mandatory) that also returns each ray's start: starts = n x 6 floats, the (origin, dir) handed
+ * to the LAST traceThroughLensElements call of the RAYTRACED branch (zoic.cpp:1879 / 1927), recorded before the call; zeros for the
+ * other lens models.  Where the ray ends with weight != 0 it is the accepted try's start. */
+void zo_create_rays_starts(zo_camera *, size_t n, const float *in4, float *planes, uint8_t *flags,
+                           const uint32_t *rng_states, float *starts);
+
 /* multi-threaded cpu baseline: per-ray states are mandatory (the reference's shared RNG is a race) */
 void zo_create_rays_mt(zo_camera *, size_t n, const float *in4, float *planes, uint8_t *flags,
                        const uint32_t *rng_states, int nthreads);
@@ -142,6 +148,11 @@ void  zo_bokeh_sample(const zo_camera *, float u1, float u2, float *dx, float *d
  * hits receives up to lensCount (z,y,x) triples of the accepted hit points; returns 1 on success and
  * writes the number of recorded hits to *nhits. */
 int   zo_trace_record(zo_camera *, zo_v3 *origin, zo_v3 *dir, zo_v3 *hits, int *nhits);
+
+/* zo_trace_record without the hit dump, for n rays: starts = n x 6 floats (origin, dir) traced through the camera's current lens
+ * table (zo_lenses); ok[i] = 1 where ray i came through, ends = n x 6 floats, the (origin, dir) the trace left (partial where it
+ * did not) */
+void  zo_trace_rays(zo_camera *, size_t n, const float *starts, uint8_t *ok, float *ends);
 
 /* diagnostic (tools/tests only): how close the closest accept/reject decision of a ray's evaluation was.
  * kind: 0 housing/stop clip (zoic.cpp:1114-1115), 1 sphere miss (:980), 2 total internal reflection (:1019) */

@@ -1,6 +1,7 @@
 """Hero-wavelength rays on the MI355X (zoic_create_rays_hero_device): column 0 is the spectral call bit for bit, counters included; a
-companion is the hero's accepted start traced once at its own wavelength -- the CPU oracle's record where the oracle accepts the same
-try at that wavelength, a lost record where it needs a later one; a companion at the hero's wavelength repeats the hero's record; FAST
+companion is the hero's accepted start traced once at its own wavelength -- the record of the CPU reference of the whole call
+(tests/hero_ref.py) on every row, which is the CPU oracle's own record where the oracle accepts the same try at that wavelength and a
+lost record where it needs a later one; a companion at the hero's wavelength repeats the hero's record; FAST
 agrees with STRICT; live companions trace back to the hero's screen sample; rejected wavelengths, the thin lens, determinism, launch
 splits and the error codes behave as the header states.
 
@@ -14,6 +15,7 @@ from zoic_amd.workloads import ray_rng_states
 
 import backward_spectral_ref as bs
 from fuzz_cameras import _oracle_spectral, same_bits
+from hero_ref import hero_reference, same_words, words_of as _words
 from spectral_ref import LAMBDA_D
 from test_spectral_gpu import BAD, WAVES, _bits, _camera, _delta, _params, _samples
 
@@ -41,11 +43,6 @@ def _hero_waves(n, k, seed=1):
     w = np.random.RandomState(seed).uniform(360.0, 830.0, (n, k)).astype(np.float32)
     w[:, 0] = np.resize(WAVES, n)
     return w
-
-
-def _words(r):
-    """(n, k, 8) uint32: all 8 words of the records of a numpy create_rays_hero result"""
-    return np.ascontiguousarray(r["rays"]).view(np.uint32).reshape(r["rays"].shape + (8,))
 
 
 def _column_equals(hero, j, ref):
@@ -84,6 +81,9 @@ def test_companions_against_the_oracle(oracle_lib, cfg, over):
     got = cam.create_rays_hero(s, w, rng_states=st)
     cam.close()
     ref = [_oracle_spectral(oracle_lib, p, disp, s, np.ascontiguousarray(w[:, j]), st)[0] for j in range(4)]
+    # every record of every row, those the try counts say nothing about included: the CPU reference of the whole call
+    want, _ = hero_reference(oracle_lib, p, disp, s, w, st)
+    assert same_words(_words(got), want).all(), int((~same_words(_words(got), want)).sum())
     tries = [((r["flags"] >> 1) & 31).astype(np.int32) for r in ref]
     # the hero is the oracle's ray at the hero's wavelength
     assert np.array_equal(got["flags"][:, 0], ref[0]["flags"])
@@ -99,7 +99,7 @@ def test_companions_against_the_oracle(oracle_lib, cfg, over):
         earlier = live & (tries[j] < tries[0])
         print("%s column %d (%g nm): live %d, same try %d (retried %d), lost %d, left out %d" %
               (cfg, j, COLUMNS[j], live.sum(), same.sum(), (same & (tries[0] > 0)).sum(), later.sum(), earlier.sum()))
-        assert earlier.sum() <= 0.02 * live.sum(), (j, earlier.sum(), live.sum())
+        assert earlier.sum() <= 0.02 * live.sum(), (j, earlier.sum(), live.sum())   # about the inputs: the try counts decide nearly every row
         assert same_bits(pl[:, same], ref[j]["planes"][:, same]).all(), (j, int((~same_bits(pl[:, same], ref[j]["planes"][:, same]).all(0)).sum()))
         assert np.array_equal(f[same], hflags[same])
         assert (_bits(pl[:, later]) == 0).all() and np.array_equal(f[later], hflags[later] | LOST)
