@@ -18,7 +18,7 @@ import traceback_cases as tc
 import traceback_jacobian_ref as jr
 from traceback_ref import TraceBack
 
-SLAB = 2048 * 256   # one grid of the kernels (traceback_jacobian.hip): larger batches are walked slab by slab
+SLAB = 2048 * 256   # one grid of the kernels (traceback.hip): larger batches are walked slab by slab
 W, H, SPP = 64, 36, 2
 N = W * H * SPP
 EDGE_ROWS = np.array([[0, 0, -1, 0, 0, -1], [0, 0, -1e30, 0, 0, -1e-30], [1e30, 0, -1, 0, 0, -1], [0, 0, -1, 1e30, 0, -1e-30],

@@ -512,6 +512,71 @@ class ZoicCamera:
             raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the items' device")
         return wavelengths
 
+    def _backward_batch(self, what, width, dline, spectral, items, wavelengths, out, flags, stream, jacobian=None, with_jacobian=False):
+        """The batch wrapper of project_points, trace_back and trace_back_jacobian.  `what` ("points" / "rays") names the (n, width)
+        float32 items; dline / spectral are the library's entry points without and with wavelengths.  Returns (out, flags) and, with
+        with_jacobian, the (n,2,6) jacobian: tensors for torch items, numpy arrays (after a round trip and a wait) for numpy items."""
+        import torch
+        if not _is_torch(items):
+            if out is not None or flags is not None or jacobian is not None:
+                raise ValueError("%s are for torch %s" % ("out, flags and jacobian" if with_jacobian else "out and flags", what))
+            if wavelengths is not None and _is_torch(wavelengths):
+                raise TypeError("numpy %s need numpy wavelengths" % what)
+            a = np.asarray(items)
+            if width == 8 and a.dtype == np.dtype(_capi.RAY_DTYPE):
+                a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != width:
+                raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32" if width == 8 else "%s must be (n, %d)" % (what, width))
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                if wavelengths is not None:
+                    self._check(spectral(self._h, a.shape[0], *[None] * (6 if with_jacobian else 5)))
+                self._check(dline(self._h, a.shape[0], *[None] * (5 if with_jacobian else 4)))
+            dev = torch.device("cuda", self.device)
+            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            res = self._backward_batch(what, width, dline, spectral, torch.from_numpy(a).to(dev), tw, None, None, None, None, with_jacobian)
+            torch.cuda.synchronize(dev)
+            return tuple(t.cpu().numpy() for t in res)
+        if items.dtype != torch.float32 or items.dim() != 2 or items.shape[1] != width or not items.is_contiguous() or not items.is_cuda:
+            raise ValueError("%s must be a contiguous (n,%d) float32 device tensor" % (what, width))
+        if items.device.index != self.device:
+            raise ValueError("%s live on cuda:%s but this camera is bound to device %d" % (what, items.device.index, self.device))
+        n = items.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=items.device)
+        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != items.device:
+            raise ValueError("out must be a contiguous (n,2) float32 tensor on the %s' device" % what)
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.int32, device=items.device)
+        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != items.device:
+            raise ValueError("flags must be a contiguous (n,) int32 tensor on the %s' device" % what)
+        res, tail = (out, flags), [out.data_ptr(), flags.data_ptr()]
+        if with_jacobian:
+            if jacobian is None:
+                jacobian = torch.empty((n, 2, 6), dtype=torch.float32, device=items.device)
+            if tuple(jacobian.shape) != (n, 2, 6) or jacobian.dtype != torch.float32 or not jacobian.is_contiguous() or jacobian.device != items.device:
+                raise ValueError("jacobian must be a contiguous (n,2,6) float32 tensor on the %s' device" % what)
+            res, tail = (out, flags, jacobian), tail + [jacobian.data_ptr()]
+        tail.append(C.c_void_p(stream if stream is not None else torch.cuda.current_stream(items.device).cuda_stream))
+        if wavelengths is not None:
+            w = self._wavelength_tensor(wavelengths, n, items)
+            self._check(spectral(self._h, n, items.data_ptr(), w.data_ptr(), *tail))
+        else:
+            self._check(dline(self._h, n, items.data_ptr(), *tail))
+        return res
+
+    def _trace_back_one(self, dline, spectral, origin, dir, wavelength, *extra):
+        """the host single-ray wrappers' call: (sx, sy, flags); extra: further output arguments of both entry points"""
+        o = _capi.Vec3(*[float(v) for v in origin])
+        d = _capi.Vec3(*[float(v) for v in dir])
+        ps = (C.c_float * 2)(0.0, 0.0)
+        f = C.c_uint32(0)
+        if wavelength is not None:
+            self._check(spectral(self._h, C.byref(o), C.byref(d), float(wavelength), ps, C.byref(f), *extra))
+        else:
+            self._check(dline(self._h, C.byref(o), C.byref(d), ps, C.byref(f), *extra))
+        return float(ps[0]), float(ps[1]), int(f.value)
+
     def project_point(self, Po, wavelength=None):
         """Reverse projection of one point on the host (zoic_project_point): (sx, sy, flags).  Po in the frame of the records the
         forward calls write.  flags bit 0: projected; bit 1: the chief ray is clipped; bit 2: beyond the exit-pupil LUT; bits 8-11:
@@ -536,45 +601,8 @@ class ZoicCamera:
                      (n,) int32 tensors on the points' device to write into.
         wavelengths: (n,) float32 (nm), numpy with numpy points, a device tensor with device points: every point projected at its own
                      wavelength (zoic_project_points_spectral_device); None: the d-line call."""
-        import torch
-        if not _is_torch(points):
-            if out is not None or flags is not None:
-                raise ValueError("out and flags are for torch points")
-            if wavelengths is not None and _is_torch(wavelengths):
-                raise TypeError("numpy points need numpy wavelengths")
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError("points must be (n, 3)")
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                if wavelengths is not None:
-                    self._check(self._lib.zoic_project_points_spectral_device(self._h, a.shape[0], None, None, None, None, None))
-                self._check(self._lib.zoic_project_points_device(self._h, a.shape[0], None, None, None, None))
-            dev = torch.device("cuda", self.device)
-            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            scr, fl = self.project_points(torch.from_numpy(a).to(dev), wavelengths=tw)
-            torch.cuda.synchronize(dev)
-            return scr.cpu().numpy(), fl.cpu().numpy()
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
-            raise ValueError("points must be a contiguous (n,3) float32 device tensor")
-        if points.device.index != self.device:
-            raise ValueError("points live on cuda:%s but this camera is bound to device %d" % (points.device.index, self.device))
-        n = points.shape[0]
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float32, device=points.device)
-        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
-            raise ValueError("out must be a contiguous (n,2) float32 tensor on the points' device")
-        if flags is None:
-            flags = torch.empty((n,), dtype=torch.int32, device=points.device)
-        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != points.device:
-            raise ValueError("flags must be a contiguous (n,) int32 tensor on the points' device")
-        st = stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream
-        if wavelengths is not None:
-            w = self._wavelength_tensor(wavelengths, n, points)
-            self._check(self._lib.zoic_project_points_spectral_device(self._h, n, points.data_ptr(), w.data_ptr(), out.data_ptr(), flags.data_ptr(),
-                                                                      C.c_void_p(st)))
-            return out, flags
-        self._check(self._lib.zoic_project_points_device(self._h, n, points.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
-        return out, flags
+        return self._backward_batch("points", 3, self._lib.zoic_project_points_device, self._lib.zoic_project_points_spectral_device, points,
+                                    wavelengths, out, flags, stream)
 
     def trace_back_ray(self, origin, dir, wavelength=None):
         """Trace-back of one camera ray on the host (zoic_trace_back_ray): (sx, sy, flags).  origin / dir in the frame of the records
@@ -583,15 +611,7 @@ class ZoicCamera:
         tables-only camera (device=-1).
         wavelength (nm): the trace through the glass at that wavelength (zoic_trace_back_ray_spectral, csrc/backward_spectral.hpp);
         outside [360, 830] or NaN: not traced back, reason _capi.TRACE_BACK_WAVELENGTH."""
-        o = _capi.Vec3(*[float(v) for v in origin])
-        d = _capi.Vec3(*[float(v) for v in dir])
-        ps = (C.c_float * 2)(0.0, 0.0)
-        f = C.c_uint32(0)
-        if wavelength is not None:
-            self._check(self._lib.zoic_trace_back_ray_spectral(self._h, C.byref(o), C.byref(d), float(wavelength), ps, C.byref(f)))
-            return float(ps[0]), float(ps[1]), int(f.value)
-        self._check(self._lib.zoic_trace_back_ray(self._h, C.byref(o), C.byref(d), ps, C.byref(f)))
-        return float(ps[0]), float(ps[1]), int(f.value)
+        return self._trace_back_one(self._lib.zoic_trace_back_ray, self._lib.zoic_trace_back_ray_spectral, origin, dir, wavelength)
 
     def trace_back(self, rays, out=None, flags=None, stream=None, wavelengths=None):
         """Trace-back of n camera rays (zoic_trace_back_rays_device): returns (screen (n,2) float32, flags (n,) int32).
@@ -604,67 +624,19 @@ class ZoicCamera:
         wavelengths: (n,) float32 (nm), numpy with numpy rays, a device tensor with device rays -- for the records of
                      create_rays(samples, wavelengths=w), the same w: every ray traced back at its own wavelength
                      (zoic_trace_back_rays_spectral_device); None: the d-line call."""
-        import torch
         if isinstance(rays, dict):
             rays = rays["rays"]
-        if not _is_torch(rays):
-            if out is not None or flags is not None:
-                raise ValueError("out and flags are for torch rays")
-            if wavelengths is not None and _is_torch(wavelengths):
-                raise TypeError("numpy rays need numpy wavelengths")
-            a = np.asarray(rays)
-            if a.dtype == np.dtype(_capi.RAY_DTYPE):
-                a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32")
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                if wavelengths is not None:
-                    self._check(self._lib.zoic_trace_back_rays_spectral_device(self._h, a.shape[0], None, None, None, None, None))
-                self._check(self._lib.zoic_trace_back_rays_device(self._h, a.shape[0], None, None, None, None))
-            dev = torch.device("cuda", self.device)
-            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            scr, fl = self.trace_back(torch.from_numpy(a).to(dev), wavelengths=tw)
-            torch.cuda.synchronize(dev)
-            return scr.cpu().numpy(), fl.cpu().numpy()
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-            raise ValueError("rays must be a contiguous (n,8) float32 device tensor")
-        if rays.device.index != self.device:
-            raise ValueError("rays live on cuda:%s but this camera is bound to device %d" % (rays.device.index, self.device))
-        n = rays.shape[0]
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
-        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rays.device:
-            raise ValueError("out must be a contiguous (n,2) float32 tensor on the rays' device")
-        if flags is None:
-            flags = torch.empty((n,), dtype=torch.int32, device=rays.device)
-        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != rays.device:
-            raise ValueError("flags must be a contiguous (n,) int32 tensor on the rays' device")
-        st = stream if stream is not None else torch.cuda.current_stream(rays.device).cuda_stream
-        if wavelengths is not None:
-            w = self._wavelength_tensor(wavelengths, n, rays)
-            self._check(self._lib.zoic_trace_back_rays_spectral_device(self._h, n, rays.data_ptr(), w.data_ptr(), out.data_ptr(), flags.data_ptr(),
-                                                                       C.c_void_p(st)))
-            return out, flags
-        self._check(self._lib.zoic_trace_back_rays_device(self._h, n, rays.data_ptr(), out.data_ptr(), flags.data_ptr(), C.c_void_p(st)))
-        return out, flags
+        return self._backward_batch("rays", 8, self._lib.zoic_trace_back_rays_device, self._lib.zoic_trace_back_rays_spectral_device, rays,
+                                    wavelengths, out, flags, stream)
 
     def trace_back_ray_jacobian(self, origin, dir, wavelength=None):
         """Trace-back of one camera ray on the host with its Jacobian (zoic_trace_back_ray_jacobian): (sx, sy, flags, J (2,6) float32).
         sx, sy and flags are trace_back_ray's bit for bit; J = d(sx, sy) / d(origin.xyz, dir.xyz), dir differentiated as given
         (csrc/traceback_jacobian.hpp); all zero for a ray that is not traced back.  Works on a tables-only camera (device=-1).
         wavelength (nm): the trace at that wavelength, held fixed (zoic_trace_back_ray_jacobian_spectral)."""
-        o = _capi.Vec3(*[float(v) for v in origin])
-        d = _capi.Vec3(*[float(v) for v in dir])
-        ps = (C.c_float * 2)(0.0, 0.0)
-        f = C.c_uint32(0)
         jac = np.zeros((2, 6), np.float32)
-        pj = jac.ctypes.data_as(C.POINTER(C.c_float))
-        if wavelength is not None:
-            self._check(self._lib.zoic_trace_back_ray_jacobian_spectral(self._h, C.byref(o), C.byref(d), float(wavelength), ps, C.byref(f), pj))
-        else:
-            self._check(self._lib.zoic_trace_back_ray_jacobian(self._h, C.byref(o), C.byref(d), ps, C.byref(f), pj))
-        return float(ps[0]), float(ps[1]), int(f.value), jac
+        return self._trace_back_one(self._lib.zoic_trace_back_ray_jacobian, self._lib.zoic_trace_back_ray_jacobian_spectral, origin, dir,
+                                    wavelength, jac.ctypes.data_as(C.POINTER(C.c_float))) + (jac,)
 
     def trace_back_jacobian(self, rays, wavelengths=None, out=None, flags=None, jacobian=None, stream=None):
         """Trace-back of n camera rays with the Jacobian of each (zoic_trace_back_jacobian_device): returns (screen (n,2) float32,
@@ -675,55 +647,10 @@ class ZoicCamera:
         rays, wavelengths, stream: as trace_back takes them (device tensors, the dict of a create_rays call, or numpy).
         out / flags / jacobian: optional (n,2) float32, (n,) int32 and (n,2,6) float32 tensors on the rays' device to write into
         (torch rays only)."""
-        import torch
         if isinstance(rays, dict):
             rays = rays["rays"]
-        if not _is_torch(rays):
-            if out is not None or flags is not None or jacobian is not None:
-                raise ValueError("out, flags and jacobian are for torch rays")
-            if wavelengths is not None and _is_torch(wavelengths):
-                raise TypeError("numpy rays need numpy wavelengths")
-            a = np.asarray(rays)
-            if a.dtype == np.dtype(_capi.RAY_DTYPE):
-                a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32")
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                if wavelengths is not None:
-                    self._check(self._lib.zoic_trace_back_jacobian_spectral_device(self._h, a.shape[0], None, None, None, None, None, None))
-                self._check(self._lib.zoic_trace_back_jacobian_device(self._h, a.shape[0], None, None, None, None, None))
-            dev = torch.device("cuda", self.device)
-            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            scr, fl, jac = self.trace_back_jacobian(torch.from_numpy(a).to(dev), wavelengths=tw)
-            torch.cuda.synchronize(dev)
-            return scr.cpu().numpy(), fl.cpu().numpy(), jac.cpu().numpy()
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-            raise ValueError("rays must be a contiguous (n,8) float32 device tensor")
-        if rays.device.index != self.device:
-            raise ValueError("rays live on cuda:%s but this camera is bound to device %d" % (rays.device.index, self.device))
-        n = rays.shape[0]
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
-        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rays.device:
-            raise ValueError("out must be a contiguous (n,2) float32 tensor on the rays' device")
-        if flags is None:
-            flags = torch.empty((n,), dtype=torch.int32, device=rays.device)
-        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != rays.device:
-            raise ValueError("flags must be a contiguous (n,) int32 tensor on the rays' device")
-        if jacobian is None:
-            jacobian = torch.empty((n, 2, 6), dtype=torch.float32, device=rays.device)
-        if tuple(jacobian.shape) != (n, 2, 6) or jacobian.dtype != torch.float32 or not jacobian.is_contiguous() or jacobian.device != rays.device:
-            raise ValueError("jacobian must be a contiguous (n,2,6) float32 tensor on the rays' device")
-        st = stream if stream is not None else torch.cuda.current_stream(rays.device).cuda_stream
-        if wavelengths is not None:
-            w = self._wavelength_tensor(wavelengths, n, rays)
-            self._check(self._lib.zoic_trace_back_jacobian_spectral_device(self._h, n, rays.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                                                           flags.data_ptr(), jacobian.data_ptr(), C.c_void_p(st)))
-            return out, flags, jacobian
-        self._check(self._lib.zoic_trace_back_jacobian_device(self._h, n, rays.data_ptr(), out.data_ptr(), flags.data_ptr(),
-                                                              jacobian.data_ptr(), C.c_void_p(st)))
-        return out, flags, jacobian
+        return self._backward_batch("rays", 8, self._lib.zoic_trace_back_jacobian_device, self._lib.zoic_trace_back_jacobian_spectral_device,
+                                    rays, wavelengths, out, flags, stream, jacobian, True)
 
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
         """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1).

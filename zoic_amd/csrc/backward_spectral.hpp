@@ -150,7 +150,7 @@ inline void fill_backward_dispersion(BackwardDispersion &D, const SpectralTable 
     }
 }
 
-// ---- launchers (traceback_spectral.hip, reverse_spectral.hip) ------------------------------------------------------------
+// ---- launchers (traceback.hip, reverse.hip) ------------------------------------------------------------------------------
 // As launch_trace_back / launch_project_points, with d_lambda = n f32 wavelengths (nm, 4-byte aligned).  Asynchronous on `stream`.
 int launch_trace_back_spectral(const TraceBackTable &T, const BackwardDispersion &D, const void *d_rays, const float *d_lambda, uint64_t n,
                                float *d_screen, uint32_t *d_flags, void *stream);

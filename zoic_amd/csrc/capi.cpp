@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -620,6 +621,21 @@ zoic_status check_ray_call(const zoic_camera *cam)
     return ZOIC_OK;
 }
 
+// the result of a call that ends with a kernel launch: rc is what the launcher returned (hipGetLastError)
+zoic_status launch_status(int rc)
+{
+    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    return ZOIC_OK;
+}
+
+// one pointer argument of a device entry point: `align`-byte aligned (a power of two), and non-NULL unless it is optional
+zoic_status check_pointer(const char *name, const void *p, unsigned align, bool optional = false)
+{
+    if ((p || optional) && !(reinterpret_cast<uintptr_t>(p) & (align - 1u))) return ZOIC_OK;
+    return fail(ZOIC_ERR_INVALID_ARGUMENT,
+                std::string(name) + (optional ? " must be " : " must be non-NULL and ") + std::to_string(align) + "-byte aligned");
+}
+
 // One launch of camera_create_ray over n samples on `stream`, asynchronous.  Safe to call from many host threads at once.
 // modeOverride (0 STRICT / 1 decision-safe FAST / 2 unchecked; -1: the camera's) and counted = false (no counter is touched)
 // serve node_update's self-check of the FAST modes.
@@ -678,7 +694,7 @@ zoic_status launch_rays(zoic_camera *cam, uint64_t n, const float *d_samples, co
     // must wait behind it
     const hipError_t re = hipEventRecord(slot->done, stream);
     if (re == hipSuccess) { slot->recorded = true; slot->lastStream = stream; }
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (rc != 0) return launch_status(rc);
     ZOIC_HIP(re);
     return ZOIC_OK;
 }
@@ -778,6 +794,18 @@ void fill_spectral(const zoic_camera *cam, SpectralTable &W)
     }
 }
 
+// the lens rows (trace order) as the arrays the backward tables' fillers take
+struct FlatRows {
+    int n;
+    float radius[kMaxSurfaces], thickness[kMaxSurfaces], ior[kMaxSurfaces], aperture[kMaxSurfaces];
+    explicit FlatRows(const LensSystem &L) : n(static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces)))
+    {
+        for (int i = 0; i < n; ++i) {
+            radius[i] = L.rows[i].radius; thickness[i] = L.rows[i].thickness; ior[i] = L.rows[i].ior; aperture[i] = L.rows[i].aperture;
+        }
+    }
+};
+
 // the reverse projection's table (reverse.hpp) of the camera's current tables
 void fill_reverse(zoic_camera *cam)
 {
@@ -788,12 +816,8 @@ void fill_reverse(zoic_camera *cam)
                            0.0f, 0.0f, false, 0, false);
         return;
     }
-    const int n = static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces));
-    float radius[kMaxSurfaces], thickness[kMaxSurfaces], ior[kMaxSurfaces], aperture[kMaxSurfaces];
-    for (int i = 0; i < n; ++i) {
-        radius[i] = L.rows[i].radius; thickness[i] = L.rows[i].thickness; ior[i] = L.rows[i].ior; aperture[i] = L.rows[i].aperture;
-    }
-    fill_reverse_table(cam->reverse, 1, cam->tanFov, n, radius, thickness, ior, aperture, L.apertureElement, L.userApertureRadius,
+    const FlatRows R(L);
+    fill_reverse_table(cam->reverse, 1, cam->tanFov, R.n, R.radius, R.thickness, R.ior, R.aperture, L.apertureElement, L.userApertureRadius,
                        L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain);
 }
 
@@ -808,23 +832,21 @@ void fill_traceback(zoic_camera *cam)
                              p.opticalVignettingRadius);
         return;
     }
-    const int n = static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces));
-    float radius[kMaxSurfaces], thickness[kMaxSurfaces], ior[kMaxSurfaces], aperture[kMaxSurfaces];
-    for (int i = 0; i < n; ++i) {
-        radius[i] = L.rows[i].radius; thickness[i] = L.rows[i].thickness; ior[i] = L.rows[i].ior; aperture[i] = L.rows[i].aperture;
-    }
-    fill_traceback_table(cam->traceBack, 1, cam->tanFov, n, radius, thickness, ior, aperture, L.apertureElement, L.userApertureRadius,
-                         L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain, 0.0f, 0.0f,
-                         false, 0.0f, 0.0f);
+    const FlatRows R(L);
+    fill_traceback_table(cam->traceBack, 1, cam->tanFov, R.n, R.radius, R.thickness, R.ior, R.aperture, L.apertureElement,
+                         L.userApertureRadius, L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0,
+                         cam->fastDomain, 0.0f, 0.0f, false, 0.0f, 0.0f);
 }
 
 // the dispersion of the camera's lens in the backward tables' order (backward_spectral.hpp); as on the forward side it is taken at
 // the call, so a zoic_camera_set_abbe_numbers override needs no update
-void fill_backward(const zoic_camera *cam, BackwardDispersion &D)
+BackwardDispersion backward_dispersion(const zoic_camera *cam)
 {
     SpectralTable W;
     fill_spectral(cam, W);
+    BackwardDispersion D;
     fill_backward_dispersion(D, W);
+    return D;
 }
 
 // device (or managed) memory: what the batch projection may read and write
@@ -833,6 +855,50 @@ bool is_device_memory(const void *ptr)
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.isManaged;
+}
+
+// The host single-item backward calls: cam, the arguments (`given`: all of those `names` lists are non-NULL), updated; then `item`
+// (it returns the flag word), reported through the optional `flags`.
+template <class Item>
+zoic_status backward_item(const zoic_camera *cam, bool given, const char *names, uint32_t *flags, Item item)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (!given) return fail(ZOIC_ERR_INVALID_ARGUMENT, std::string(names) + " must be non-NULL");
+    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
+    const uint32_t f = item();
+    if (flags) *flags = f;
+    return ZOIC_OK;
+}
+
+struct DevicePointer {
+    const char *name;
+    const void *p;
+    unsigned align;
+    bool optional = false;
+};
+
+// The batch backward calls: the camera, n == 0 (OK before any pointer is looked at), every pointer's NULL / alignment check, the
+// device, every given pointer's memory type, and only then `launch` (it returns the launcher's rc).  Nothing is launched and no output
+// touched on any error.
+template <class Launch>
+zoic_status backward_batch(zoic_camera *cam, uint64_t n, std::initializer_list<DevicePointer> ptrs, Launch launch)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    for (const DevicePointer &a : ptrs)
+        if (zoic_status s = check_pointer(a.name, a.p, a.align, a.optional)) return s;
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    for (const DevicePointer &a : ptrs) {
+        if (!a.p || is_device_memory(a.p)) continue;
+        std::string names;   // "d_rays, d_screen and d_flags"
+        for (const DevicePointer *q = ptrs.begin(); q != ptrs.end(); ++q) {
+            if (q != ptrs.begin()) names += (q + 1 == ptrs.end()) ? " and " : ", ";
+            names += q->name;
+        }
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, names + " must be device memory");
+    }
+    return launch_status(launch());
 }
 
 }  // namespace
@@ -1190,9 +1256,9 @@ zoic_status zoic_create_rays_device(zoic_camera *cam, uint64_t n, const float *d
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
     if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
-    if (reinterpret_cast<uintptr_t>(d_samples) & 15u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be 16-byte aligned");
-    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (zoic_status s = check_pointer("d_samples", d_samples, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     return launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, reinterpret_cast<RayRecord *>(d_rays), static_cast<hipStream_t>(stream));
@@ -1334,10 +1400,10 @@ zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const fl
     static_assert(sizeof(zoic_ray_differential) == 48, "zoic_ray_differential layout");
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
-    if (!d_samples || (reinterpret_cast<uintptr_t>(d_samples) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be non-NULL and 16-byte aligned");
-    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_out must be non-NULL and 16-byte aligned");
+    if (zoic_status s = check_pointer("d_samples", d_samples, 16)) return s;
+    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
+    if (zoic_status s = check_pointer("d_out", d_out, 16)) return s;
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1346,10 +1412,8 @@ zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const fl
         ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
         return ZOIC_OK;
     }
-    const int rc = launch_ray_differentials(model, cam->kolb, cam->thin, cam->bokehDev, d_samples, d_rng_states, ray_index_base, n,
-                                            reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy, reinterpret_cast<float *>(d_out), st);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return launch_status(launch_ray_differentials(model, cam->kolb, cam->thin, cam->bokehDev, d_samples, d_rng_states, ray_index_base, n,
+                                                  reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy, reinterpret_cast<float *>(d_out), st));
 }
 
 zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
@@ -1358,10 +1422,10 @@ zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
     if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
-    if (reinterpret_cast<uintptr_t>(d_samples) & 15u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be 16-byte aligned");
-    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
-    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (zoic_status s = check_pointer("d_samples", d_samples, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_wavelengths", d_wavelengths, 4)) return s;
+    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1369,16 +1433,12 @@ zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const
     if (cam->params.p.lensModel != ZOIC_RAYTRACED) {
         // THINLENS (and NONE's error): the records of zoic_create_rays_device, then the rows of invalid wavelengths rejected
         if (zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, rays, st)) return s;
-        const int rc = launch_spectral_reject(d_wavelengths, n, rays, cam->dCounters, cam->thin.useDof != 0, st);
-        if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-        return ZOIC_OK;
+        return launch_status(launch_spectral_reject(d_wavelengths, n, rays, cam->dCounters, cam->thin.useDof != 0, st));
     }
     SpectralTable W;
     fill_spectral(cam, W);
-    const int rc = launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, rays,
-                                        cam->dCounters, cam->kernel_mode(), st);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return launch_status(launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, rays,
+                                              cam->dCounters, cam->kernel_mode(), st));
 }
 
 zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples, const float *d_wavelengths,
@@ -1392,10 +1452,10 @@ zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t 
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
     if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
-    if (reinterpret_cast<uintptr_t>(d_samples) & 15u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be 16-byte aligned");
-    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
-    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
+    if (zoic_status s = check_pointer("d_samples", d_samples, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_wavelengths", d_wavelengths, 4)) return s;
+    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1418,16 +1478,14 @@ zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t 
         const hipError_t re = hipEventRecord(H.done, st);
         if (re == hipSuccess) H.recorded = true;
         if (s != ZOIC_OK) return s;
-        if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
+        if (rc != 0) return launch_status(rc);
         ZOIC_HIP(re);
         return ZOIC_OK;
     }
     SpectralTable W;
     fill_spectral(cam, W);
-    const int rc = launch_kolb_hero(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, k, rays,
-                                    cam->dCounters, cam->kernel_mode(), st);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return launch_status(launch_kolb_hero(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, k, rays,
+                                          cam->dCounters, cam->kernel_mode(), st));
 }
 
 zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
@@ -1437,12 +1495,12 @@ zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n,
     static_assert(sizeof(zoic_vec3) == 12, "zoic_vec3 layout");
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
-    if (!d_samples || (reinterpret_cast<uintptr_t>(d_samples) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples must be non-NULL and 16-byte aligned");
-    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
-    if (d_rng_states && (reinterpret_cast<uintptr_t>(d_rng_states) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rng_states must be 16-byte aligned");
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_out must be non-NULL and 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_chromatic) & 7u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_chromatic must be 8-byte aligned");
+    if (zoic_status s = check_pointer("d_samples", d_samples, 16)) return s;
+    if (zoic_status s = check_pointer("d_wavelengths", d_wavelengths, 4)) return s;
+    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
+    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
+    if (zoic_status s = check_pointer("d_out", d_out, 16)) return s;
+    if (zoic_status s = check_pointer("d_chromatic", d_chromatic, 8, true)) return s;
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1454,11 +1512,9 @@ zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n,
     }
     SpectralTable W;
     fill_spectral(cam, W);
-    const int rc = launch_ray_differentials_spectral(model, cam->kolb, W, cam->thin, cam->bokehDev, d_samples, d_wavelengths, d_rng_states,
-                                                     ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy,
-                                                     reinterpret_cast<float *>(d_out), reinterpret_cast<float *>(d_chromatic), st);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return launch_status(launch_ray_differentials_spectral(model, cam->kolb, W, cam->thin, cam->bokehDev, d_samples, d_wavelengths,
+                                                           d_rng_states, ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays), dsx,
+                                                           dsy, reinterpret_cast<float *>(d_out), reinterpret_cast<float *>(d_chromatic), st));
 }
 
 int zoic_camera_get_dispersion(const zoic_camera *cam, int capacity, float *ior_d, float *abbe, float *cauchy_b_out)
@@ -1926,184 +1982,92 @@ zoic_status zoic_camera_set_reverse_projection(zoic_camera *cam, int enable)
 
 zoic_status zoic_project_point(const zoic_camera *cam, const zoic_vec3 *Po, float *Ps, uint32_t *flags)
 {
-    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
-    if (!Po || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "Po and Ps must be non-NULL");
-    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
-    const uint32_t f = project_point(cam->reverse, Po->x, Po->y, Po->z, Ps[0], Ps[1]);
-    if (flags) *flags = f;
-    return ZOIC_OK;
+    return backward_item(cam, Po && Ps, "Po and Ps", flags, [&] { return project_point(cam->reverse, Po->x, Po->y, Po->z, Ps[0], Ps[1]); });
 }
 
 zoic_status zoic_project_points_device(zoic_camera *cam, uint64_t n, const float *d_points, float *d_screen, uint32_t *d_flags, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_points || (reinterpret_cast<uintptr_t>(d_points) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points must be non-NULL and 4-byte aligned");
-    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
-    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    if (!is_device_memory(d_points) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points, d_screen and d_flags must be device memory");
-    const int rc = launch_project_points(cam->reverse, d_points, n, d_screen, d_flags, stream);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return backward_batch(cam, n, {{"d_points", d_points, 4}, {"d_screen", d_screen, 8}, {"d_flags", d_flags, 4, true}},
+                          [&] { return launch_project_points(cam->reverse, d_points, n, d_screen, d_flags, stream); });
 }
 
 zoic_status zoic_trace_back_ray(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps, uint32_t *flags)
 {
-    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
-    if (!origin || !dir || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir and Ps must be non-NULL");
-    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
-    const uint32_t f = trace_back_ray(cam->traceBack, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0], Ps[1]);
-    if (flags) *flags = f;
-    return ZOIC_OK;
+    return backward_item(cam, origin && dir && Ps, "origin, dir and Ps", flags, [&] {
+        return trace_back_ray(cam->traceBack, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0], Ps[1]);
+    });
 }
 
 zoic_status zoic_trace_back_rays_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_screen, uint32_t *d_flags, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
-    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
-    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    if (!is_device_memory(d_rays) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_screen and d_flags must be device memory");
-    const int rc = launch_trace_back(cam->traceBack, d_rays, n, d_screen, d_flags, stream);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return backward_batch(cam, n, {{"d_rays", d_rays, 16}, {"d_screen", d_screen, 8}, {"d_flags", d_flags, 4, true}},
+                          [&] { return launch_trace_back(cam->traceBack, d_rays, n, d_screen, d_flags, stream); });
 }
 
 zoic_status zoic_project_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, float *Ps, uint32_t *flags)
 {
-    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
-    if (!Po || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "Po and Ps must be non-NULL");
-    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
-    BackwardDispersion D;
-    fill_backward(cam, D);
-    const uint32_t f = project_point_spectral(cam->reverse, D, wavelength_nm, Po->x, Po->y, Po->z, Ps[0], Ps[1]);
-    if (flags) *flags = f;
-    return ZOIC_OK;
+    return backward_item(cam, Po && Ps, "Po and Ps", flags, [&] {
+        return project_point_spectral(cam->reverse, backward_dispersion(cam), wavelength_nm, Po->x, Po->y, Po->z, Ps[0], Ps[1]);
+    });
 }
 
 zoic_status zoic_project_points_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points, const float *d_wavelengths, float *d_screen,
                                                 uint32_t *d_flags, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_points || (reinterpret_cast<uintptr_t>(d_points) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points must be non-NULL and 4-byte aligned");
-    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
-    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
-    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    if (!is_device_memory(d_points) || !is_device_memory(d_wavelengths) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_points, d_wavelengths, d_screen and d_flags must be device memory");
-    BackwardDispersion D;
-    fill_backward(cam, D);
-    const int rc = launch_project_points_spectral(cam->reverse, D, d_points, d_wavelengths, n, d_screen, d_flags, stream);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return backward_batch(
+        cam, n, {{"d_points", d_points, 4}, {"d_wavelengths", d_wavelengths, 4}, {"d_screen", d_screen, 8}, {"d_flags", d_flags, 4, true}},
+        [&] { return launch_project_points_spectral(cam->reverse, backward_dispersion(cam), d_points, d_wavelengths, n, d_screen, d_flags, stream); });
 }
 
 zoic_status zoic_trace_back_ray_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm, float *Ps,
                                          uint32_t *flags)
 {
-    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
-    if (!origin || !dir || !Ps) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir and Ps must be non-NULL");
-    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
-    BackwardDispersion D;
-    fill_backward(cam, D);
-    const uint32_t f = trace_back_ray_spectral(cam->traceBack, D, wavelength_nm, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0],
-                                               Ps[1]);
-    if (flags) *flags = f;
-    return ZOIC_OK;
+    return backward_item(cam, origin && dir && Ps, "origin, dir and Ps", flags, [&] {
+        return trace_back_ray_spectral(cam->traceBack, backward_dispersion(cam), wavelength_nm, origin->x, origin->y, origin->z, dir->x, dir->y,
+                                       dir->z, Ps[0], Ps[1]);
+    });
 }
 
 zoic_status zoic_trace_back_rays_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths, float *d_screen,
                                                  uint32_t *d_flags, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
-    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
-    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
-    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    if (!is_device_memory(d_rays) || !is_device_memory(d_wavelengths) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)))
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_wavelengths, d_screen and d_flags must be device memory");
-    BackwardDispersion D;
-    fill_backward(cam, D);
-    const int rc = launch_trace_back_spectral(cam->traceBack, D, d_rays, d_wavelengths, n, d_screen, d_flags, stream);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return backward_batch(
+        cam, n, {{"d_rays", d_rays, 16}, {"d_wavelengths", d_wavelengths, 4}, {"d_screen", d_screen, 8}, {"d_flags", d_flags, 4, true}},
+        [&] { return launch_trace_back_spectral(cam->traceBack, backward_dispersion(cam), d_rays, d_wavelengths, n, d_screen, d_flags, stream); });
 }
 
 zoic_status zoic_trace_back_ray_jacobian(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps, uint32_t *flags, float *J)
 {
-    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
-    if (!origin || !dir || !Ps || !J) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir, Ps and J must be non-NULL");
-    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
-    const uint32_t f = trace_back_ray_jacobian(cam->traceBack, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0], Ps[1], J);
-    if (flags) *flags = f;
-    return ZOIC_OK;
+    return backward_item(cam, origin && dir && Ps && J, "origin, dir, Ps and J", flags, [&] {
+        return trace_back_ray_jacobian(cam->traceBack, origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, Ps[0], Ps[1], J);
+    });
 }
 
 zoic_status zoic_trace_back_jacobian_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_screen, uint32_t *d_flags,
                                             float *d_jacobian, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
-    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
-    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
-    if (!d_jacobian || (reinterpret_cast<uintptr_t>(d_jacobian) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_jacobian must be non-NULL and 16-byte aligned");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    if (!is_device_memory(d_rays) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)) || !is_device_memory(d_jacobian))
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_screen, d_flags and d_jacobian must be device memory");
-    const int rc = launch_trace_back_jacobian(cam->traceBack, d_rays, n, d_screen, d_flags, d_jacobian, stream);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return backward_batch(cam, n, {{"d_rays", d_rays, 16}, {"d_screen", d_screen, 8}, {"d_flags", d_flags, 4, true}, {"d_jacobian", d_jacobian, 16}},
+                          [&] { return launch_trace_back_jacobian(cam->traceBack, d_rays, n, d_screen, d_flags, d_jacobian, stream); });
 }
 
 zoic_status zoic_trace_back_ray_jacobian_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm,
                                                   float *Ps, uint32_t *flags, float *J)
 {
-    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
-    if (!origin || !dir || !Ps || !J) return fail(ZOIC_ERR_INVALID_ARGUMENT, "origin, dir, Ps and J must be non-NULL");
-    if (!cam->updated) return fail(ZOIC_ERR_NOT_UPDATED, "zoic_camera_update has not succeeded yet");
-    BackwardDispersion D;
-    fill_backward(cam, D);
-    const uint32_t f = trace_back_ray_jacobian_spectral(cam->traceBack, D, wavelength_nm, origin->x, origin->y, origin->z, dir->x, dir->y,
-                                                        dir->z, Ps[0], Ps[1], J);
-    if (flags) *flags = f;
-    return ZOIC_OK;
+    return backward_item(cam, origin && dir && Ps && J, "origin, dir, Ps and J", flags, [&] {
+        return trace_back_ray_jacobian_spectral(cam->traceBack, backward_dispersion(cam), wavelength_nm, origin->x, origin->y, origin->z, dir->x,
+                                                dir->y, dir->z, Ps[0], Ps[1], J);
+    });
 }
 
 zoic_status zoic_trace_back_jacobian_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths,
                                                      float *d_screen, uint32_t *d_flags, float *d_jacobian, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays must be non-NULL and 16-byte aligned");
-    if (!d_wavelengths || (reinterpret_cast<uintptr_t>(d_wavelengths) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_wavelengths must be non-NULL and 4-byte aligned");
-    if (!d_screen || (reinterpret_cast<uintptr_t>(d_screen) & 7u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_screen must be non-NULL and 8-byte aligned");
-    if (d_flags && (reinterpret_cast<uintptr_t>(d_flags) & 3u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_flags must be 4-byte aligned");
-    if (!d_jacobian || (reinterpret_cast<uintptr_t>(d_jacobian) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_jacobian must be non-NULL and 16-byte aligned");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    if (!is_device_memory(d_rays) || !is_device_memory(d_wavelengths) || !is_device_memory(d_screen) || (d_flags && !is_device_memory(d_flags)) ||
-        !is_device_memory(d_jacobian))
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_rays, d_wavelengths, d_screen, d_flags and d_jacobian must be device memory");
-    BackwardDispersion D;
-    fill_backward(cam, D);
-    const int rc = launch_trace_back_jacobian_spectral(cam->traceBack, D, d_rays, d_wavelengths, n, d_screen, d_flags, d_jacobian, stream);
-    if (rc != 0) return fail(ZOIC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(static_cast<hipError_t>(rc)));
-    return ZOIC_OK;
+    return backward_batch(cam, n, {{"d_rays", d_rays, 16}, {"d_wavelengths", d_wavelengths, 4}, {"d_screen", d_screen, 8},
+                                   {"d_flags", d_flags, 4, true}, {"d_jacobian", d_jacobian, 16}},
+                          [&] {
+                              return launch_trace_back_jacobian_spectral(cam->traceBack, backward_dispersion(cam), d_rays, d_wavelengths, n,
+                                                                         d_screen, d_flags, d_jacobian, stream);
+                          });
 }
 
 zoic_status zoic_host_alloc(size_t bytes, void **out)

@@ -1,13 +1,16 @@
-// reverse.hip -- the batch reverse projection (reverse.hpp): one point per lane.
+// reverse.hip -- the batch reverse projection (reverse.hpp) and the same at a wavelength per point (backward_spectral.hpp): two
+// kernels, one point per lane.
 //
 // Mapping: wave64, 256-lane workgroups, a grid of at most kRevGridCap workgroups; a batch larger than one grid's worth (a slab of
-// kRevGridCap x 256 points) is walked slab by slab by the same lanes.  The ReverseTable arrives by value as a kernel argument: the
-// interface loop's index is wave-uniform, so every table read is a scalar load.  No LDS, no scratch.  A lane reads its packed
-// float3 (three dword loads; a wave's 768 bytes are contiguous), runs the search of project_point -- the lanes of a wave loop
-// until the last of them has converged -- and writes one float2 and, if asked, one flag word.
+// kRevGridCap x 256 points) is walked slab by slab by the same lanes.  The ReverseTable (and, spectral, the BackwardDispersion)
+// arrives by value as a kernel argument: the interface loops' index is wave-uniform, so every table read is a scalar load (the
+// dispersion entry: one 8-byte load).  No LDS, no scratch.  A lane reads its packed float3 (three dword loads; a wave's 768 bytes are
+// contiguous) and, spectral, one more coalesced dword, its wavelength; runs the search of project_point -- the lanes of a wave loop
+// until the last of them has converged; spectral: dl and the index in front of the stop once, and in every pass of the search one
+// index and one division per interface on top of the d-line pass -- and writes one float2 and, if asked, one flag word.
 #include <hip/hip_runtime.h>
 
-#include "reverse.hpp"
+#include "backward_spectral.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 
@@ -17,29 +20,61 @@ namespace {
 constexpr int kRevBlock = 256;
 constexpr uint64_t kRevGridCap = 2048;
 
-}  // namespace
+dim3 rev_grid(uint64_t n)
+{
+    const uint64_t blocks = (n + kRevBlock - 1) / kRevBlock;
+    return dim3(static_cast<uint32_t>(blocks < kRevGridCap ? blocks : kRevGridCap));
+}
 
-// budget: 0 scratch, 0 spills
-__global__ __launch_bounds__(kRevBlock) void project_points_kernel(const ReverseTable T, const float *__restrict__ points, uint64_t n,
-                                                                   float2 *__restrict__ screen, uint32_t *__restrict__ flags)
+// the grid-stride walk of the two kernels: project(i, px, py, pz, sx, sy) returns point i's flag word
+template <class Project>
+__device__ __forceinline__ void rev_walk(const float *__restrict__ points, uint64_t n, float2 *__restrict__ screen, uint32_t *__restrict__ flags,
+                                         Project project)
 {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kRevBlock;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kRevBlock + threadIdx.x; i < n; i += stride) {
         const float *p = points + i * 3u;
         float sx, sy;
-        const uint32_t f = project_point(T, p[0], p[1], p[2], sx, sy);
+        const uint32_t f = project(i, p[0], p[1], p[2], sx, sy);
         screen[i] = make_float2(sx, sy);
         if (flags) flags[i] = f;
     }
 }
 
+}  // namespace
+
+// budget (both): 0 scratch, 0 spills; the spectral projection at most 64 VGPRs (8 waves per SIMD)
+__global__ __launch_bounds__(kRevBlock) void project_points_kernel(const ReverseTable T, const float *__restrict__ points, uint64_t n,
+                                                                   float2 *__restrict__ screen, uint32_t *__restrict__ flags)
+{
+    rev_walk(points, n, screen, flags, [&](uint64_t, float px, float py, float pz, float &sx, float &sy) {
+        return project_point(T, px, py, pz, sx, sy);
+    });
+}
+
+__global__ __launch_bounds__(kRevBlock) void project_points_spectral_kernel(const ReverseTable T, const BackwardDispersion D,
+                                                                            const float *__restrict__ points, const float *__restrict__ lambda,
+                                                                            uint64_t n, float2 *__restrict__ screen, uint32_t *__restrict__ flags)
+{
+    rev_walk(points, n, screen, flags, [&](uint64_t i, float px, float py, float pz, float &sx, float &sy) {
+        return project_point_spectral(T, D, lambda[i], px, py, pz, sx, sy);
+    });
+}
+
 int launch_project_points(const ReverseTable &T, const float *d_points, uint64_t n, float *d_screen, uint32_t *d_flags, void *stream)
 {
     if (n == 0) return 0;
-    const uint64_t blocks = (n + kRevBlock - 1) / kRevBlock;
-    const dim3 grid(static_cast<uint32_t>(blocks < kRevGridCap ? blocks : kRevGridCap));
-    hipLaunchKernelGGL(project_points_kernel, grid, dim3(kRevBlock), 0, static_cast<hipStream_t>(stream), T, d_points, n,
+    hipLaunchKernelGGL(project_points_kernel, rev_grid(n), dim3(kRevBlock), 0, static_cast<hipStream_t>(stream), T, d_points, n,
                        reinterpret_cast<float2 *>(d_screen), d_flags);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_project_points_spectral(const ReverseTable &T, const BackwardDispersion &D, const float *d_points, const float *d_lambda,
+                                   uint64_t n, float *d_screen, uint32_t *d_flags, void *stream)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(project_points_spectral_kernel, rev_grid(n), dim3(kRevBlock), 0, static_cast<hipStream_t>(stream), T, D, d_points,
+                       d_lambda, n, reinterpret_cast<float2 *>(d_screen), d_flags);
     return static_cast<int>(hipGetLastError());
 }
 

@@ -50,6 +50,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "backward_tables.hpp"
 #include "tables.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -317,12 +318,7 @@ inline void fill_reverse_table(ReverseTable &T, int model, float tanFov, int cou
     T.halfSensor = sensorWidth * 0.5f;
     T.invHalfSensor = 1.0f / T.halfSensor;
     float vtx[kMaxSurfaces];
-    float summed = 0.0f;   // computeLensCenters, zoic.cpp:963-969
-    for (int i = 0; i < count; ++i) {
-        summed = (i == 0) ? thickness[0] : summed + thickness[i];
-        vtx[i] = summed;
-    }
-    const float userAperture2 = userApertureRadius * userApertureRadius;
+    backward_vertices(count, thickness, vtx);
     // paraxial entrance pupil: a ray from the stop's centre towards the front
     const double u0 = 0.1;
     double y = 0.0, u = u0, z = vtx[apertureElement];
@@ -347,12 +343,7 @@ inline void fill_reverse_table(ReverseTable &T, int model, float tanFov, int cou
         const float front = (i + 1 < count) ? ior[i + 1] : 1.0f;
         S.etaF = ior[i] / front;
         S.etaR = front / ior[i];
-        // Surface::housing2 (lens_system.cpp fill_surfaces): the largest f32 <= (aperture / 2)^2, at the stop also <= userApertureRadius^2
-        const double half = static_cast<double>(aperture[i]) * 0.5, lim = half * half;
-        float h = static_cast<float>(lim);
-        if (static_cast<double>(h) > lim) h = std::nextafterf(h, -INFINITY);
-        if (i == apertureElement && userAperture2 < h) h = userAperture2;
-        S.housing2 = h;
+        S.housing2 = backward_housing2(aperture[i], i == apertureElement, userApertureRadius);
     }
     T.frontRadius = std::sqrt(T.surf[0].housing2);
 }

@@ -50,6 +50,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "backward_tables.hpp"
 #include "tables.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -127,10 +128,23 @@ struct TbDLine {
     ZOIC_HD float eta(int, const TbSurface &S) { return S.eta; }
 };
 
-// the trace-back of one ray: returns the flag word, writes sx, sy
-template <class Medium = TbDLine>
-ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy,
-                                Medium M = Medium())
+// What rides along with the trace: tb_trace calls these five members at fixed points of the one primal sequence, so whatever they
+// compute, Ps and flags are the same operations on the same operands.  TbNoTangents carries nothing (trace_back_ray);
+// TbFourTangents (traceback_jacobian.hpp) carries the four tangents of the Jacobian.
+struct TbNoTangents {
+    ZOIC_HD void line(float, float, float) {}                          // (dx, dy, 1 / dz): the direction has passed its guards
+    ZOIC_HD void thin(const TraceBackTable &, float, float) {}         // (T, s, sf): THINLENS, Ps is written
+    ZOIC_HD void seed(float, float, float) {}                          // (u): at the front vertex plane, before the first interface
+    ZOIC_HD void interface(float, float, float, float, float, float, float, float, float, float, float, float) {}
+                                                                       // (c, t, n, cosi, eta, sqrt(k2), g, u): u BEFORE the refraction
+    ZOIC_HD void sensor(const TraceBackTable &, float, float, float, float, float, float, float) {}
+                                                                       // (T, t, 1 / u.z, u.x, u.y, s, im, il): Ps and flags are settled
+};
+
+// the trace-back of one ray with G riding along: returns the flag word, writes sx, sy
+template <class Medium, class Tangents>
+ZOIC_HD uint32_t tb_trace(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy, Medium &M,
+                          Tangents &G)
 {
     sx = 0.0f; sy = 0.0f;
     if (T.model != 0 && T.model != 1) return kTbModel << kTbReasonShift;
@@ -147,6 +161,7 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
     float ux = ax * il, uy = ay * il, uz = az * il;
     const float idz = tb_rcp(dz);
     if (!tb_finite(im, il, idz)) return kTbNonFinite << kTbReasonShift;
+    G.line(dx, dy, idz);
 
     if (T.model == 0) {   // THINLENS (record frame: the lens in z = 0, the scene at z < 0)
         if (!(oz <= 0.0f)) return kTbAway << kTbReasonShift;
@@ -163,6 +178,7 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
         const float x = fx * T.invFocalTan, y = fy * T.invFocalTan;
         if (!(fabsf(x) <= kTbMaxFloat && fabsf(y) <= kTbMaxFloat)) return kTbNonFinite << kTbReasonShift;
         sx = x + 0.0f; sy = y + 0.0f;   // (+0 for a zero)
+        G.thin(T, s, sf);
         return kTbTraced;
     }
 
@@ -181,6 +197,7 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
     const float s = (oz + T.zFront) * idz;
     float x = fmaf(s, dx, -ox), y = fmaf(s, dy, -oy), z = fmaf(s, dz, -oz) - T.zFront;
     if (!tb_finite(x, y, z) || !(fabsf(s) <= kTbMaxFloat)) return kTbNonFinite << kTbReasonShift;
+    G.seed(ux, uy, uz);
     for (int jj = 0; jj < T.count; ++jj) {
         const int j = tb_uniform(jj);
         const TbSurface S = T.surf[j];   // the whole entry at once
@@ -208,12 +225,15 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
         const float eta = M.eta(j, S), eta2 = eta * eta;
         const float k2 = fmaf(eta2, cosi * cosi, 1.0f - eta2);
         if (!(k2 >= 0.0f)) return tb_end(kTbTir, iface);
-        const float g = fmaf(eta, cosi, -tb_sqrt(k2));
+        const float sk = tb_sqrt(k2);
+        const float g = fmaf(eta, cosi, -sk);
+        G.interface(c, t, nx, ny, nz, cosi, eta, sk, g, ux, uy, uz);   // with the ray's direction BEFORE the refraction
         ux = fmaf(eta, ux, g * nx); uy = fmaf(eta, uy, g * ny); uz = fmaf(eta, uz, g * nz);
         x = hx; y = hy; z = hz;
     }
     if (!(uz < 0.0f)) return tb_end(kTbMiss, 0);   // turned round at the rear element: no sensor point
-    const float t = (T.sensorZ - z) * tb_rcp(uz);
+    const float iuz = tb_rcp(uz);
+    const float t = (T.sensorZ - z) * iuz;
     const float px = fmaf(t, ux, x) * T.invHalfSensor, py = fmaf(t, uy, y) * T.invHalfSensor;
     if (!(fabsf(px) <= kTbMaxFloat && fabsf(py) <= kTbMaxFloat)) return kTbNonFinite << kTbReasonShift;
     sx = px + 0.0f; sy = py + 0.0f;
@@ -223,7 +243,16 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
         const float dist = fabsf(tb_sqrt(fx * fx + fy * fy));
         if (!(dist * 8.0f <= static_cast<float>(T.lutSize - 1))) flags |= kTbPastLut;
     }
+    G.sensor(T, t, iuz, ux, uy, s, im, il);
     return flags;
+}
+
+template <class Medium = TbDLine>
+ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy,
+                                Medium M = Medium())
+{
+    TbNoTangents G;
+    return tb_trace(T, ox, oy, oz, dx, dy, dz, sx, sy, M, G);
 }
 
 // Host: the table of a camera from its lens rows (trace order, rear first, after LensSystem::prepare: radius, thickness, ior,
@@ -254,12 +283,7 @@ inline void fill_traceback_table(TraceBackTable &T, int model, float tanFov, int
     T.halfSensor = sensorWidth * 0.5f;
     T.invHalfSensor = 1.0f / T.halfSensor;
     float vtx[kMaxSurfaces];
-    float summed = 0.0f;   // computeLensCenters, zoic.cpp:963-969
-    for (int i = 0; i < count; ++i) {
-        summed = (i == 0) ? thickness[0] : summed + thickness[i];
-        vtx[i] = summed;
-    }
-    const float userAperture2 = userApertureRadius * userApertureRadius;
+    backward_vertices(count, thickness, vtx);
     T.zFront = vtx[count - 1];
     T.sensorZ = static_cast<float>(static_cast<double>(originShift) - static_cast<double>(vtx[0]));
     for (int j = 0; j < count; ++j) {
@@ -269,12 +293,7 @@ inline void fill_traceback_table(TraceBackTable &T, int model, float tanFov, int
         S.curv = static_cast<float>(1.0 / static_cast<double>(radius[i]));
         const float front = (i + 1 < count) ? ior[i + 1] : 1.0f;
         S.eta = front / ior[i];
-        // Surface::housing2 (lens_system.cpp fill_surfaces): the largest f32 <= (aperture / 2)^2, at the stop also <= userApertureRadius^2
-        const double half = static_cast<double>(aperture[i]) * 0.5, lim = half * half;
-        float h = static_cast<float>(lim);
-        if (static_cast<double>(h) > lim) h = std::nextafterf(h, -INFINITY);
-        if (i == apertureElement && userAperture2 < h) h = userAperture2;
-        S.housing2 = h;
+        S.housing2 = backward_housing2(aperture[i], i == apertureElement, userApertureRadius);
     }
     T.capSlack = kTbCapSlack * std::sqrt(T.surf[0].housing2);
 }

@@ -21,9 +21,9 @@
 //   Overflow   J is not clipped: for a ray of an extreme scale an entry may be +-inf; an entry that is not a number is written as the
 //              one quiet NaN 0x7fc00000 (a NaN's sign and payload are the only bits the host and the device may disagree on).
 //
-// Ps and flags are trace_back_ray's bit for bit, for every input: the primal operations below restate traceback.hpp's operation
-// for operation (as hero.hip restates spectral.hip); tests/test_traceback_jacobian_cpu.py holds the two together on every ray set the
-// trace-back's own tests use.
+// Ps and flags are trace_back_ray's bit for bit, for every input, by construction: both run the one primal sequence, traceback.hpp's
+// tb_trace, and the tangents below only ride along with it (its Tangents parameter) -- they read the trace's values at five fixed
+// points and write J, never a value the trace reads.
 //
 // Tangents.  The rays through the lens are a 4-dimensional manifold, and the start step is analytic, so FOUR tangents are carried
 // through the interfaces (24 live registers, not 36) and composed with the start step's 4 x 6 at the end:
@@ -73,98 +73,42 @@ ZOIC_HD void tbj_zero(float *J)
     for (int k = 0; k < 12; ++k) J[k] = 0.0f;
 }
 
-// the trace-back of one ray and its Jacobian: returns the flag word, writes sx, sy and J[12]
-template <class Medium = TbDLine>
-ZOIC_HD uint32_t trace_back_ray_jacobian(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx,
-                                         float &sy, float *J, Medium M = Medium())
-{
-    sx = 0.0f; sy = 0.0f;
-    tbj_zero(J);
-    // ---- traceback.hpp's operations, one for one, from here to the interface loop
-    if (T.model != 0 && T.model != 1) return kTbModel << kTbReasonShift;
-    if (T.model == 0 && !T.useDof) return kTbModel << kTbReasonShift;
-    if (T.model == 1 && !T.domain) return kTbOutsideDomain << kTbReasonShift;
-    if (!tb_finite(ox, oy, oz) || !tb_finite(dx, dy, dz)) return kTbNonFinite << kTbReasonShift;
-    const float m = fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz)));
-    if (!(m > 0.0f)) return kTbNonFinite << kTbReasonShift;
-    if (!(dz < 0.0f)) return kTbAway << kTbReasonShift;
-    const float im = tb_rcp(m);
-    const float ax = dx * im, ay = dy * im, az = dz * im;
-    const float il = tb_rcp(tb_sqrt(fmaf(ax, ax, fmaf(ay, ay, az * az))));
-    float ux = ax * il, uy = ay * il, uz = az * il;
-    const float idz = tb_rcp(dz);
-    if (!tb_finite(im, il, idz)) return kTbNonFinite << kTbReasonShift;
-    const float sxz = dx * idz, syz = dy * idz;   // the line's slopes dx / dz, dy / dz (tangents only)
+// The four tangents riding along with tb_trace (traceback.hpp's Tangents): the slopes of the line, the basis across u, and D[4].
+struct TbFourTangents {
+    float *J;
+    float sxz, syz;                          // the line's slopes dx / dz, dy / dz
+    float e1x, e1y, e1z, e2x, e2y, e2z;
+    TbTangent D[4];
 
-    if (T.model == 0) {   // THINLENS
-        if (!(oz <= 0.0f)) return kTbAway << kTbReasonShift;
-        const float s = -oz * idz;
-        const float px = fmaf(s, dx, ox), py = fmaf(s, dy, oy);
-        if (!tb_finite(s, px, py)) return kTbNonFinite << kTbReasonShift;
-        if (!(fmaf(px, px, py * py) <= T.aperture2)) return tb_end(kTbClipped, 0);
-        if (T.ovOn) {
-            const float vx = fmaf(ux, T.ovDistance, -px), vy = fmaf(uy, T.ovDistance, -py);
-            if (!(tb_sqrt(fmaf(vx, vx, vy * vy)) < T.ovLimit)) return tb_end(kTbClipped, 0);
-        }
-        const float sf = -T.focalDistance * idz;
-        const float fx = fmaf(sf, dx, px), fy = fmaf(sf, dy, py);
-        const float x = fx * T.invFocalTan, y = fy * T.invFocalTan;
-        if (!(fabsf(x) <= kTbMaxFloat && fabsf(y) <= kTbMaxFloat)) return kTbNonFinite << kTbReasonShift;
-        sx = x + 0.0f; sy = y + 0.0f;
-        // the closed form: tau = -(oz + fd) / dz
+    ZOIC_HD void line(float dx, float dy, float idz) { sxz = dx * idz; syz = dy * idz; }
+
+    // THINLENS, the closed form: tau = -(oz + fd) / dz
+    ZOIC_HD void thin(const TraceBackTable &T, float s, float sf)
+    {
         const float I = T.invFocalTan;
         const float tauI = (s + sf) * I;
         J[0] = I;                        J[7] = I;
         J[2] = tbj_number(-sxz * I);     J[8] = tbj_number(-syz * I);
         J[3] = tbj_number(tauI);         J[10] = tbj_number(tauI);
         J[5] = tbj_number(-tauI * sxz);  J[11] = tbj_number(-tauI * syz);
-        return kTbTraced;
     }
-
-    {
-        const TbSurface &S0 = T.surf[0];
-        const float zq = -oz - T.zFront;
-        const float h2 = fminf(fmaf(ox, ox, oy * oy), S0.housing2);
-        const float c = S0.curv;
-        const float e = fmaxf(fmaf(-c * c, h2, 1.0f), 0.0f);
-        const float cap = -(c * h2) * tb_rcp(1.0f + tb_sqrt(e));
-        if (!(zq >= cap - T.capSlack)) return kTbAway << kTbReasonShift;
-    }
-    const float s = (oz + T.zFront) * idz;
-    float x = fmaf(s, dx, -ox), y = fmaf(s, dy, -oy), z = fmaf(s, dz, -oz) - T.zFront;
-    if (!tb_finite(x, y, z) || !(fabsf(s) <= kTbMaxFloat)) return kTbNonFinite << kTbReasonShift;
 
     // the four seeds: x, y, and u towards e1, e2 (u.z < 0)
-    const float ba = tb_rcp(1.0f - uz), bb = ux * uy * ba;
-    const float e1x = fmaf(-ux * ux, ba, 1.0f), e1y = -bb, e1z = ux;
-    const float e2x = bb, e2y = fmaf(uy * uy, ba, -1.0f), e2z = -uy;
-    TbTangent D[4] = {{1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f},
-                      {0.0f, 0.0f, 0.0f, e1x, e1y, e1z}, {0.0f, 0.0f, 0.0f, e2x, e2y, e2z}};
+    ZOIC_HD void seed(float ux, float uy, float uz)
+    {
+        const float ba = tb_rcp(1.0f - uz), bb = ux * uy * ba;
+        e1x = fmaf(-ux * ux, ba, 1.0f); e1y = -bb; e1z = ux;
+        e2x = bb; e2y = fmaf(uy * uy, ba, -1.0f); e2z = -uy;
+        D[0] = TbTangent{1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        D[1] = TbTangent{0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        D[2] = TbTangent{0.0f, 0.0f, 0.0f, e1x, e1y, e1z};
+        D[3] = TbTangent{0.0f, 0.0f, 0.0f, e2x, e2y, e2z};
+    }
 
-    for (int jj = 0; jj < T.count; ++jj) {
-        const int j = tb_uniform(jj);
-        const TbSurface S = T.surf[j];
-        const int iface = T.count - 1 - jj;
-        const float c = S.curv;
-        const float zr = z + S.dz;
-        const float F = fmaf(c, fmaf(x, x, fmaf(y, y, zr * zr)), zr + zr);
-        const float B = fmaf(c, fmaf(x, ux, fmaf(y, uy, zr * uz)), uz);
-        const float disc = fmaf(-c, F, B * B);
-        if (!(disc >= 0.0f)) return tb_end(kTbMiss, iface);
-        const float sq = tb_sqrt(disc);
-        const bool near = B <= 0.0f;
-        const float rden = tb_rcp(near ? B - sq : c);
-        const float t = (near ? -F : -(B + sq)) * rden;
-        const float hx = fmaf(t, ux, x), hy = fmaf(t, uy, y), hz = fmaf(t, uz, zr);
-        if (!(fmaf(hx, hx, hy * hy) <= S.housing2)) return tb_end(hx == hx && hy == hy ? kTbClipped : kTbMiss, iface);
-        const float nx = c * hx, ny = c * hy, nz = fmaf(c, hz, 1.0f);
-        const float cosi = -fmaf(ux, nx, fmaf(uy, ny, uz * nz));
-        const float eta = M.eta(j, S), eta2 = eta * eta;
-        const float k2 = fmaf(eta2, cosi * cosi, 1.0f - eta2);
-        if (!(k2 >= 0.0f)) return tb_end(kTbTir, iface);
-        const float sk = tb_sqrt(k2);
-        const float g = fmaf(eta, cosi, -sk);
-        // the tangents, with the ray's direction BEFORE the refraction
+    // one interface, with the ray's direction u BEFORE the refraction
+    ZOIC_HD void interface(float c, float t, float nx, float ny, float nz, float cosi, float eta, float sk, float g, float ux, float uy,
+                           float uz)
+    {
         const float icos = tb_rcp(cosi);                // n . u = -cosi
         const float gc = -(eta * g) * tb_rcp(sk);       // dg / dcos
 #pragma unroll
@@ -181,47 +125,45 @@ ZOIC_HD uint32_t trace_back_ray_jacobian(const TraceBackTable &T, float ox, floa
             d.uz = fmaf(eta, d.uz, fmaf(dg, nz, g * dnz));
             d.x = dhx; d.y = dhy; d.z = dhz;
         }
-        ux = fmaf(eta, ux, g * nx); uy = fmaf(eta, uy, g * ny); uz = fmaf(eta, uz, g * nz);
-        x = hx; y = hy; z = hz;
-    }
-    if (!(uz < 0.0f)) return tb_end(kTbMiss, 0);
-    const float iuz = tb_rcp(uz);
-    const float t = (T.sensorZ - z) * iuz;
-    const float px = fmaf(t, ux, x) * T.invHalfSensor, py = fmaf(t, uy, y) * T.invHalfSensor;
-    if (!(fabsf(px) <= kTbMaxFloat && fabsf(py) <= kTbMaxFloat)) return kTbNonFinite << kTbReasonShift;
-    sx = px + 0.0f; sy = py + 0.0f;
-    uint32_t flags = kTbTraced;
-    if (T.useLUT) {
-        const float fx = sx * T.halfSensor, fy = sy * T.halfSensor;
-        const float dist = fabsf(tb_sqrt(fx * fx + fy * fy));
-        if (!(dist * 8.0f <= static_cast<float>(T.lutSize - 1))) flags |= kTbPastLut;
     }
 
-    // the sensor plane: d(sx, sy) along each of the four tangents
-    float gx[4], gy[4];
+    // the sensor plane: d(sx, sy) along each of the four tangents, then the start step's 4 x 6.  1 / |dir| = im il.
+    ZOIC_HD void sensor(const TraceBackTable &T, float t, float iuz, float ux, float uy, float s, float im, float il)
+    {
+        float gx[4], gy[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const TbTangent &d = D[k];
-        const float dt = -fmaf(t, d.uz, d.z) * iuz;
-        gx[k] = fmaf(ux, dt, fmaf(t, d.ux, d.x)) * T.invHalfSensor;
-        gy[k] = fmaf(uy, dt, fmaf(t, d.uy, d.y)) * T.invHalfSensor;
+        for (int k = 0; k < 4; ++k) {
+            const TbTangent &d = D[k];
+            const float dt = -fmaf(t, d.uz, d.z) * iuz;
+            gx[k] = fmaf(ux, dt, fmaf(t, d.ux, d.x)) * T.invHalfSensor;
+            gy[k] = fmaf(uy, dt, fmaf(t, d.uy, d.y)) * T.invHalfSensor;
+        }
+        const float kx = fmaf(gx[0], sxz, gx[1] * syz), ky = fmaf(gy[0], sxz, gy[1] * syz);   // d / d oz
+        const float ax1 = gx[2] * il * im, ax2 = gx[3] * il * im, ay1 = gy[2] * il * im, ay2 = gy[3] * il * im;
+        J[0] = tbj_number(-gx[0]);
+        J[1] = tbj_number(-gx[1]);
+        J[2] = tbj_number(kx);
+        J[3] = tbj_number(fmaf(s, gx[0], fmaf(ax1, e1x, ax2 * e2x)));
+        J[4] = tbj_number(fmaf(s, gx[1], fmaf(ax1, e1y, ax2 * e2y)));
+        J[5] = tbj_number(fmaf(-s, kx, fmaf(ax1, e1z, ax2 * e2z)));
+        J[6] = tbj_number(-gy[0]);
+        J[7] = tbj_number(-gy[1]);
+        J[8] = tbj_number(ky);
+        J[9] = tbj_number(fmaf(s, gy[0], fmaf(ay1, e1x, ay2 * e2x)));
+        J[10] = tbj_number(fmaf(s, gy[1], fmaf(ay1, e1y, ay2 * e2y)));
+        J[11] = tbj_number(fmaf(-s, ky, fmaf(ay1, e1z, ay2 * e2z)));
     }
-    // the start step's 4 x 6.  1 / |dir| = im il.
-    const float kx = fmaf(gx[0], sxz, gx[1] * syz), ky = fmaf(gy[0], sxz, gy[1] * syz);   // d / d oz
-    const float ax1 = gx[2] * il * im, ax2 = gx[3] * il * im, ay1 = gy[2] * il * im, ay2 = gy[3] * il * im;
-    J[0] = tbj_number(-gx[0]);
-    J[1] = tbj_number(-gx[1]);
-    J[2] = tbj_number(kx);
-    J[3] = tbj_number(fmaf(s, gx[0], fmaf(ax1, e1x, ax2 * e2x)));
-    J[4] = tbj_number(fmaf(s, gx[1], fmaf(ax1, e1y, ax2 * e2y)));
-    J[5] = tbj_number(fmaf(-s, kx, fmaf(ax1, e1z, ax2 * e2z)));
-    J[6] = tbj_number(-gy[0]);
-    J[7] = tbj_number(-gy[1]);
-    J[8] = tbj_number(ky);
-    J[9] = tbj_number(fmaf(s, gy[0], fmaf(ay1, e1x, ay2 * e2x)));
-    J[10] = tbj_number(fmaf(s, gy[1], fmaf(ay1, e1y, ay2 * e2y)));
-    J[11] = tbj_number(fmaf(-s, ky, fmaf(ay1, e1z, ay2 * e2z)));
-    return flags;
+};
+
+// the trace-back of one ray and its Jacobian: returns the flag word, writes sx, sy and J[12]
+template <class Medium = TbDLine>
+ZOIC_HD uint32_t trace_back_ray_jacobian(const TraceBackTable &T, float ox, float oy, float oz, float dx, float dy, float dz, float &sx,
+                                         float &sy, float *J, Medium M = Medium())
+{
+    tbj_zero(J);
+    TbFourTangents G;
+    G.J = J;
+    return tb_trace(T, ox, oy, oz, dx, dy, dz, sx, sy, M, G);
 }
 
 // the same at the ray's wavelength (nm), held fixed
@@ -236,7 +178,7 @@ ZOIC_HD uint32_t trace_back_ray_jacobian_spectral(const TraceBackTable &T, const
     return trace_back_ray_jacobian(T, ox, oy, oz, dx, dy, dz, sx, sy, J, TbSpectral{D.med, spectral_dl(lambda), 1.0f});
 }
 
-// ---- launchers (traceback_jacobian.hip) ----------------------------------------------------------------------------------
+// ---- launchers (traceback.hip) ----------------------------------------------------------------------------------
 // As launch_trace_back / launch_trace_back_spectral, with d_jacobian = n x 12 floats (16-byte aligned).  Asynchronous on `stream`.
 int launch_trace_back_jacobian(const TraceBackTable &T, const void *d_rays, uint64_t n, float *d_screen, uint32_t *d_flags, float *d_jacobian,
                                void *stream);
