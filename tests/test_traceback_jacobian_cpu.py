@@ -203,31 +203,8 @@ def accuracy(oracle_lib, name, spectral=False):
     else:
         T, lam, trace = TraceBack(info, p), None, None
         trace = T.trace
-    ref = trace(o, d)
-    cand = ref["traced"] & ~T.edge(ref)
-    Jref, ok_ref = jr.jacobian_ref(trace, o, d, s)
-    Jref5, ok_ref5 = jr.jacobian_ref(trace, o, d, s, 1e-5)
-    cand &= ok_ref & ok_ref5
-    ps, fl, J = jr.host_jacobian(cam, o, d, lam)
-    cand &= (fl & 1) == 1
-    eJ = jr.rel_error(J, np.where(cand[:, None, None], Jref, 1.0), s)
-    rows = []
-    for h in jr.YARDSTICK_STEPS:
-        Y, ok = jr.yardstick(cam, o, d, s, h, lam)
-        O, D = jr._neighbours(o, d, h * s)
-        ok64 = trace(O, D)["traced"].reshape(12, len(o)).all(0)
-        kept = cand & ok & ok64
-        if kept.sum() < 2:
-            continue
-        eY = jr.rel_error(Y[kept], Jref[kept], s)
-        rows.append(dict(h=h, kept=kept, left_out=1.0 - kept.sum() / len(o), left_out64=1.0 - (cand & ok64).sum() / len(o),
-                         y_med=float(np.median(eY)), y_p99=float(np.percentile(eY, 99)),
-                         j_med=float(np.median(eJ[kept])), j_p99=float(np.percentile(eJ[kept], 99))))
-    for r in rows:
-        print("%s%s h 2^%d: kept %d of %d (left out %.2f %%, by the f64 trace alone %.2f %%)  J med %.3g p99 %.3g | yardstick med %.3g p99 %.3g"
-              % (name, " spectral" if spectral else "", round(np.log2(r["h"])), r["kept"].sum(), len(o), 100 * r["left_out"],
-                 100 * r["left_out64"], r["j_med"], r["j_p99"], r["y_med"], r["y_p99"]))
-    _ACC[key] = dict(p=p, cam=cam, T=T, s=s, o=o, d=d, lam=lam, J=J, Jref=Jref, Jref5=Jref5, eJ=eJ, rows=rows, n=len(o), stride=stride)
+    A = jr.measure(cam, trace, T.edge, o, d, lam, s, tag=name + (" spectral" if spectral else ""))
+    _ACC[key] = dict(A, p=p, T=T, stride=stride)
     return _ACC[key]
 
 

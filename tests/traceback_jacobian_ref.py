@@ -4,8 +4,19 @@ Column scales s: s_o = the front housing radius (RAYTRACED) or apertureRadius (T
 the three of dir (the tests' directions are normalised in f64 before the cast to f32).  Errors are measured per ray as
 |(J - Jref) S|_F / |Jref S|_F with S = diag(s).
 
+Far start points.  TraceBack.trace intersects every sphere from the origin it is given: d2 = L.L - tca^2 with |L| about the distance to
+the lens, a subtraction that cancels as distance^2 in f64.  Central differences taken straight from it are useless at scene distances:
+at 3 000 cm the steps 1e-5 s and 1e-6 s disagree by 2e-3 ... 7e-2, at 1e4 cm by 3e-2 ... 0.8, and J's apparent error IS that
+disagreement.  So never difference TraceBack.trace at a far origin.  near_trace(trace, z_plane) first moves every (origin, dir) it is
+given -- each finite-difference neighbour along its OWN line -- to the plane z = z_plane just in front of the lens (front_plane), in
+f64; Ps belongs to the line, so the derivative is the same, and the trace then starts a housing radius from the front vertex whatever
+the distance.  far_scales gives the column scales for a start point k out: s_o for the origin columns, s_o / k for those of dir, so
+that a unit of every column moves the point where the line meets the lens by one housing radius.  (The dir steps are then h s_o / k
+on a unit vector: in f64 they are taken to 1e-16 / (h s_o / k) of themselves, which is why the far tests use the steps 1e-4 and 1e-5
+where the near ones use 1e-5 and 1e-6.)
+
 Also here: the yardstick -- what a caller can do without the feature, the f32 central-difference Jacobian from zoic_trace_back_ray --
-and the per-ray host calls the CPU and GPU tests share."""
+the per-ray host calls the CPU and GPU tests share, and measure(), the procedure of the accuracy tests."""
 import ctypes
 
 import numpy as np
@@ -26,6 +37,43 @@ def scales(info, params):
     else:
         s_o = float(info["apertureRadius"])
     return np.array([s_o, s_o, s_o, 1.0, 1.0, 1.0])
+
+
+def far_scales(s, k):
+    """(6,) column scales for a start point k out along the ray: s_o, s_o, s_o, s_o / k, s_o / k, s_o / k"""
+    s = np.asarray(s, np.float64)
+    return np.concatenate([s[:3], s[:3] / float(k)])
+
+
+def front_plane(T, s):
+    """z (record frame) of the plane one front housing radius s[0] in front of the front vertex of the TraceBack T: no point of it
+    lies behind the front cap, whose sag is at most the housing radius"""
+    return -(float(T.vtx[T.n - 1]) + float(s[0]))
+
+
+def near_trace(trace, z_plane):
+    """trace(O, D) with every start point first moved along its own line to the plane z = z_plane, in f64: the same Ps, without the
+    cancellation of a far origin (the module's docstring)"""
+    def moved(O, D):
+        O = np.array(O, np.float64).reshape(-1, 3)
+        D = np.array(D, np.float64).reshape(-1, 3)
+        with np.errstate(all="ignore"):
+            P = O + ((z_plane - O[:, 2]) / D[:, 2])[:, None] * D
+        return trace(P, D)
+    return moved
+
+
+def far_rays(o, d, m=1024, seed=29):
+    """m rays for the bitwise comparisons made from m of the records (o, d), evenly spread: the start point moved 30 ... 1e4 cm out
+    along the ray, every other one with dir scaled by 1e3 or 1e-3.  (origin (m,3) f32, dir (m,3) f32)"""
+    rng = np.random.default_rng(seed)
+    pick = np.linspace(0, len(o) - 1, m).astype(int)
+    u = unit_f32(d[pick]).astype(np.float64)
+    k = 10.0 ** rng.uniform(np.log10(30.0), 4.0, len(pick))
+    far = (np.asarray(o, np.float64)[pick] + k[:, None] * u).astype(F32)
+    scale = np.ones(len(pick))
+    scale[1::4], scale[3::4] = 1e3, 1e-3
+    return far, (u * scale[:, None]).astype(F32)
 
 
 def _neighbours(o, d, step):
@@ -140,3 +188,36 @@ def unit_f32(d):
     """directions normalised in f64, then cast to f32"""
     d = np.asarray(d, np.float64)
     return (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F32)
+
+
+def measure(cam, trace, edge, o, d, lam, s, ref_steps=(REF_STEP, 1e-5), steps=YARDSTICK_STEPS, tag=""):
+    """The procedure of the accuracy tests on the rays (o, d) (f32; lam: a wavelength per ray, or None) with the column scales s.
+    trace(O, D) is the f64 trace (for a far start point: through near_trace), edge(res) its edge set.  Jref is taken at ref_steps[0],
+    Jref5 at ref_steps[1]; a ray is a candidate if the f64 trace takes it back off the edge with all 24 reference neighbours, and the
+    library traces it.  Per yardstick step h a row: the rays kept there (the 12 neighbours at h s trace in f64 and in the library),
+    the share left out (and by the f64 trace alone) and the median / p99 error of the yardstick and of J on them."""
+    ref = trace(o, d)
+    cand = ref["traced"] & ~edge(ref)
+    Jref, ok_ref = jacobian_ref(trace, o, d, s, ref_steps[0])
+    Jref5, ok_ref5 = jacobian_ref(trace, o, d, s, ref_steps[1])
+    cand &= ok_ref & ok_ref5
+    ps, fl, J = host_jacobian(cam, o, d, lam)
+    cand &= (fl & 1) == 1
+    eJ = rel_error(J, np.where(cand[:, None, None], Jref, 1.0), s)
+    rows = []
+    for h in steps:
+        Y, ok = yardstick(cam, o, d, s, h, lam)
+        O, D = _neighbours(o, d, h * s)
+        ok64 = trace(O, D)["traced"].reshape(12, len(o)).all(0)
+        kept = cand & ok & ok64
+        if kept.sum() < 2:
+            continue
+        eY = rel_error(Y[kept], Jref[kept], s)
+        rows.append(dict(h=h, kept=kept, left_out=1.0 - kept.sum() / len(o), left_out64=1.0 - (cand & ok64).sum() / len(o),
+                         y_med=float(np.median(eY)), y_p99=float(np.percentile(eY, 99)),
+                         j_med=float(np.median(eJ[kept])), j_p99=float(np.percentile(eJ[kept], 99)), Y=Y))
+    for r in rows:
+        print("%s h 2^%d: kept %d of %d (left out %.2f %%, by the f64 trace alone %.2f %%)  J med %.3g p99 %.3g | yardstick med %.3g p99 %.3g"
+              % (tag, round(np.log2(r["h"])), r["kept"].sum(), len(o), 100 * r["left_out"], 100 * r["left_out64"], r["j_med"],
+                 r["j_p99"], r["y_med"], r["y_p99"]))
+    return dict(cam=cam, s=s, o=o, d=d, lam=lam, ref=ref, ps=ps, fl=fl, J=J, Jref=Jref, Jref5=Jref5, eJ=eJ, rows=rows, n=len(o))
