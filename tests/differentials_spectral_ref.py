@@ -55,6 +55,12 @@ def trace(surf, eta, o, d):
     return o, d, worst
 
 
+def min_cos_incidence(surf, eta, o, d):
+    """differentials_ref.min_cos_incidence with eta (n, count): (n,) smallest |cos i| / cos t of each ray's f64 trace at its own
+    wavelength, the conditioning of its Jacobian (trace's own arithmetic: the third thing it returns)"""
+    return trace(surf, eta, o, d)[2]
+
+
 def jacobian_fd(surf, disp, lam, half_sensor, o0, d0, h=1e-5):
     """(n,12) central differences of the flipped (O, D) w.r.t. sx and sy with L = o0.xy + d0.xy fixed, at each ray's wavelength:
     columns dOdx, dOdy, dDdx, dDdy"""

@@ -78,20 +78,35 @@ def camera(name, device=-1, precision=None):
 _RECORDS = {}
 
 
-def oracle_records(oracle_lib, name):
-    """the oracle's forward records of the frame tc.W x tc.H x tc.SPP behind lens `name` (the STRICT kernel's bits), cached and not to
-    be written to: samples (N,4), origin (N,3), dir (N,3), weight (N,)"""
+def oracle_camera(oracle_lib, name):
+    """an updated OracleCamera behind lens `name` (the caller closes it)"""
+    oc = oracle_lib.OracleCamera()
+    oc.set_lens_text(LENSES[name].text)
+    oc.update(**params(name))
+    return oc
+
+
+def _oracle_frame(oracle_lib, name):
     if name not in _RECORDS:
         s, st = tc.frame_samples()
-        oc = oracle_lib.OracleCamera()
-        oc.set_lens_text(LENSES[name].text)
-        oc.update(**params(name))
+        oc = oracle_camera(oracle_lib, name)
         r = oc.create_rays(s, rng_states=st)
-        _RECORDS[name] = s, r["origin"].T.copy(), r["dir"].T.copy(), r["weight"].copy()
+        _RECORDS[name] = s, r["origin"].T.copy(), r["dir"].T.copy(), r["weight"].copy(), r["tries"].astype(np.int64)
         oc.close()
         for a in _RECORDS[name]:
             a.setflags(write=False)
     return _RECORDS[name]
+
+
+def oracle_records(oracle_lib, name):
+    """the oracle's forward records of the frame tc.W x tc.H x tc.SPP behind lens `name` (the STRICT kernel's bits), cached and not to
+    be written to: samples (N,4), origin (N,3), dir (N,3), weight (N,)"""
+    return _oracle_frame(oracle_lib, name)[:4]
+
+
+def oracle_tries(oracle_lib, name):
+    """(N,) the try each of oracle_records' rays was accepted at (0: the sample's own lens point)"""
+    return _oracle_frame(oracle_lib, name)[4]
 
 
 _POINTS = {}
