@@ -65,32 +65,36 @@ def _arnold_inputs(s_np, dsx=1.0, dsy=1.0):
 @pytest.mark.parametrize("cfg", ["C1", "C2", "C3", "C4", "C5"])
 @pytest.mark.parametrize("precision", [PRECISION_STRICT, PRECISION_FAST])
 def test_arnold_rows_unchanged(gpu, cfg, precision):
-    """origin, dir and weight of every row are zoic_create_rays_arnold's, bit for bit; the derivative fields are the batch call's"""
+    """origin, dir and weight of every row are zoic_create_rays_arnold's, bit for bit; the derivative fields are the batch call's --
+    at the full size and at n = 257 (a partial last wave and a second wave-tile)"""
+    import torch
     p = _params(cfg)
     cam = _camera(p, precision)
-    s = _samples(N)
-    inputs = _arnold_inputs(s)
-    plain = cam.create_rays_arnold(inputs, ray_index_base=7)
-    rows = cam.create_rays_arnold(inputs, ray_index_base=7, differentials=True)
-    keep = np.r_[0:6, 18:21]
-    assert np.array_equal(rows[:, keep].view(np.uint32), plain[:, keep].view(np.uint32))
-    import torch
-    st = torch.from_numpy(s).cuda()
-    rays = cam.create_rays(st, ray_index_base=7)["rays"]
-    d = cam.ray_differentials(st, rays, ray_index_base=7).cpu().numpy()
-    assert np.array_equal(rows[:, 6:18].view(np.uint32), d.view(np.uint32))
-    # per-row dsx / dsy scale the raw columns
     rs = np.random.RandomState(3)
-    inputs2 = inputs.copy()
-    inputs2[:, 2] = rs.uniform(-2e-3, 2e-3, N).astype(np.float32)
-    inputs2[:, 3] = rs.uniform(-2e-3, 2e-3, N).astype(np.float32)
-    rows2 = cam.create_rays_arnold(inputs2, ray_index_base=7, differentials=True)
-    live = rows[:, 18] != 0
-    for cols, k in ((slice(6, 9), 2), (slice(9, 12), 3), (slice(12, 15), 2), (slice(15, 18), 3)):
-        want = (rows[:, cols] * inputs2[:, k:k + 1]).astype(np.float32)
-        got = rows2[:, cols]
-        ulps = np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64))
-        assert ulps[live].max(initial=0) <= 1
+    dsx, dsy = rs.uniform(-2e-3, 2e-3, N).astype(np.float32), rs.uniform(-2e-3, 2e-3, N).astype(np.float32)
+    for n in (N, 257):
+        s = _samples(N)[:n]
+        inputs = _arnold_inputs(s)
+        plain = cam.create_rays_arnold(inputs, ray_index_base=7)
+        rows = cam.create_rays_arnold(inputs, ray_index_base=7, differentials=True)
+        assert rows.shape[0] == n
+        keep = np.r_[0:6, 18:21]
+        assert np.array_equal(rows[:, keep].view(np.uint32), plain[:, keep].view(np.uint32))
+        st = torch.from_numpy(s).cuda()
+        rays = cam.create_rays(st, ray_index_base=7)["rays"]
+        d = cam.ray_differentials(st, rays, ray_index_base=7).cpu().numpy()
+        assert np.array_equal(rows[:, 6:18].view(np.uint32), d.view(np.uint32))
+        # per-row dsx / dsy scale the raw columns
+        inputs2 = inputs.copy()
+        inputs2[:, 2] = dsx[:n]
+        inputs2[:, 3] = dsy[:n]
+        rows2 = cam.create_rays_arnold(inputs2, ray_index_base=7, differentials=True)
+        live = rows[:, 18] != 0
+        for cols, k in ((slice(6, 9), 2), (slice(9, 12), 3), (slice(12, 15), 2), (slice(15, 18), 3)):
+            want = (rows[:, cols] * inputs2[:, k:k + 1]).astype(np.float32)
+            got = rows2[:, cols]
+            ulps = np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64))
+            assert ulps[live].max(initial=0) <= 1
     cam.close()
 
 

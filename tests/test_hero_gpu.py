@@ -53,21 +53,23 @@ def _column_equals(hero, j, ref):
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cfg", ["C1", "C2", "C3", "C5"])
 def test_hero_column_is_the_spectral_call(cfg):
-    cam, _ = _cam(cfg)
+    """STRICT and FAST: both calls run one kernel body, so column 0 and the counters are the spectral call's in every bit in FAST too"""
     s_all, st_all = _samples(N, seed=11), ray_rng_states(N, seed=2)
-    for n in (N, 1, 63, 64, 65, 257):   # a partial wave, the chunk edge at 256, a lane that holds several rays in turn
-        s, st = s_all[:n], st_all[:n]
-        w = _hero_waves(n, 4)
-        ref, cr = _delta(cam, lambda: cam.create_rays(s, rng_states=st, wavelengths=w[:, 0].copy(), ray_index_base=3))
-        got, cg = _delta(cam, lambda: cam.create_rays_hero(s, w, rng_states=st, ray_index_base=3))
-        assert got["rays"].shape == (n, 4) and got["planes"].shape == (7, n, 4)
-        _column_equals(got, 0, ref)
-        assert cg == cr, (n, cg, cr)
-        one, c1 = _delta(cam, lambda: cam.create_rays_hero(s, w[:, :1].copy(), rng_states=st, ray_index_base=3))
-        assert one["rays"].shape == (n, 1)
-        _column_equals(one, 0, ref)
-        assert c1 == cr
-    cam.close()
+    for precision in (PRECISION_STRICT, PRECISION_FAST):
+        cam, _ = _cam(cfg, precision)
+        for n in (N, 1, 63, 64, 65, 257):   # a partial wave, the chunk edge at 256, a lane that holds several rays in turn
+            s, st = s_all[:n], st_all[:n]
+            w = _hero_waves(n, 4)
+            ref, cr = _delta(cam, lambda: cam.create_rays(s, rng_states=st, wavelengths=w[:, 0].copy(), ray_index_base=3))
+            got, cg = _delta(cam, lambda: cam.create_rays_hero(s, w, rng_states=st, ray_index_base=3))
+            assert got["rays"].shape == (n, 4) and got["planes"].shape == (7, n, 4)
+            _column_equals(got, 0, ref)
+            assert cg == cr, (precision, n, cg, cr)
+            one, c1 = _delta(cam, lambda: cam.create_rays_hero(s, w[:, :1].copy(), rng_states=st, ray_index_base=3))
+            assert one["rays"].shape == (n, 1)
+            _column_equals(one, 0, ref)
+            assert c1 == cr
+        cam.close()
 
 
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------

@@ -183,8 +183,8 @@ def test_rows_beside_hostile_neighbours(oracle_lib, precision):
 
 
 # ---- 5: past the grid's first pass ---------------------------------------------------------------------------------------------
-# mirrored from zoic_amd/csrc/hero.hip: kHeroGridCap blocks of kHeroBlock threads; a wave of kolb_hero_kernel claims kHeroChunk samples
-# at a time, a thread of hero_replicate_kernel one row per stride
+# mirrored from zoic_amd/csrc/spectral.hip: kSpecGridCap blocks of kSpecBlock threads; a wave of kolb_spectral_kernel<FAST, HERO> claims
+# kSpecChunk samples at a time, a thread of hero_replicate_kernel one row per stride
 HERO_GRID_CAP, HERO_BLOCK, HERO_CHUNK = 2048, 256, 256
 KOLB_FIRST_PASS = HERO_GRID_CAP * (HERO_BLOCK // 64) * HERO_CHUNK      # 2 097 152 samples
 THIN_FIRST_PASS = HERO_GRID_CAP * HERO_BLOCK                           # 524 288 rows

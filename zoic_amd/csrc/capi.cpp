@@ -116,7 +116,7 @@ struct LaunchSlot {
     DeviceBuffer<uint32_t> redo;        // the Kolb launch's scratch (kolb_scratch_dwords): work list of decision-safe FAST
 };
 
-// zoic_create_rays_hero_device on a THINLENS camera: the thin-lens kernel's n records, before hero.hip spreads them over the
+// zoic_create_rays_hero_device on a THINLENS camera: the thin-lens kernel's n records, before spectral.hip spreads them over the
 // columns.  One buffer per camera: a call holds `m` while it enqueues, and its stream waits for the previous user's `done`.
 struct HeroStage {
     std::mutex m;
@@ -877,11 +877,11 @@ struct DevicePointer {
     bool optional = false;
 };
 
-// The batch backward calls: the camera, n == 0 (OK before any pointer is looked at), every pointer's NULL / alignment check, the
-// device, every given pointer's memory type, and only then `launch` (it returns the launcher's rc).  Nothing is launched and no output
-// touched on any error.
-template <class Launch>
-zoic_status backward_batch(zoic_camera *cam, uint64_t n, std::initializer_list<DevicePointer> ptrs, Launch launch)
+// The batch device calls of both directions: the camera, n == 0 (OK before any pointer is looked at), every pointer's NULL / alignment
+// check in argument order, the device, with `deviceMemoryOnly` every given pointer's memory type, and only then `body` (it returns the
+// call's status).  Nothing is launched and no output touched on any error.
+template <class Body>
+zoic_status device_batch(zoic_camera *cam, uint64_t n, std::initializer_list<DevicePointer> ptrs, bool deviceMemoryOnly, Body body)
 {
     if (zoic_status s = check_ray_call(cam)) return s;
     if (n == 0) return ZOIC_OK;
@@ -890,7 +890,7 @@ zoic_status backward_batch(zoic_camera *cam, uint64_t n, std::initializer_list<D
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     for (const DevicePointer &a : ptrs) {
-        if (!a.p || is_device_memory(a.p)) continue;
+        if (!deviceMemoryOnly || !a.p || is_device_memory(a.p)) continue;
         std::string names;   // "d_rays, d_screen and d_flags"
         for (const DevicePointer *q = ptrs.begin(); q != ptrs.end(); ++q) {
             if (q != ptrs.begin()) names += (q + 1 == ptrs.end()) ? " and " : ", ";
@@ -898,7 +898,21 @@ zoic_status backward_batch(zoic_camera *cam, uint64_t n, std::initializer_list<D
         }
         return fail(ZOIC_ERR_INVALID_ARGUMENT, names + " must be device memory");
     }
-    return launch_status(launch());
+    return body();
+}
+
+// the forward calls (samples -> rays, rays -> differentials): any memory the device can reach
+template <class Body>
+zoic_status forward_batch(zoic_camera *cam, uint64_t n, std::initializer_list<DevicePointer> ptrs, Body body)
+{
+    return device_batch(cam, n, ptrs, false, body);
+}
+
+// the backward calls: device memory only; `launch` returns the launcher's rc
+template <class Launch>
+zoic_status backward_batch(zoic_camera *cam, uint64_t n, std::initializer_list<DevicePointer> ptrs, Launch launch)
+{
+    return device_batch(cam, n, ptrs, true, [&] { return launch_status(launch()); });
 }
 
 }  // namespace
@@ -1253,15 +1267,9 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
 zoic_status zoic_create_rays_device(zoic_camera *cam, uint64_t n, const float *d_samples, const uint32_t *d_rng_states,
                                     uint64_t ray_index_base, zoic_ray *d_rays, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
-    if (zoic_status s = check_pointer("d_samples", d_samples, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    return launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, reinterpret_cast<RayRecord *>(d_rays), static_cast<hipStream_t>(stream));
+    return forward_batch(cam, n, {{"d_samples", d_samples, 16}, {"d_rng_states", d_rng_states, 16, true}, {"d_rays", d_rays, 16}}, [&] {
+        return launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, reinterpret_cast<RayRecord *>(d_rays), static_cast<hipStream_t>(stream));
+    });
 }
 
 zoic_status zoic_create_rays_host(zoic_camera *cam, uint64_t n, const float *h_samples, const uint32_t *h_rng_states,
@@ -1398,47 +1406,71 @@ zoic_status zoic_ray_differentials_device(zoic_camera *cam, uint64_t n, const fl
                                           zoic_ray_differential *d_out, void *stream)
 {
     static_assert(sizeof(zoic_ray_differential) == 48, "zoic_ray_differential layout");
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (zoic_status s = check_pointer("d_samples", d_samples, 16)) return s;
-    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
-    if (zoic_status s = check_pointer("d_out", d_out, 16)) return s;
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int model = cam->params.p.lensModel;
-    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no derivative
-        ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
-        return ZOIC_OK;
-    }
-    return launch_status(launch_ray_differentials(model, cam->kolb, cam->thin, cam->bokehDev, d_samples, d_rng_states, ray_index_base, n,
-                                                  reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy, reinterpret_cast<float *>(d_out), st));
+    return forward_batch(
+        cam, n, {{"d_samples", d_samples, 16}, {"d_rng_states", d_rng_states, 16, true}, {"d_rays", d_rays, 16}, {"d_out", d_out, 16}},
+        [&]() -> zoic_status {
+            const hipStream_t st = static_cast<hipStream_t>(stream);
+            const int model = cam->params.p.lensModel;
+            if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no derivative
+                ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
+                return ZOIC_OK;
+            }
+            return launch_status(launch_ray_differentials(model, cam->kolb, cam->thin, cam->bokehDev, d_samples, d_rng_states, ray_index_base, n,
+                                                          reinterpret_cast<const RayRecord *>(d_rays), dsx, dsy, reinterpret_cast<float *>(d_out), st));
+        });
+}
+
+// zoic_create_rays_spectral_device (k == 1) and zoic_create_rays_hero_device (k >= 2): d_wavelengths = n x k, d_rays = n x k records
+static zoic_status create_rays_wavelengths(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples, const float *d_wavelengths,
+                                           const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream)
+{
+    return forward_batch(
+        cam, n, {{"d_samples", d_samples, 16}, {"d_wavelengths", d_wavelengths, 4}, {"d_rng_states", d_rng_states, 16, true}, {"d_rays", d_rays, 16}},
+        [&]() -> zoic_status {
+            const hipStream_t st = static_cast<hipStream_t>(stream);
+            RayRecord *rays = reinterpret_cast<RayRecord *>(d_rays);
+            if (cam->params.p.lensModel == ZOIC_RAYTRACED) {
+                SpectralTable W;
+                fill_spectral(cam, W);
+                const int mode = cam->kernel_mode();
+                return launch_status(k == 1 ? launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base,
+                                                                   n, rays, cam->dCounters, mode, st)
+                                            : launch_kolb_hero(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n,
+                                                               k, rays, cam->dCounters, mode, st));
+            }
+            const bool countsRays = cam->thin.useDof != 0;
+            if (k == 1) {
+                // THINLENS (and NONE's error): the records of zoic_create_rays_device, then the rows of invalid wavelengths rejected
+                if (zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, rays, st)) return s;
+                return launch_status(launch_spectral_reject(d_wavelengths, n, rays, cam->dCounters, countsRays, st));
+            }
+            // the same at k wavelengths: the n records into the camera's staging buffer, then spread over the columns with the invalid
+            // wavelengths rejected
+            HeroStage &H = cam->heroStage;
+            std::lock_guard<std::mutex> lk(H.m);
+            if (!H.done) ZOIC_HIP(hipEventCreateWithFlags(&H.done, hipEventDisableTiming));
+            if (H.rays.cap < n) {   // growing the buffer frees the old one: its previous user must be over
+                if (H.recorded) ZOIC_HIP(hipEventSynchronize(H.done));
+                ZOIC_HIP(H.rays.reserve(n));
+            }
+            if (H.recorded) ZOIC_HIP(hipStreamWaitEvent(st, H.done, 0));
+            zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, H.rays.ptr, st);
+            int rc = 0;
+            if (s == ZOIC_OK) rc = launch_hero_replicate(H.rays.ptr, d_wavelengths, n, k, rays, cam->dCounters, countsRays, st);
+            // whatever was queued reads or writes the buffer: its next user waits behind it
+            const hipError_t re = hipEventRecord(H.done, st);
+            if (re == hipSuccess) H.recorded = true;
+            if (s != ZOIC_OK) return s;
+            if (rc != 0) return launch_status(rc);
+            ZOIC_HIP(re);
+            return ZOIC_OK;
+        });
 }
 
 zoic_status zoic_create_rays_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
                                              const uint32_t *d_rng_states, uint64_t ray_index_base, zoic_ray *d_rays, void *stream)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
-    if (zoic_status s = check_pointer("d_samples", d_samples, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_wavelengths", d_wavelengths, 4)) return s;
-    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    RayRecord *rays = reinterpret_cast<RayRecord *>(d_rays);
-    if (cam->params.p.lensModel != ZOIC_RAYTRACED) {
-        // THINLENS (and NONE's error): the records of zoic_create_rays_device, then the rows of invalid wavelengths rejected
-        if (zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, rays, st)) return s;
-        return launch_status(launch_spectral_reject(d_wavelengths, n, rays, cam->dCounters, cam->thin.useDof != 0, st));
-    }
-    SpectralTable W;
-    fill_spectral(cam, W);
-    return launch_status(launch_kolb_spectral(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, rays,
-                                              cam->dCounters, cam->kernel_mode(), st));
+    return create_rays_wavelengths(cam, n, 1u, d_samples, d_wavelengths, d_rng_states, ray_index_base, d_rays, stream);
 }
 
 zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples, const float *d_wavelengths,
@@ -1449,43 +1481,7 @@ zoic_status zoic_create_rays_hero_device(zoic_camera *cam, uint64_t n, uint32_t 
     if (k == 0 || k > ZOIC_HERO_MAX_WAVELENGTHS) return fail(ZOIC_ERR_INVALID_ARGUMENT, "k must be 1 ... ZOIC_HERO_MAX_WAVELENGTHS");
     // one wavelength per sample: the spectral call itself (its argument checks, its kernel, its counters)
     if (k == 1) return zoic_create_rays_spectral_device(cam, n, d_samples, d_wavelengths, d_rng_states, ray_index_base, d_rays, stream);
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!d_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples is NULL");
-    if (zoic_status s = check_pointer("d_samples", d_samples, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_wavelengths", d_wavelengths, 4)) return s;
-    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    RayRecord *rays = reinterpret_cast<RayRecord *>(d_rays);
-    if (cam->params.p.lensModel != ZOIC_RAYTRACED) {
-        // THINLENS (and NONE's error): the n records of zoic_create_rays_device into the camera's staging buffer, then spread over the
-        // columns with the invalid wavelengths rejected
-        HeroStage &H = cam->heroStage;
-        std::lock_guard<std::mutex> lk(H.m);
-        if (!H.done) ZOIC_HIP(hipEventCreateWithFlags(&H.done, hipEventDisableTiming));
-        if (H.rays.cap < n) {   // growing the buffer frees the old one: its previous user must be over
-            if (H.recorded) ZOIC_HIP(hipEventSynchronize(H.done));
-            ZOIC_HIP(H.rays.reserve(n));
-        }
-        if (H.recorded) ZOIC_HIP(hipStreamWaitEvent(st, H.done, 0));
-        zoic_status s = launch_rays(cam, n, d_samples, d_rng_states, ray_index_base, H.rays.ptr, st);
-        int rc = 0;
-        if (s == ZOIC_OK) rc = launch_hero_replicate(H.rays.ptr, d_wavelengths, n, k, rays, cam->dCounters, cam->thin.useDof != 0, st);
-        // whatever was queued reads or writes the buffer: its next user waits behind it
-        const hipError_t re = hipEventRecord(H.done, st);
-        if (re == hipSuccess) H.recorded = true;
-        if (s != ZOIC_OK) return s;
-        if (rc != 0) return launch_status(rc);
-        ZOIC_HIP(re);
-        return ZOIC_OK;
-    }
-    SpectralTable W;
-    fill_spectral(cam, W);
-    return launch_status(launch_kolb_hero(cam->kolb, W, cam->bokehDev, d_samples, d_wavelengths, d_rng_states, ray_index_base, n, k, rays,
-                                          cam->dCounters, cam->kernel_mode(), st));
+    return create_rays_wavelengths(cam, n, k, d_samples, d_wavelengths, d_rng_states, ray_index_base, d_rays, stream);
 }
 
 zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n, const float *d_samples, const float *d_wavelengths,
@@ -1493,28 +1489,23 @@ zoic_status zoic_ray_differentials_spectral_device(zoic_camera *cam, uint64_t n,
                                                    float dsy, zoic_ray_differential *d_out, zoic_vec3 *d_chromatic, void *stream)
 {
     static_assert(sizeof(zoic_vec3) == 12, "zoic_vec3 layout");
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (zoic_status s = check_pointer("d_samples", d_samples, 16)) return s;
-    if (zoic_status s = check_pointer("d_wavelengths", d_wavelengths, 4)) return s;
-    if (zoic_status s = check_pointer("d_rng_states", d_rng_states, 16, true)) return s;
-    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
-    if (zoic_status s = check_pointer("d_out", d_out, 16)) return s;
-    if (zoic_status s = check_pointer("d_chromatic", d_chromatic, 8, true)) return s;
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int model = cam->params.p.lensModel;
-    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no derivative
-        ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
-        if (d_chromatic) ZOIC_HIP(hipMemsetAsync(d_chromatic, 0, n * 2u * sizeof(zoic_vec3), st));
-        return ZOIC_OK;
-    }
-    SpectralTable W;
-    fill_spectral(cam, W);
-    return launch_status(launch_ray_differentials_spectral(model, cam->kolb, W, cam->thin, cam->bokehDev, d_samples, d_wavelengths,
-                                                           d_rng_states, ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays), dsx,
-                                                           dsy, reinterpret_cast<float *>(d_out), reinterpret_cast<float *>(d_chromatic), st));
+    return forward_batch(
+        cam, n, {{"d_samples", d_samples, 16}, {"d_wavelengths", d_wavelengths, 4}, {"d_rng_states", d_rng_states, 16, true}, {"d_rays", d_rays, 16},
+                 {"d_out", d_out, 16}, {"d_chromatic", d_chromatic, 8, true}},
+        [&]() -> zoic_status {
+            const hipStream_t st = static_cast<hipStream_t>(stream);
+            const int model = cam->params.p.lensModel;
+            if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no derivative
+                ZOIC_HIP(hipMemsetAsync(d_out, 0, n * sizeof(zoic_ray_differential), st));
+                if (d_chromatic) ZOIC_HIP(hipMemsetAsync(d_chromatic, 0, n * 2u * sizeof(zoic_vec3), st));
+                return ZOIC_OK;
+            }
+            SpectralTable W;
+            fill_spectral(cam, W);
+            return launch_status(launch_ray_differentials_spectral(model, cam->kolb, W, cam->thin, cam->bokehDev, d_samples, d_wavelengths,
+                                                                   d_rng_states, ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays), dsx,
+                                                                   dsy, reinterpret_cast<float *>(d_out), reinterpret_cast<float *>(d_chromatic), st));
+        });
 }
 
 int zoic_camera_get_dispersion(const zoic_camera *cam, int capacity, float *ior_d, float *abbe, float *cauchy_b_out)

@@ -1,9 +1,9 @@
-// differentials_device.hpp -- what the differential passes (differentials.hip, spectral_differentials.hip) share on the device:
-// the launch shape and the replay of a record's accepted try with the ray kernels' own STRICT helpers.
+// differentials_device.hpp -- what the differential kernels (differentials.hip, spectral_differentials.hip) share on the device:
+// the launch shape, the replay of a record's accepted try with the ray kernels' own STRICT helpers, and the pass over a batch.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "differentials.hpp"
+#include "differentials_spectral.hpp"
 #include "kolb_pool_body.hpp"
 #include "thin_device.hpp"
 
@@ -74,6 +74,105 @@ static __device__ __forceinline__ RayDifferential thin_ray(const ThinTable &T, c
     const float inter = fabsf(T.focalDistance / dir0.z);
     const V3 q{dir0.x * inter - lens.x * T.apertureRadius, dir0.y * inter - lens.y * T.apertureRadius, dir0.z * inter};
     return thin_differentials(q, T.tanFov * fabsf(T.focalDistance));
+}
+
+// The pass over a batch: a wave takes 64 consecutive rays at a time.  It first reads the second half of its records (weight, flags) and,
+// with SPECTRAL, the wavelengths of the rays that have weight -- a lane whose wavelength is invalid is not live, whatever its record
+// says.  A wave without a live lane writes zeros and never reads a sample; otherwise the live lanes call rayFn and scale its tangents
+// by dsx / dsy.  Results leave through a per-wave LDS transpose as fully coalesced stores.
+//   ROWS: inputs are AtCameraInput rows (each row's own dsx / dsy), outputs whole AtCameraOutput rows (21 dword stores per lane);
+//   otherwise (sx, sy, lensx, lensy) samples in, 12 floats out (three 16-byte stores per lane), and with CHROMATIC six more to
+//   `chroma` (three 8-byte stores per lane).
+// RayFn(sample, tries, i) -> RayDifferential, with SPECTRAL RayFn(sample, lambda, tries, i) -> SpectralDifferential.
+template <bool ROWS, bool SPECTRAL, bool CHROMATIC, class RayFn>
+static __device__ __forceinline__ void differentials_pass(RayFn rayFn, const float4 *__restrict__ samples, const float *__restrict__ inputs7,
+                                                          const float *__restrict__ lambdas, const RayRecord *__restrict__ rays, uint64_t n,
+                                                          float dsx, float dsy, float *__restrict__ out, float *__restrict__ chroma)
+{
+    static_assert(!(ROWS && SPECTRAL) && (SPECTRAL || !CHROMATIC), "Arnold rows carry no wavelength; the wavelength tangent needs one");
+    constexpr uint32_t K = ROWS ? 21u : CHROMATIC ? 18u : 12u;   // floats per ray written (CHROMATIC: a wave's stage is 64 x 12, then 64 x 6)
+    __shared__ __align__(16) float stage[kDiffBlock / 64][64 * K];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    float *st = stage[wave];
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kDiffBlock;
+    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kDiffBlock + wave * 64u; base < n; base += stride) {
+        const uint64_t i = base + lane;
+        const bool have = i < n;
+        const float4 *rec = reinterpret_cast<const float4 *>(rays + (have ? i : base));
+        const float4 r1 = rec[1];                                              // dy dz weight flags
+        const float4 r0 = ROWS ? rec[0] : make_float4(0.f, 0.f, 0.f, 0.f);    // ox oy oz dx
+        bool live = have && r1.z != 0.0f;
+        float lambda = 0.0f;
+        if constexpr (SPECTRAL) {
+            if (live) lambda = lambdas[i];                                     // (0: not a wavelength) a dead wave reads none
+            live = live && spectral_valid(lambda);
+        }
+        const V3 zero{0.f, 0.f, 0.f};
+        SpectralDifferential g{RayDifferential{zero, zero, zero, zero}, zero, zero};
+        RayDifferential &r = g.screen;
+        if (__ballot(live) != 0ull && live) {
+            float4 s;
+            float sdx = dsx, sdy = dsy;
+            if constexpr (ROWS) {
+                const float *p = inputs7 + i * 7u;   // sx sy dsx dsy lensx lensy relative_time
+                s = make_float4(p[0], p[1], p[4], p[5]);
+                sdx = p[2]; sdy = p[3];
+            } else {
+                s = samples[i];
+            }
+            const uint32_t tries = (__builtin_bit_cast(uint32_t, r1.w) >> 1) & 31u;
+            if constexpr (SPECTRAL) g = rayFn(s, lambda, tries, i);
+            else r = rayFn(s, tries, i);
+            r.dOdx = diff_scale(r.dOdx, sdx); r.dDdx = diff_scale(r.dDdx, sdx);
+            r.dOdy = diff_scale(r.dOdy, sdy); r.dDdy = diff_scale(r.dDdy, sdy);
+        }
+        const uint64_t left = n - base;
+        const uint32_t valid = left < 64u ? static_cast<uint32_t>(left) : 64u;
+        float4 *st4 = reinterpret_cast<float4 *>(st);
+        float2 *st2 = reinterpret_cast<float2 *>(st + 64u * 12u);
+        if constexpr (ROWS) {
+            // AtCameraOutput: origin, dir, dOdx, dOdy, dDdx, dDdy, weight[3] -- origin / dir / weight as expand_outputs_kernel copies them
+            const float v[K] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r.dOdx.x, r.dOdx.y, r.dOdx.z, r.dOdy.x, r.dOdy.y, r.dOdy.z,
+                                r.dDdx.x, r.dDdx.y, r.dDdx.z, r.dDdy.x, r.dDdy.y, r.dDdy.z, r1.z, r1.z, r1.z};
+#pragma unroll
+            for (uint32_t f = 0; f < K; ++f) st[lane * K + f] = v[f];   // stride 21 dwords: conflict-free
+        } else {
+            st4[lane * 3u + 0u] = make_float4(r.dOdx.x, r.dOdx.y, r.dOdx.z, r.dOdy.x);
+            st4[lane * 3u + 1u] = make_float4(r.dOdy.y, r.dOdy.z, r.dDdx.x, r.dDdx.y);
+            st4[lane * 3u + 2u] = make_float4(r.dDdx.z, r.dDdy.x, r.dDdy.y, r.dDdy.z);
+            if constexpr (CHROMATIC) {
+                st2[lane * 3u + 0u] = make_float2(g.dOdl.x, g.dOdl.y);
+                st2[lane * 3u + 1u] = make_float2(g.dOdl.z, g.dDdl.x);
+                st2[lane * 3u + 2u] = make_float2(g.dDdl.y, g.dDdl.z);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes have landed
+        if constexpr (ROWS) {
+            float *dst = out + base * K;
+#pragma unroll
+            for (uint32_t m = 0; m < K; ++m) {
+                const uint32_t j = m * 64u + lane;
+                if (j < valid * K) dst[j] = st[j];
+            }
+        } else {
+            float4 *dst = reinterpret_cast<float4 *>(out) + base * 3u;
+#pragma unroll
+            for (uint32_t m = 0; m < 3u; ++m) {
+                const uint32_t j = m * 64u + lane;
+                if (j < valid * 3u) dst[j] = st4[j];
+            }
+            if constexpr (CHROMATIC) {
+                float2 *dst2 = reinterpret_cast<float2 *>(chroma) + base * 3u;
+#pragma unroll
+                for (uint32_t m = 0; m < 3u; ++m) {
+                    const uint32_t j = m * 64u + lane;
+                    if (j < valid * 3u) dst2[j] = st2[j];
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();   // the next wave-tile overwrites the stage
+    }
 }
 
 }  // namespace zoic

@@ -28,7 +28,7 @@ namespace zoic {
 constexpr uint32_t kHeroMaxWavelengths = 8;
 constexpr uint32_t kHeroCompanionLost = 0x100u;   // flag bit 8: the companion did not come through at the hero's lens point
 
-// ---- launchers (hero.hip) -------------------------------------------------------------------------------------------------
+// ---- launchers (spectral.hip) ------------------------------------------------------------------------------------------
 // RAYTRACED: d_lambda = n x k f32 (nm), hero first; out = n x k records.  mode as launch_kolb_spectral.  Ray i draws from the stream
 // keyed by rayBase + i (or d_rng[i]); the counters move as launch_kolb_spectral's on column 0.
 int launch_kolb_hero(const KolbTable &table, const SpectralTable &spec, const BokehTables &bokeh, const float *d_samples,

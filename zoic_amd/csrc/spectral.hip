@@ -1,8 +1,9 @@
-// spectral.hip -- camera_create_ray (RAYTRACED, zoic.cpp:1850-1964) at a wavelength per ray (spectral.hpp has the model).
+// spectral.hip -- camera_create_ray (RAYTRACED, zoic.cpp:1850-1964) at a wavelength per ray (spectral.hpp has the model), and with
+// HERO at k wavelengths per sample: the hero's accepted try traced once more at each companion wavelength (hero.hpp has the contract).
 //
-// Mapping.  Persistent lanes: a wave claims CHUNKS of kSpecChunk consecutive rays (grid-stride over the batch) and each lane holds
-// one ray until it is finished, then takes the next ray of the chunk (ballot + mbcnt).  A round of the wave's loop is
-//   * refill: free lanes take the chunk's next rays and set them up -- the reference's set-up arithmetic (setup_ray<true>: sensor
+// Mapping.  Persistent lanes: a wave claims CHUNKS of kSpecChunk consecutive samples (grid-stride over the batch) and each lane holds
+// one sample until it is finished, then takes the next sample of the chunk (ballot + mbcnt).  A round of the wave's loop is
+//   * refill: free lanes take the chunk's next samples and set them up -- the reference's set-up arithmetic (setup_ray<true>: sensor
 //     point, exit-pupil LUT, parabola rotation), the sample's own lens point, the ray's wavelength;
 //   * candidate search: a lane whose try dies at interface 0 (a clip there is geometry only: the wavelength plays no part) draws
 //     the next lens sample from its retry stream, as the pool kernels do -- tries and stream advance exactly as in the reference's
@@ -11,14 +12,21 @@
 //   * the finished rays' records are written and their counts kept per lane; a failed try goes back to the search.
 // Dead pixels (outside the image circle, all 27 tries are one) and retry-dead rays (no retry can reach the rear element:
 // dead_ray_end) end after their first try, as in the pool kernels.
+// HERO adds a life to the lane: a hero that finishes with weight keeps its lane and its start (os, ds) -- saved in front of every
+// trace, in STRICT as in FAST -- and goes back into the round's trace stage as a candidate at the next companion's dl, column after
+// column, before the lane takes the next sample.  Hero tries and companions of different lanes run through the same trace instruction
+// stream, so the trace stage stays as full as without companions; set-up, the reference sampler's gathers and the interface-0 search
+// are paid once per sample, not per wavelength.  A hero of weight 0 writes its k - 1 lost records at once and frees the lane.  k is a
+// wave-uniform kernel argument; no loop is unrolled over it.  Without HERO k is the constant 1 and all of this compiles away: column 0
+// and the counters are one body's, whatever k.
 // STRICT: trace_lens_spectral_strict (spectral.hpp), the reference's arithmetic bit for bit.  FAST (both FAST modes): f32 with
 // explicit FMAs (fast_optics.hpp FastHit / fast_refract) on per-lane eta, qOffset and krScale; set-up, lens samples, directions and
 // the interface-0 test stay the reference's, and a try with a clip inside a guard band (FastSurface::housingLo/Hi) is traced again
 // in the reference's arithmetic from the same start: every clip decision is either a FAST one outside its band or a STRICT one.
 #include <hip/hip_runtime.h>
 
+#include "hero.hpp"
 #include "kolb_pool_body.hpp"
-#include "spectral.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 
@@ -26,15 +34,16 @@ namespace zoic {
 namespace {
 
 constexpr int kSpecBlock = 256;
-constexpr uint32_t kSpecChunk = 256;           // rays per claim of a wave: 4 per lane
+constexpr uint32_t kSpecChunk = 256;           // samples per claim of a wave: 4 per lane
 constexpr uint32_t kSpecMinSearching = 16;     // the search goes on while at least this many lanes are looking
 constexpr uint64_t kSpecGridCap = 2048;        // 8 waves per SIMD on 256 CUs
 
 // The kernels' argument list as a struct (HIP lays kernel arguments out like a C struct, kolb_pool_body.hpp KolbKernelArgs): the
-// traces read the tables through the kernarg segment (spectral.hpp ZOIC_SPEC_PIN).
+// traces read the tables through the kernarg segment (spectral.hpp ZOIC_SPEC_PIN).  T first: kernarg_fast_surfaces() (fast_optics.hpp)
+// counts on it.
 struct SpectralKernelArgs {
     KolbTable T; SpectralTable W; BokehTables B; const float4 *samples; const float *lambdas; const uint4 *rngStates; uint64_t rayBase; uint64_t n;
-    RayRecord *out; DeviceCounters *counters;
+    RayRecord *out; DeviceCounters *counters; uint32_t k;
 };
 typedef const Surface __attribute__((address_space(4))) *SurfaceTable;
 typedef const SpectralTable __attribute__((address_space(4))) *SpectralTablePtr;
@@ -54,8 +63,8 @@ __device__ __forceinline__ bool trace_strict(int count, float dl, V3 &o, V3 &d, 
     return trace_lens_spectral_strict(kernarg_surfaces(), kernarg_spectral(), count, dl, o, d, tirCount);
 }
 
-// One try's trace in FAST arithmetic with the per-lane constants of the ray's wavelength.  (o, d) as trace_lens_fast_rolled leaves
-// them; `unsure`: a clip decision inside its interface's guard band was met (the caller then traces the try in STRICT).
+// One trace in FAST arithmetic with the per-lane constants of the lane's wavelength.  (o, d) as trace_lens_fast_rolled leaves
+// them; `unsure`: a clip decision inside its interface's guard band was met (the caller then traces the same start in STRICT).
 __device__ __forceinline__ bool trace_fast(int n, float dl, V3 &o, V3 &d, uint32_t &tirCount, bool &unsure)
 {
     const float inv = frsq_fast(fast_norm2(d));
@@ -98,15 +107,37 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return v;
 }
 
+__device__ __forceinline__ void store_zero_record(RayRecord *out, uint64_t at, uint32_t flags)
+{
+    store_ray_record(out, at, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, flags);
+}
+
+// the tail of the passes behind the thin-lens kernel: the counts it gave rejected rows are taken back (`flags`: such a row's record)
+__device__ __forceinline__ void count_taken_back(uint32_t flags, uint32_t &succ, uint32_t &vign)
+{
+    if (((flags >> 1) & 31u) > static_cast<uint32_t>(kMaxTries)) ++vign; else ++succ;
+}
+__device__ __forceinline__ void take_back(DeviceCounters *counters, uint32_t succ, uint32_t vign)
+{
+    DeviceCounters *cs = counter_set(counters);
+    succ = wave_sum(succ); vign = wave_sum(vign);
+    if (cs && (threadIdx.x & 63u) == 0u) {   // two's complement: the host sums the counter sets modulo 2^64
+        if (succ) atomicAdd(&cs->succes, 0ull - static_cast<unsigned long long>(succ));
+        if (vign) atomicAdd(&cs->vignetted, 0ull - static_cast<unsigned long long>(vign));
+    }
+}
+
 }  // namespace
 
-// budget: 0 scratch, 0 spills
-template <bool FAST>
+// budget: 0 scratch, 0 spills.  HERO: k = kRows wavelengths per sample, record (idx, col) at out[idx k + col]; otherwise k is 1 and every
+// hero-only statement below (col, hflags, hw, the saved start, the advance stage, the lost companions) is compiled away.
+template <bool FAST, bool HERO>
 __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTable T, const SpectralTable W, const BokehTables B,
                                                                    const float4 *__restrict__ samples, const float *__restrict__ lambdas,
                                                                    const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
-                                                                   RayRecord *__restrict__ out, DeviceCounters *counters)
+                                                                   RayRecord *__restrict__ out, DeviceCounters *counters, uint32_t kRows)
 {
+    const uint32_t k = HERO ? kRows : 1u;
     __shared__ __align__(16) float2 lut[kLutEntries];   // (maxScale, centroid.x) pairs of the exit-pupil LUT: setup_ray's lookup
     if (threadIdx.x < kLutEntries) lut[threadIdx.x] = make_float2(T.lutMaxScale[threadIdx.x], T.lutCentroidX[threadIdx.x]);
     __syncthreads();
@@ -122,10 +153,14 @@ __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTab
         bool busy = false, searching = false, cand = false, finiteSample = true;
         uint64_t idx = 0;
         uint32_t tries = 0;
+        uint32_t col = 0;        // the column this lane works on: 0 the hero's tries, j >= 1 the companion at lambdas[idx k + j]
+        uint32_t hflags = 0;     // the finished hero's flags and weight: what its companions carry
+        float hw = 0.0f;
         float dl = 0.0f;
         RaySetup rs{};
         Rng rng{1u, 2u, 3u, 4u};
         V3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
+        V3 os = o, ds = d;       // the start of the lane's last trace: the hero's accepted try leaves its companions' start here
         for (;;) {
             // ---- refill ---------------------------------------------------------------------------------------------------
             const unsigned long long freeMask = __ballot(!busy);
@@ -139,11 +174,13 @@ __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTab
                 next += took < left ? took : left;
             }
             if (fresh) {
-                const float lambda = lambdas[idx];
-                if (!spectral_valid(lambda)) {
-                    store_ray_record(out, idx, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, kSpectralRejected);   // no counter
+                const float lambda = lambdas[idx * k];
+                if (!spectral_valid(lambda)) {   // an invalid hero rejects the whole row; no counter
+#pragma nounroll
+                    for (uint32_t j = 0; j < k; ++j) store_zero_record(out, idx * k + j, kSpectralRejected);
                 } else {
                     busy = true;
+                    col = 0u;
                     const float4 s = samples[idx];
                     dl = spectral_dl(lambda);
                     rs = setup_ray<true>(T, lut, s.x, s.y);
@@ -168,8 +205,9 @@ __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTab
                 continue;
             }
 
-            // ---- candidate search (zoic.cpp:1927-1947: a clip at interface 0 bumps no counter and leaves (o, d) untouched) -------
-            bool done = false, failed = false;
+            // ---- candidate search: hero tries only, a companion is a candidate already (zoic.cpp:1927-1947: a clip at interface 0
+            // bumps no counter and leaves (o, d) untouched) ------------------------------------------------------------------------
+            bool done = false, failed = false, advance = false;
             for (;;) {
                 const uint32_t looking = static_cast<uint32_t>(__popcll(__ballot(searching)));
                 if (looking == 0u || (looking < kSpecMinSearching && __ballot(cand) != 0ull)) break;
@@ -195,46 +233,54 @@ __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTab
                 }
             }
 
-            // ---- the candidates' traces ------------------------------------------------------------------------------------
+            // ---- the candidates' traces: hero tries and companions, each lane at its own dl ---------------------------------------
             if (__ballot(cand) != 0ull && cand) {
                 cand = false;
                 uint32_t tirTry = 0;
                 bool ok;
+                os = o; ds = d;
                 if constexpr (FAST) {
-                    const V3 os = o, ds = d;
                     bool unsure = false;
                     ok = trace_fast(T.lensCount, dl, o, d, tirTry, unsure);
-                    if (unsure) {   // a clip too close to call: this try in the reference's arithmetic
+                    if (unsure) {   // a clip too close to call: this start in the reference's arithmetic
                         o = os; d = ds; tirTry = 0;
                         ok = trace_strict(T.lensCount, dl, o, d, tirTry);
                     }
                 } else {
                     ok = trace_strict(T.lensCount, dl, o, d, tirTry);
                 }
-                tir += tirTry;
-                if (ok) {
-                    done = true;
-                    failed = tries > static_cast<uint32_t>(kMaxTries);   // a success at try 26 is still out of tries (zoic.cpp:1927, 1951)
-                } else if (tries == 0u && (rs.flags & kRetryDeadBit) != 0u) {
-                    done = true; failed = true; tries = 0xffu;
-                } else if (tries >= kOut) {
-                    done = true; failed = true;   // the partial state of try 26 (zoic.cpp:1951-1961)
+                if (HERO && col != 0u) {   // a companion: one trace, no retry, no counter
+                    if (ok) store_ray_record(out, idx * k + col, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, hw, hflags);
+                    else store_zero_record(out, idx * k + col, hflags | kHeroCompanionLost);
+                    ++col;
+                    advance = true;
                 } else {
-                    o = V3{rs.o0x, rs.o0y, T.originShift};
-                    searching = true;
-                    if (tries == 0u) rng = ray_stream(rngStates, T.seed, rayBase, idx);
-                    const float u = rng_unit(xor128(rng));
-                    const float v = rng_unit(xor128(rng));
-                    ++tries;
-                    d = retry_direction(T, lens_sample<true>(T, B, nullptr, u, v), rs.o0x, rs.o0y, rs.maxScale, rs.translation, rs.sn, rs.cs);
+                    tir += tirTry;
+                    if (ok) {
+                        done = true;
+                        failed = tries > static_cast<uint32_t>(kMaxTries);   // a success at try 26 is still out of tries (zoic.cpp:1927, 1951)
+                    } else if (tries == 0u && (rs.flags & kRetryDeadBit) != 0u) {
+                        done = true; failed = true; tries = 0xffu;
+                    } else if (tries >= kOut) {
+                        done = true; failed = true;   // the partial state of try 26 (zoic.cpp:1951-1961)
+                    } else {
+                        o = V3{rs.o0x, rs.o0y, T.originShift};
+                        searching = true;
+                        if (tries == 0u) rng = ray_stream(rngStates, T.seed, rayBase, idx);
+                        const float u = rng_unit(xor128(rng));
+                        const float v = rng_unit(xor128(rng));
+                        ++tries;
+                        d = retry_direction(T, lens_sample<true>(T, B, nullptr, u, v), rs.o0x, rs.o0y, rs.maxScale, rs.translation, rs.sn, rs.cs);
+                    }
                 }
             }
 
-            // ---- finished rays -----------------------------------------------------------------------------------------------
+            // ---- finished heroes ---------------------------------------------------------------------------------------------
             if (done) {
                 float w;
                 uint32_t flags;
-                if (tries == 0xffu) {   // retry-dead: retries 1 ... 26 die at interface 0 (the arithmetic of the pool kernels)
+                const bool retryDead = tries == 0xffu;
+                if (retryDead) {   // retries 1 ... 26 die at interface 0 (the arithmetic of the pool kernels)
                     const DeadRayEnd e = dead_ray_end<true>(T, B, nullptr, rs, ray_stream(rngStates, T.seed, rayBase, idx));
                     o = e.o; d = e.d; w = e.w;
                     flags = 1u | (e.tries << 1) | ((rs.flags & 1u) << 6);
@@ -245,8 +291,36 @@ __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTab
                     flags = (tries > 0u ? 1u : 0u) | (tries << 1) | ((rs.flags & 1u) << 6);
                     if (failed) ++vign; else ++succ;                                             // zoic.cpp:1951-1957
                 }
-                store_ray_record(out, idx, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);   // zoic.cpp:1960-1961
-                busy = false; searching = false; cand = false;
+                store_ray_record(out, idx * k, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);   // zoic.cpp:1960-1961
+                searching = false; cand = false;
+                if (HERO && w != 0.0f && !retryDead) {   // the lane stays: its companions start where the accepted try started
+                    hw = w; hflags = flags; col = 1u;
+                    advance = true;
+                } else {   // no start to share (weight 0, or a retry-dead ray's NaN draw, hero.hpp): the companions are lost; an invalid wavelength is still rejected
+#pragma nounroll
+                    for (uint32_t j = 1; j < k; ++j)
+                        store_zero_record(out, idx * k + j, spectral_valid(lambdas[idx * k + j]) ? (flags | kHeroCompanionLost) : kSpectralRejected);
+                    busy = false;
+                }
+            }
+
+            // ---- the lane's next companion: invalid wavelengths are rejected on the way, after the last column the lane is free ------
+            if (HERO && advance) {
+                float lambda = 0.0f;
+#pragma nounroll
+                while (col < k) {
+                    lambda = lambdas[idx * k + col];
+                    if (spectral_valid(lambda)) break;
+                    store_zero_record(out, idx * k + col, kSpectralRejected);
+                    ++col;
+                }
+                if (col < k) {
+                    dl = spectral_dl(lambda);
+                    o = os; d = ds;
+                    cand = true;
+                } else {
+                    busy = false;
+                }
             }
         }
     }
@@ -268,22 +342,53 @@ __global__ __launch_bounds__(kSpecBlock) void spectral_reject_kernel(const float
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSpecBlock + threadIdx.x; i < n; i += stride) {
         if (spectral_valid(lambdas[i])) continue;
         const uint32_t flags = out[i].flags;
-        if (countsRays) { if (((flags >> 1) & 31u) > static_cast<uint32_t>(kMaxTries)) ++vign; else ++succ; }
-        store_ray_record(out, i, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, kSpectralRejected);
+        if (countsRays) count_taken_back(flags, succ, vign);
+        store_zero_record(out, i, kSpectralRejected);
     }
-    DeviceCounters *cs = counter_set(counters);
-    succ = wave_sum(succ); vign = wave_sum(vign);
-    if (cs && (threadIdx.x & 63u) == 0u) {   // two's complement: the host sums the counter sets modulo 2^64
-        if (succ) atomicAdd(&cs->succes, 0ull - static_cast<unsigned long long>(succ));
-        if (vign) atomicAdd(&cs->vignetted, 0ull - static_cast<unsigned long long>(vign));
+    take_back(counters, succ, vign);
+}
+
+// the same rows at k wavelengths: record i of the thin-lens kernel into the valid columns of row i, the others rejected; the count
+// of a row whose hero is rejected is taken back.  (Not the pass above at k = 1: that one works in place and writes rejected rows only.)
+__global__ __launch_bounds__(kSpecBlock) void hero_replicate_kernel(const RayRecord *__restrict__ staged, const float *__restrict__ lambdas, uint64_t n,
+                                                                    uint32_t k, RayRecord *__restrict__ out, DeviceCounters *counters, int countsRays)
+{
+    uint32_t succ = 0, vign = 0;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kSpecBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSpecBlock + threadIdx.x; i < n; i += stride) {
+        const float4 *p = reinterpret_cast<const float4 *>(staged + i);
+        const float4 a = p[0], b = p[1];
+        const uint32_t flags = __builtin_bit_cast(uint32_t, b.w);
+        const bool hero = spectral_valid(lambdas[i * k]);
+        if (!hero && countsRays) count_taken_back(flags, succ, vign);
+#pragma nounroll
+        for (uint32_t j = 0; j < k; ++j) {
+            if (hero && spectral_valid(lambdas[i * k + j])) store_ray_record(out, i * k + j, a.x, a.y, a.z, a.w, b.x, b.y, b.z, flags);
+            else store_zero_record(out, i * k + j, kSpectralRejected);
+        }
     }
+    take_back(counters, succ, vign);
 }
 
 namespace {
-uint32_t spec_grid(uint64_t n, uint64_t raysPerBlock)
+uint32_t spec_grid(uint64_t n, uint64_t itemsPerBlock)
 {
-    const uint64_t blocks = (n + raysPerBlock - 1) / raysPerBlock;
+    const uint64_t blocks = (n + itemsPerBlock - 1) / itemsPerBlock;
     return static_cast<uint32_t>(blocks < kSpecGridCap ? blocks : kSpecGridCap);
+}
+
+// k == 1: one wavelength per sample, the kernel without the hero's stages
+int launch_wavelength_rays(const KolbTable &table, const SpectralTable &spec, const BokehTables &bokeh, const float *d_samples,
+                           const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, uint32_t k, RayRecord *out,
+                           DeviceCounters *d_counters, int mode, void *stream)
+{
+    if (n == 0) return 0;
+    const auto kernel = k == 1u ? (mode == 0 ? kolb_spectral_kernel<false, false> : kolb_spectral_kernel<true, false>)
+                                : (mode == 0 ? kolb_spectral_kernel<false, true> : kolb_spectral_kernel<true, true>);
+    const dim3 grid(spec_grid(n, static_cast<uint64_t>(kSpecChunk) * (kSpecBlock / 64)));
+    hipLaunchKernelGGL(kernel, grid, dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), table, spec, bokeh,
+                       reinterpret_cast<const float4 *>(d_samples), d_lambda, reinterpret_cast<const uint4 *>(d_rng), rayBase, n, out, d_counters, k);
+    return static_cast<int>(hipGetLastError());
 }
 }  // namespace
 
@@ -291,16 +396,16 @@ int launch_kolb_spectral(const KolbTable &table, const SpectralTable &spec, cons
                          const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, RayRecord *out,
                          DeviceCounters *d_counters, int mode, void *stream)
 {
+    return launch_wavelength_rays(table, spec, bokeh, d_samples, d_lambda, d_rng, rayBase, n, 1u, out, d_counters, mode, stream);
+}
+
+int launch_kolb_hero(const KolbTable &table, const SpectralTable &spec, const BokehTables &bokeh, const float *d_samples,
+                     const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, uint32_t k, RayRecord *out,
+                     DeviceCounters *d_counters, int mode, void *stream)
+{
     if (n == 0) return 0;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const float4 *samples = reinterpret_cast<const float4 *>(d_samples);
-    const uint4 *rng = reinterpret_cast<const uint4 *>(d_rng);
-    const dim3 grid(spec_grid(n, static_cast<uint64_t>(kSpecChunk) * (kSpecBlock / 64)));
-    if (mode == 0)
-        hipLaunchKernelGGL(kolb_spectral_kernel<false>, grid, dim3(kSpecBlock), 0, s, table, spec, bokeh, samples, d_lambda, rng, rayBase, n, out, d_counters);
-    else
-        hipLaunchKernelGGL(kolb_spectral_kernel<true>, grid, dim3(kSpecBlock), 0, s, table, spec, bokeh, samples, d_lambda, rng, rayBase, n, out, d_counters);
-    return static_cast<int>(hipGetLastError());
+    if (k < 2 || k > kHeroMaxWavelengths) return static_cast<int>(hipErrorInvalidValue);   // k = 1 is launch_kolb_spectral
+    return launch_wavelength_rays(table, spec, bokeh, d_samples, d_lambda, d_rng, rayBase, n, k, out, d_counters, mode, stream);
 }
 
 int launch_spectral_reject(const float *d_lambda, uint64_t n, RayRecord *out, DeviceCounters *d_counters, bool countsRays, void *stream)
@@ -308,6 +413,16 @@ int launch_spectral_reject(const float *d_lambda, uint64_t n, RayRecord *out, De
     if (n == 0) return 0;
     hipLaunchKernelGGL(spectral_reject_kernel, dim3(spec_grid(n, kSpecBlock)), dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), d_lambda, n, out,
                        d_counters, countsRays ? 1 : 0);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_hero_replicate(const RayRecord *staged, const float *d_lambda, uint64_t n, uint32_t k, RayRecord *out, DeviceCounters *d_counters,
+                          bool countsRays, void *stream)
+{
+    if (n == 0) return 0;
+    if (k < 2 || k > kHeroMaxWavelengths) return static_cast<int>(hipErrorInvalidValue);   // k = 1 is launch_spectral_reject
+    hipLaunchKernelGGL(hero_replicate_kernel, dim3(spec_grid(n, kSpecBlock)), dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), staged, d_lambda, n, k,
+                       out, d_counters, countsRays ? 1 : 0);
     return static_cast<int>(hipGetLastError());
 }
 
