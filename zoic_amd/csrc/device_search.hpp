@@ -66,11 +66,13 @@ __device__ __forceinline__ int cell_of(float u, int cellCount, bool &inRange)
     return inRange ? static_cast<int>(u * static_cast<float>(cellCount)) : 0;   // exact: cellCount is a power of two
 }
 
-__device__ __forceinline__ int cell_resolve(const uint4 rec, float u, bool inRange, bool &exceptional)
+// exceptional: the wave mask of the lanes that have to finish with upper_bound (the record's flag, or a sample outside [0,1)) -- a ballot per
+// compare, combined in scalar registers: the flag never exists as a 0/1 value per lane
+__device__ __forceinline__ int cell_resolve(const uint4 rec, float u, unsigned long long &exceptional)
 {
     const float a = __builtin_bit_cast(float, rec.x), b = __builtin_bit_cast(float, rec.y);
     const bool ge0 = !(u < a), ge1 = !(u < b);          // sorted: ge1 implies ge0
-    exceptional = ((rec.w >> 31) != 0u) | !inRange;
+    exceptional = __builtin_amdgcn_ballot_w64(static_cast<int32_t>(rec.w) < 0) | __builtin_amdgcn_ballot_w64(!(u >= 0.0f)) | __builtin_amdgcn_ballot_w64(!(u < 1.0f));
     const uint32_t pair = ge1 ? rec.w : rec.z;           // k = 2 -> idx[lo+2] (low half of .w)
     return static_cast<int>((ge0 & !ge1) ? (pair >> 16) : (pair & 0xffffu));   // k = 1 -> high half of .z
 }
@@ -83,12 +85,13 @@ struct CellProbe { uint4 rec; int row; uint32_t cellIndex; };
 
 __device__ __forceinline__ CellProbe bokeh_cells_issue(const BokehTables &B, const float *ldsRowCells, int y, float uRow, float uCol)
 {
-    bool inR, inC, excR;
+    bool inR, inC;
+    unsigned long long excR;
     const int gr = cell_of(uRow, B.rowCellCount, inR);
     const int gc = cell_of(uCol, B.colCellCount, inC);
-    int row = cell_resolve(reinterpret_cast<const uint4 *>(ldsRowCells)[gr], uRow, inR, excR);
-    if (__ballot(excR) != 0ull) {          // rare, wave-uniform: dense cell or a sample outside [0,1)
-        if (excR) {
+    int row = cell_resolve(reinterpret_cast<const uint4 *>(ldsRowCells)[gr], uRow, excR);
+    if (excR != 0ull) {          // rare, wave-uniform: dense cell or a sample outside [0,1)
+        if (__builtin_amdgcn_inverse_ballot_w64(excR)) {
             const uint32_t bnd = B.rowBounds[gr];
             const int lo = inR ? static_cast<int>(bnd & 0xffffu) : 0, hi = inR ? static_cast<int>(bnd >> 16) : y;
             int r = lo + upper_bound_idx(B.cdfRow + lo, hi - lo, uRow);
@@ -99,7 +102,8 @@ __device__ __forceinline__ CellProbe bokeh_cells_issue(const BokehTables &B, con
     CellProbe p;
     p.row = row;
     p.cellIndex = static_cast<uint32_t>(row) * static_cast<uint32_t>(B.colCellCount) + static_cast<uint32_t>(gc);
-    p.rec = reinterpret_cast<const uint4 *>(B.colCells)[p.cellIndex];
+    // scalar base + a 32-bit byte offset (the records of an image fill far less than 4 GB)
+    p.rec = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(B.colCells) + p.cellIndex * 16u);
     return p;
 }
 
@@ -107,11 +111,11 @@ template <bool EXACT_DIVIDE>
 __device__ __forceinline__ V2 bokeh_cells_finish(const BokehTables &B, int x, int y, float uCol, const CellProbe &p)
 {
     const bool inC = (uCol >= 0.0f) & (uCol < 1.0f);
-    bool excC;
+    unsigned long long excC;
     const int row = p.row;
-    int col = cell_resolve(p.rec, uCol, inC, excC);
-    if (__ballot(excC) != 0ull) {
-        if (excC) {
+    int col = cell_resolve(p.rec, uCol, excC);
+    if (excC != 0ull) {
+        if (__builtin_amdgcn_inverse_ballot_w64(excC)) {
             const uint32_t bnd = B.colBounds[p.cellIndex];
             const int lo = inC ? static_cast<int>(bnd & 0xffffu) : 0, hi = inC ? static_cast<int>(bnd >> 16) : x;
             const int start = row * x;

@@ -13,21 +13,35 @@
 //     PUSHES the unfinished ones -- ballot + mbcnt compaction -- onto the wave's pool in LDS (48 bytes per ray: index,
 //     sensor point, exit-pupil constants, tries/flags, retry stream);
 //   * phase B (retry pass): as soon as the pool holds 64 rays (or no fresh sample is left) the wave POPS 64 of them,
-//     runs one more try for each -- same search loop, same trace -- writes the finished ones, pushes the rest back.
+//     seeds the retry streams of those that have not drawn yet, runs one more try for each -- the search loop, then the
+//     same trace -- writes the finished ones, pushes the rest back.
 // Every pass therefore starts with (up to) 64 live lanes, set-up runs exactly once per ray at full width, and the pass
 // loop carries a dozen wave-uniform scalars and the prefetched sample.  Per-ray retry streams (keyed by the global ray
 // index) make the result independent of lane / pass / wave, so STRICT stays bit-identical to the oracle.
+//
+// Bookkeeping.  Outside the retry search a pass is wave-uniform control flow, and there the lanes' flags (active, searching,
+// candidate, unsure, to-finish, dead pixel, finished, keep) are 64-bit wave masks in SGPR pairs, combined with s_and / s_andn2 /
+// s_or; a lane re-enters per-lane form through an inverse ballot -- the mask IS the branch's exec -- only where it has
+// something to do.  (A flag kept as a bool went through v_cndmask 0/1 + v_cmp_ne at each of its ballots: that is how LLVM
+// lowers the ballot of anything but a single compare, so composite conditions are ballots per compare, combined in scalars.)
+// Inside the search the flags stay per lane -- a mask updated inside a divergent branch is a divergent value to LLVM and lands
+// in VGPRs -- and become masks once, behind the loop.  A retry stream's key depends on the seed and the HIGH word of the ray
+// index only: the host computes it for the launch's first high word (kernel argument seedKey), a lane past a multiple of 2^32
+// recomputes it.  Wave-uniform flags carried round the pass loop are 0/1 words (a bool would occupy an SGPR pair as a lane
+// mask); loads and stores of consecutive lanes take a scalar base and a 32-bit lane offset.
 //
 // Hand-overs (same contract as round 2): GUARD (decision-safe FAST) lists the rays with a decision inside its guard band
 // for the STRICT kernel that follows on the stream; DEAD instantiations collect "retry-dead" rays whose first try failed
 // (tables.hpp KolbTable::retry*) in a second LDS list and complete them 64 at a time INSIDE this kernel (finish_dead_ray
 // at full lane width) -- the byte map, its memset and the separate finish kernel of round 2 are gone.
 //
-// Order of memory operations in a pass (vmcnt is ONE in-order counter): pool pop (LDS) -> candidate search (retries: the
-// bokeh sampler's dependent global load) -> the fresh batches move up (IMAGE: the column cell record of the next batch's
-// first lens sample is requested -- its LDS -> global chain flies under this pass's trace -- then the batch after it) ->
-// trace -> record stores -> pool push (LDS).  The next pass waits for its probe and its samples with vmcnt(2+): the two
-// record stores issued after them are never waited for.
+// Order of memory operations in a pass (vmcnt is ONE in-order counter): pool pop (LDS; caller-supplied retry-stream states:
+// one global load per ray that has not drawn yet) -> candidate search (retries: the bokeh sampler's dependent global load) ->
+// the fresh batches move up (IMAGE: the column cell record of the next batch's first lens sample is requested -- its LDS ->
+// global chain flies under this pass's trace -- then the batch after it) -> trace -> record stores -> pool push (LDS).
+// Every vector-memory wait LLVM places in the pass loop is vmcnt(0) (it does not count past a control-flow merge): a pass's
+// first wait -- for its probe and samples in phase A, at the first search round's entry in phase B -- also covers the previous
+// pass's record stores.  Deferring the stores or fencing the loads in front of them was measured and bought nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +73,7 @@ struct KolbKernelArgs {
     DeviceCounters *counters; unsigned int *workCursor; uint32_t ldsWords, chunkRays, chunksPerPart, minSearching;
     uint32_t *redoList; unsigned int *redoCount;             // GUARD kernel: appends the rays it cannot decide; LISTED kernel: reads them
     unsigned int *clearCursor;                                // the cursor block of the NEXT launch on this slot: zeroed by workgroup 0 (not LISTED)
+    uint32_t seedKey;                                         // pool kernels: rng_key(T.seed, rayBase >> 32), the retry streams' key for the launch's first high index word
 };
 template <class V, size_t OFFSET>
 __device__ __forceinline__ V kernarg_field()
@@ -226,9 +241,18 @@ constexpr uint32_t kPoolTriesShift = 8, kPoolDeadBit = 1u << 13, kPoolRetryDeadB
 #define ZOIC_POOL_ATTR_STRICT __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
 
+// The lanes' flags (searching, cand, unsure ...) live as 64-bit wave masks in SGPRs: the ballot of a flag is that mask.  (__ballot takes an
+// int: a flag went through v_cndmask 0/1 + v_cmp_ne at every site.)
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ uint32_t mask_rank(unsigned long long m)   // exclusive prefix count of the lanes set in m
 {
     return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+}
+__device__ __forceinline__ unsigned long long double_bits(uint32_t m)   // bit i of m -> bits 2i and 2i + 1
+{
+    unsigned long long r;
+    asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"(m));
+    return r;
 }
 __device__ __forceinline__ bool mask_bit(unsigned long long m, uint32_t lane) { return ((m >> lane) & 1ull) != 0ull; }
 
@@ -285,19 +309,19 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
     uint32_t next = 0, end = 0, part = blockIdx.x % kCursorParts, partsTried = 0;
     float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
     uint32_t base1 = 0, base2 = 0, cnt1 = 0, cnt2 = 0;
-    bool have1 = false, have2 = false;
+    uint32_t have1 = 0u, have2 = 0u;   // 0 / 1 in one SGPR each (a wave-uniform bool carried round the pass loop occupies an SGPR pair, as a lane mask)
     CellProbe probe{make_uint4(0u, 0u, 0u, 0u), 0, 0u};
     const auto request_batch = [&]() {   // -> b2
-        have2 = false;
+        have2 = 0u;
         if (next >= end) {   // claim the next chunk: one atomic per chunkRays samples per wave
             if (!claim_chunk(ZOIC_KARG(workCursor), lane, part, partsTried, ZOIC_KARG(chunkRays), ZOIC_KARG(chunksPerPart), n, next, end)) return;
         }
         base2 = next;
         cnt2 = (end - next < 64u) ? end - next : 64u;
-        const uint32_t wi = (lane < cnt2) ? next + lane : next;
-        s2 = samples[wi];
+        const uint32_t wl = (lane < cnt2) ? lane : 0u;
+        s2 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(samples + next) + wl * 16u);   // scalar base + 32-bit lane offset
         next += cnt2;
-        have2 = true;
+        have2 = 1u;
     };
     const auto advance_batches = [&]() {   // b1 <- b2 (+ its probe), b2 <- the next request
         s1 = s2; base1 = base2; cnt1 = cnt2; have1 = have2;
@@ -315,25 +339,35 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
     // compute-dense and the waves inside the trace go first.
     constexpr bool memoryPhasesFirst = IMAGE;
     for (;;) {
-        const bool drain = !have1;                                          // no fresh sample left for this wave
+        const bool drain = have1 == 0u;                                         // no fresh sample left for this wave
         const bool fromPool = poolCnt >= 64u || (drain && poolCnt != 0u);
         if (!fromPool && drain) break;
         if (memoryPhasesFirst) __builtin_amdgcn_s_setprio(1);
         FastSurfaceTable fsurf = nullptr;
-        if constexpr (GUARD) fsurf = launder_table(kernarg_fast_surfaces());   // keeps the table's s_loads at their use (fast_optics.hpp)
+        if constexpr (GUARD) {   // keeps the table's s_loads at their use (fast_optics.hpp); derived from the kernarg base here, every pass: the sum is not carried round the loop
+            typedef const char __attribute__((address_space(4))) *KernargBytes;
+            KernargBytes kb = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kb));
+            fsurf = (FastSurfaceTable)(kb + offsetof(KolbTable, fsurf));
+        }
         else if constexpr (!STRICT) fsurf = kernarg_fast_surfaces();
         (void)fsurf;
 
         // ---- the pass's 64 rays: a fresh batch (phase A) or 64 pooled rays (phase B) -------------------------------------
-        bool active, dead, unsure = false;
+        bool active, dead;
         uint32_t idx, tries, lutMiss;   // lutMiss: bit 0 outside the LUT, bits 1.. the TIR tally, kRetryDeadBit
         float o0x, o0y, maxScale, translation, sn, cs;
         uint32_t rminq = 0u;   // two-level search: the ray's per-draw reject bound (setup_ray)
         (void)rminq;
         Rng rng{1, 2, 3, 4};
         V3 o, d{0.0f, 0.0f, 1.0f};
-        bool cand = false, finiteSample = true, searching;
-        bool toFinish = false;   // a retry-dead ray whose first try has failed -> the dead list
+        bool finiteSample = true;
+        uint32_t passBase = 0u;   // phase A: the batch's first ray
+        // The lanes' flags are 64-bit wave masks (SGPR pairs, s_and / s_andn2 / s_or) wherever control flow is wave-uniform -- everywhere but inside the
+        // retry search, which keeps them per lane -- and a lane re-enters per-lane form (inverse ballot: the mask is the branch's exec) only where it has
+        // something to do.  searchingM: still looking for a candidate; candMask: holds one; unsureM (GUARD): a decision too close to call;
+        // toFinishM (DEAD): a retry-dead ray whose first try has failed -> the dead list; deadM / finiteM: dead pixel / finite first lens sample.
+        unsigned long long activeM, searchingM, candMask = 0ull, unsureM = 0ull, toFinishM = 0ull, deadM, finiteM = ~0ull;
         // does (o, d) clear interface 0?  near0: too close to call (GUARD)
         const auto clears_rear = [&](const V3 &oo, const V3 &dd, bool &near0) {
             if constexpr (STRICT) {
@@ -347,20 +381,23 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
         };
         if (!fromPool) {
             // phase A: set 64 fresh rays up and run the search's FIRST step for all of them (zoic.cpp:1853-1925)
+            activeM = cnt1 >= 64u ? ~0ull : (1ull << cnt1) - 1ull;
+            passBase = base1;
             active = lane < cnt1;
             idx = base1 + lane;
             const RaySetup rs = setup_ray<STRICT, TWO>(T, lutLds, s1.x, s1.y);
             o0x = rs.o0x; o0y = rs.o0y; maxScale = rs.maxScale; translation = rs.translation; sn = rs.sn; cs = rs.cs;
             lutMiss = rs.flags; dead = rs.dead; rminq = rs.rminq;
-            if constexpr (GUARD) unsure = active && T.useLUT && rs.lutEdge;
+            if constexpr (GUARD) { if (T.useLUT) unsureM = activeM & wave_ballot(rs.lutEdge); }
             tries = 0;
             o = V3{o0x, o0y, T.originShift};
-            searching = GUARD ? (active && !unsure) : active;
+            searchingM = activeM & ~unsureM;
             const float u = s1.z, v = s1.w;
             // dead pixel (outside the image circle, LUT entries zero): whatever finite point the sampler returns, the direction
             // is (0 - o.x, 0 - o.y, dirZ); samples in [0,1)^2 off the disk mapping's 0/0 centre need no sampler
             V2 lens;
-            const bool anyDead = __ballot(dead) != 0ull;
+            deadM = wave_ballot(dead);
+            const bool anyDead = deadM != 0ull;
             // plain: a sample in [0,1)^2 off the disk mapping's 0/0 centre -- for a dead pixel the sampler's (finite) point is never looked at
             bool plainSample = true;
             if (anyDead) plainSample = (u >= 0.0f) & (u < 1.0f) & (v >= 0.0f) & (v < 1.0f) & !((u == 0.5f) & (v == 0.5f));   // wave-uniform: most waves hold no dead pixel and skip these compares
@@ -369,11 +406,12 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                 // a wave of nothing but dead pixels with plain samples (the corners of a frame wider than the image circle: three quarters of C5's) needs no
                 // lens sample at all: ~35 instructions a ray of the ~250 such a ray costs [MI355X, profiles/ab_r06/ab_dead_wave.log]
                 lens = V2{0.0f, 0.0f};
-                if (__ballot(active && !(dead && plainSample)) != 0ull) lens = sample_lens(u, v);
+                if (wave_ballot(active && !(dead && plainSample)) != 0ull) lens = sample_lens(u, v);
             }
             if (anyDead) {
                 if (dead && plainSample) lens = V2{0.0f, 0.0f};
                 finiteSample = (fabsf(lens.x) <= 3.0e38f) && (fabsf(lens.y) <= 3.0e38f);
+                finiteM = wave_ballot(finiteSample);
             }
             if (!T.useLUT) {                    // zoic.cpp:1873-1877
                 d = V3{(lens.x * T.rearAperture) - o.x, (lens.y * T.rearAperture) - o.y, T.dirZ};
@@ -389,21 +427,30 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             // like one clipped later and goes to the pool (or, retry-dead, to the dead list) from behind it.  Same rays; [MI355X, profiles/ab_r06/ab_no_a0.log]
             // the test was 30 (STRICT: 65) instructions a ray that the trace repeats: C4 +2.1 %, C3 +1.4 %, C2 +1.0 % decision-safe, STRICT +2.1 %; without the
             // dead-pixel exception C5 -3.5 %.
-            bool near0 = false;
-            bool pass0 = true;
-            if (anyDead) pass0 = clears_rear(o, d, near0);
-            if (searching) {
-                if (GUARD && near0) { unsure = true; searching = false; }   // too close to call: no decision is taken here
-                else if (pass0) { cand = true; searching = false; }
-                else {
-                    // a clip at interface 0 bumps no TIR counter and leaves (o, d) untouched: for a dead pixel all 27 tries are this one
-                    if (dead && finiteSample) { tries = kOut; searching = false; }
-                    else if (DEAD && (lutMiss & kRetryDeadBit) != 0u) { toFinish = true; searching = false; }   // no retry can succeed
+            if (!anyDead) { candMask = searchingM; searchingM = 0ull; }
+            else {
+                bool near0 = false;
+                const bool pass0 = clears_rear(o, d, near0);
+                if constexpr (GUARD) {   // too close to call: no decision is taken here
+                    const unsigned long long nearM = searchingM & wave_ballot(near0);
+                    unsureM |= nearM; searchingM &= ~nearM;
+                }
+                candMask = searchingM & wave_ballot(pass0);
+                searchingM &= ~candMask;
+                // a clip at interface 0 bumps no TIR counter and leaves (o, d) untouched: for a dead pixel all 27 tries are this one
+                const unsigned long long outNowM = searchingM & deadM & finiteM;
+                if (__builtin_amdgcn_inverse_ballot_w64(outNowM)) tries = kOut;
+                searchingM &= ~outNowM;
+                if constexpr (DEAD) {   // no retry can succeed
+                    toFinishM = searchingM & wave_ballot((lutMiss & kRetryDeadBit) != 0u);
+                    searchingM &= ~toFinishM;
                 }
             }
         } else {
             const uint32_t cnt = poolCnt < 64u ? poolCnt : 64u;
             poolCnt -= cnt;
+            activeM = cnt >= 64u ? ~0ull : (1ull << cnt) - 1ull;
+            searchingM = activeM;
             active = lane < cnt;
             const uint32_t slot = poolCnt + (active ? lane : 0u);
             const float4 e0 = pool0[slot];
@@ -415,10 +462,24 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             rng = Rng{e2.x, e2.y, e2.z, e2.w};
             tries = (packed >> kPoolTriesShift) & 31u;
             dead = (packed & kPoolDeadBit) != 0u;
+            deadM = wave_ballot(dead);
             lutMiss = (packed & 0x7fu) | ((packed & kPoolRetryDeadBit) ? kRetryDeadBit : 0u);
             if constexpr (TWO) rminq = (packed >> 16) & 0xffu;
             o = V3{o0x, o0y, T.originShift};
-            searching = active;
+            // a ray that has not drawn yet: its private xorshift128 stream is seeded here, once, before the search (every popped ray draws in
+            // the first round).  The stream's key is the launch's (kernel argument) unless the ray's index lies past a multiple of 2^32.
+            if (tries == 0u) {
+                const uint4 *states = ZOIC_KARG(rngStates);
+                if (states) { const uint4 r = states[idx]; rng = Rng{r.x, r.y, r.z, r.w}; }
+                else {
+                    const uint64_t rayBase = ZOIC_KARG(rayBase);
+                    const uint32_t baseLo = static_cast<uint32_t>(rayBase), lo = baseLo + idx;
+                    uint32_t key = ZOIC_KARG(seedKey);
+                    if (__builtin_expect(lo < baseLo, 0))   // idx < 2^31: at most one carry
+                        key = rng_key(kernarg_field<uint32_t, offsetof(KolbKernelArgs, T) + offsetof(KolbTable, seed)>(), static_cast<uint32_t>(rayBase >> 32) + 1u);
+                    rng = rng_from_key(key, lo);
+                }
+            }
         }
 
         // ---- candidate search: RETRIES draw lens samples until one clears the rear element's housing (zoic.cpp:1927-1947) ----
@@ -428,16 +489,12 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
         // once for the survivors.  The loop is wave-uniform: it goes on while enough lanes are looking to be worth the others'
         // wait (any lane, once the wave has no fresh work left).  Retry passes only: the lanes of a fresh batch that are still
         // looking go to the pool as they are (tries == 0) and draw from there -- same rays, the per-ray retry streams see to that.
-        if (fromPool)
+        if (fromPool) {
+        bool searching = active, cand = false, unsure = false;
         for (;;) {
-            const uint32_t looking = static_cast<uint32_t>(__popcll(__ballot(searching)));
+            const uint32_t looking = static_cast<uint32_t>(__popcll(wave_ballot(searching)));
             if (looking < (drain ? 1u : minSearching)) break;
             if (searching) {
-                if (tries == 0) {               // first retry of this ray: seed its private xorshift128 stream
-                    const uint4 *states = ZOIC_KARG(rngStates);
-                    if (states) { const uint4 r = states[idx]; rng = Rng{r.x, r.y, r.z, r.w}; }
-                    else rng = rng_for_ray(kernarg_field<uint32_t, offsetof(KolbKernelArgs, T) + offsetof(KolbTable, seed)>(), ZOIC_KARG(rayBase) + idx);
-                }
                 if constexpr (IMAGE && ZOIC_SEARCH_DRAWS > 1) {
                     // several draws per round: their column records are all requested before the first is read, so a round waits
                     // for memory once; a later draw counts (tries, retry stream) only when the ones before it were rejected with
@@ -494,7 +551,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                 const float rminf = static_cast<float>(rminq) * (1.0f / 256.0f);
 #pragma unroll
                 for (int k = 0; k < kTwoLevelDraws; ++k) {
-                    if (k > 0 && __ballot(searching && !pending) == 0ull) break;
+                    if (k > 0 && wave_ballot(searching && !pending) == 0ull) break;
                     if (searching && !pending) {
                         pu = rng_unit(xor128(rng));   // zoic.cpp:1930
                         pv = rng_unit(xor128(rng));
@@ -515,77 +572,101 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             }
         }
 
+        candMask = wave_ballot(cand); searchingM = wave_ballot(searching);
+        if constexpr (GUARD) unsureM = wave_ballot(unsure);
+        }
+
         // ---- the fresh batches move up; issued here so that the sampler's dependent load above never waits for these loads ------
         if (!fromPool) advance_batches();
 
+        const unsigned long long firstTryM = wave_ballot(tries == 0u);
+        unsigned long long outM = wave_ballot(tries > static_cast<uint32_t>(kMaxTries));   // out of tries
+        unsigned long long deadFirstM = firstTryM & deadM & finiteM;   // dead pixels at their first try with a finite sample: one failed trace decides all 27 tries
+        asm volatile("" : "+s"(deadFirstM));   // combined HERE: one SGPR pair lives through the trace, not three (LLVM sinks the ands behind it and spills)
+
         // ---- one full trace for every lane that holds a candidate -------------------------------------------------------------
-        bool ok = false;
+        unsigned long long okM = 0ull;   // the try got through
         const V3 oStart = o, dStart = d;
-        const bool firstTry = tries == 0;
-        const unsigned long long candMask = __ballot(cand);
         if (candMask != 0ull) {
             if (memoryPhasesFirst) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3);
-            uint32_t tirTry = 0;   // 0/1: this try ended in total internal reflection
-            if constexpr (NS > 0) {
-                if constexpr (STRICT) {
+            unsigned long long tirM;   // this try ended in total internal reflection
+            if constexpr (NS > 0 && !STRICT) {
+                unsigned long long unsureMask;
+                okM = trace_lens_fast_pred<NS, GUARD>(fsurf, o, d, candMask, tirM, unsureMask);
+                if constexpr (GUARD) unsureM |= unsureMask;
+            } else {
+                const bool cand = __builtin_amdgcn_inverse_ballot_w64(candMask);
+                bool ok = false, unsure = false;
+                uint32_t tirTry = 0;   // 0/1
+                if constexpr (NS > 0) {
                     bool oor = false;
                     ok = trace_lens_strict_pred<NS>(T, o, d, tirTry, cand, oor);
-                    if (__builtin_expect(__ballot(cand && oor) != 0ull, 0)) {   // never seen: a root left the lean sequences' verified range
+                    if (__builtin_expect(wave_ballot(cand && oor) != 0ull, 0)) {   // never seen: a root left the lean sequences' verified range
                         if (cand && oor) { o = oStart; d = dStart; tirTry = 0; ok = trace_lens_strict(T, o, d, tirTry); }
                     }
-                } else {
-                    unsigned long long tirMask, unsureMask;
-                    const unsigned long long alive = trace_lens_fast_pred<NS, GUARD>(fsurf, o, d, candMask, tirMask, unsureMask);
-                    ok = mask_bit(alive, lane);
-                    tirTry = mask_bit(tirMask, lane) ? 1u : 0u;
-                    if constexpr (GUARD) unsure |= mask_bit(unsureMask, lane);
+                } else if (cand) {
+                    if constexpr (STRICT) ok = trace_lens_strict(T, o, d, tirTry);
+                    else if constexpr (GUARD) { bool u2 = false; ok = trace_lens_fast_rolled(T, o, d, tirTry, &u2); unsure |= u2; }
+                    else ok = trace_lens_fast_rolled(T, o, d, tirTry);
                 }
-            } else if (cand) {
-                if constexpr (STRICT) ok = trace_lens_strict(T, o, d, tirTry);
-                else if constexpr (GUARD) { bool u2 = false; ok = trace_lens_fast_rolled(T, o, d, tirTry, &u2); unsure |= u2; }
-                else ok = trace_lens_fast_rolled(T, o, d, tirTry);
+                okM = wave_ballot(ok);
+                tirM = wave_ballot(tirTry != 0u);
+                if constexpr (GUARD) unsureM |= wave_ballot(unsure);
             }
-            const bool shortcut = cand && !ok && firstTry && dead && finiteSample && !(GUARD && unsure);
-            // the shortcut stands for 26 more identical failures: account for their TIR bumps as well
+            // dead-pixel shortcut: a failed first try stands for 26 more identical failures -- account for their TIR bumps as well
+            const unsigned long long shortcutM = candMask & ~okM & deadFirstM & ~unsureM;
             if constexpr (DEFER) {
                 // a dropped ray must leave no trace in the counters (the kernel that picks it up counts it): TIR bumps are
                 // tallied per ray, above bit 0 of lutMiss, and reach the wave total only when the ray finishes here
-                if (!unsure) lutMiss += (tirTry << 1) + (shortcut ? (tirTry * kOut) << 1 : 0u);
+                const unsigned long long bumpM = tirM & ~unsureM;
+                if (bumpM != 0ull) {
+                    if (__builtin_amdgcn_inverse_ballot_w64(bumpM)) lutMiss += 1u << 1;
+                    if (__builtin_amdgcn_inverse_ballot_w64(bumpM & shortcutM)) lutMiss += kOut << 1;
+                }
             } else {
-                tir += static_cast<uint32_t>(__popcll(__ballot(tirTry != 0u))) + kOut * static_cast<uint32_t>(__popcll(__ballot(shortcut && tirTry != 0u)));
+                tir += static_cast<uint32_t>(__popcll(tirM)) + kOut * static_cast<uint32_t>(__popcll(shortcutM & tirM));
             }
-            if (shortcut) tries = kOut;   // ... then finish the ray as the reference would
-            else if (DEAD && cand && !ok && firstTry && (lutMiss & kRetryDeadBit) != 0u) toFinish = true;   // first try failed inside the lens: same
+            if (shortcutM != 0ull) {   // ... then finish the ray as the reference would
+                if (__builtin_amdgcn_inverse_ballot_w64(shortcutM)) tries = kOut;
+                outM |= shortcutM;
+            }
+            // a retry-dead ray whose first try failed inside the lens: no retry can succeed either
+            if constexpr (DEAD) toFinishM |= candMask & ~okM & firstTryM & ~shortcutM & wave_ballot((lutMiss & kRetryDeadBit) != 0u);
             if constexpr (NS > 0) {
                 // the predicated trace does not keep the partial state of a failed ray; a ray that FINISHES failed (out of
                 // tries) gets it from the branchy trace, which stops at the failing interface
-                if (cand && !ok && tries > static_cast<uint32_t>(kMaxTries) && !(GUARD && unsure)) {
-                    uint32_t ignored = 0;
-                    o = oStart; d = dStart;
-                    if constexpr (STRICT) (void)trace_lens_strict(T, o, d, ignored);
-                    else (void)trace_lens_fast_rolled(T, o, d, ignored);
+                const unsigned long long againM = candMask & ~okM & outM & ~unsureM;
+                if (againM != 0ull) {
+                    if (__builtin_amdgcn_inverse_ballot_w64(againM)) {
+                        uint32_t ignored = 0;
+                        o = oStart; d = dStart;
+                        if constexpr (STRICT) (void)trace_lens_strict(T, o, d, ignored);
+                        else (void)trace_lens_fast_rolled(T, o, d, ignored);
+                    }
                 }
             }
         }
         if (!memoryPhasesFirst) __builtin_amdgcn_s_setprio(0);
-        // a lane that ran out at interface 0 hands out the untouched (o, d) of its last sample -- the reference's partial state
-        // (the predicated trace scribbles over the registers of lanes that ride along)
-        if (!cand) { o = oStart; d = dStart; }
 
         // ---- finished rays: counters + record; hand-overs; everything else goes (back) to the pool --------------------------
-        const bool dropU = GUARD && active && unsure;                 // -> STRICT kernel, evaluated from scratch
-        const bool dropF = DEAD && active && toFinish && !dropU;       // -> completed below, 64 at a time
-        const bool finished = active && !searching && !toFinish && (ok || tries > static_cast<uint32_t>(kMaxTries)) && !dropU;
+        const unsigned long long dropUM = GUARD ? activeM & unsureM : 0ull;                 // -> STRICT kernel, evaluated from scratch
+        const unsigned long long dropFM = DEAD ? activeM & toFinishM & ~dropUM : 0ull;      // -> completed below, 64 at a time
+        const unsigned long long finishedM = activeM & ~searchingM & ~toFinishM & (okM | outM) & ~dropUM;
+        // a lane that ran out at interface 0 hands out the untouched (o, d) of its last sample -- the reference's partial state
+        // (the predicated trace scribbles over the registers of lanes that ride along; only a finished ray's are looked at)
+        if ((finishedM & ~candMask) != 0ull) {
+            if (__builtin_amdgcn_inverse_ballot_w64(finishedM & ~candMask)) { o = oStart; d = dStart; }
+        }
         if constexpr (DEFER) {
-            if (finished || dropF) tirAcc += (lutMiss & ~kRetryDeadBit) >> 1;
+            if (__builtin_amdgcn_inverse_ballot_w64(finishedM | dropFM)) tirAcc += (lutMiss & ~kRetryDeadBit) >> 1;
         }
         {
-            const uint32_t nv = static_cast<uint32_t>(__popcll(__ballot(finished && tries > static_cast<uint32_t>(kMaxTries))));
+            const uint32_t nv = static_cast<uint32_t>(__popcll(finishedM & outM));
             vign += nv;                                                                       // zoic.cpp:1951-1957
-            succ += static_cast<uint32_t>(__popcll(__ballot(finished))) - nv;
+            succ += static_cast<uint32_t>(__popcll(finishedM)) - nv;
         }
         {
-            float w = (tries > static_cast<uint32_t>(kMaxTries)) ? 0.0f : 1.0f;
+            float w = __builtin_amdgcn_inverse_ballot_w64(outM) ? 0.0f : 1.0f;
             if (T.exposureOn) w *= T.exposureMul;                                            // zoic.cpp:1981-1987
             const uint32_t flags = (tries > 0 ? 1u : 0u) | (tries << 1) | ((lutMiss & 1u) << 6);
             constexpr bool kTransposed = IMAGE && !STRICT;   // the FAST IMAGE kernels
@@ -601,47 +682,46 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
                 stA[lane] = make_float4(o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f);   // zoic.cpp:1960-1961
                 stB[lane] = make_float4(d.y * -1.0f, d.z * -1.0f, w, __builtin_bit_cast(float, flags));
                 __builtin_amdgcn_wave_barrier();
-                const unsigned long long fin = __ballot(finished);
                 const float4 *half = (lane & 1u) ? stB : stA;
-                float4 *dst = reinterpret_cast<float4 *>(out + (idx - lane));   // idx = batch base + lane (advance_batches has moved base1 on)
+                // scalar base (the batch's first record; advance_batches has moved base1 on) + a 32-bit lane offset; lanes 2r and 2r + 1 write the halves
+                // of ray r's record (r + 32 in the second instruction): their exec masks are the finished mask's halves with every bit doubled
+                char *dst = reinterpret_cast<char *>(out + passBase);
                 const float4 p0 = half[lane >> 1], p1 = half[32u + (lane >> 1)];
-                if ((fin >> (lane >> 1)) & 1ull) dst[lane] = p0;
-                if ((fin >> (32u + (lane >> 1))) & 1ull) dst[64u + lane] = p1;
+                if (__builtin_amdgcn_inverse_ballot_w64(double_bits(static_cast<uint32_t>(finishedM)))) *reinterpret_cast<float4 *>(dst + lane * 16u) = p0;
+                if (__builtin_amdgcn_inverse_ballot_w64(double_bits(static_cast<uint32_t>(finishedM >> 32)))) *reinterpret_cast<float4 *>(dst + (1024u + lane * 16u)) = p1;
                 __builtin_amdgcn_wave_barrier();
             } else
-            if (finished) {
+            if (__builtin_amdgcn_inverse_ballot_w64(finishedM)) {
                 store_ray_record(out, idx, o.x * -1.0f, o.y * -1.0f, o.z * -1.0f, d.x * -1.0f, d.y * -1.0f, d.z * -1.0f, w, flags);   // zoic.cpp:1960-1961
             }
         }
         if constexpr (GUARD) {
-            const unsigned long long m = __ballot(dropU);
-            if (m != 0ull) {
-                if (dropU) unsureLds[unsureCnt + mask_rank(m)] = idx;
-                unsureCnt += static_cast<uint32_t>(__popcll(m));
+            if (dropUM != 0ull) {
+                if (__builtin_amdgcn_inverse_ballot_w64(dropUM)) unsureLds[unsureCnt + mask_rank(dropUM)] = idx;
+                unsureCnt += static_cast<uint32_t>(__popcll(dropUM));
             }
         }
         if constexpr (DEAD) {
-            const unsigned long long m = __ballot(dropF);
-            if (m != 0ull) {
-                if (dropF) deadLds[deadCnt + mask_rank(m)] = idx;
-                deadCnt += static_cast<uint32_t>(__popcll(m));
+            if (dropFM != 0ull) {
+                if (__builtin_amdgcn_inverse_ballot_w64(dropFM)) deadLds[deadCnt + mask_rank(dropFM)] = idx;
+                deadCnt += static_cast<uint32_t>(__popcll(dropFM));
             }
         }
         {
-            const bool keep = active && !finished && !dropU && !dropF;
-            const unsigned long long m = __ballot(keep);
-            if (m != 0ull) {
-                if (keep) {
-                    const uint32_t slot = poolCnt + mask_rank(m);
-                    uint32_t packed = (lutMiss & 0x7fu) | (tries << kPoolTriesShift) | (dead ? kPoolDeadBit : 0u) |
+            const unsigned long long keepM = activeM & ~finishedM & ~dropUM & ~dropFM;
+            if (keepM != 0ull) {
+                const uint32_t slot = poolCnt + mask_rank(keepM);
+                if (__builtin_amdgcn_inverse_ballot_w64(keepM)) {
+                    uint32_t packed = (lutMiss & 0x7fu) | (tries << kPoolTriesShift) | (__builtin_amdgcn_inverse_ballot_w64(deadM) ? kPoolDeadBit : 0u) |
                                       ((lutMiss & kRetryDeadBit) ? kPoolRetryDeadBit : 0u);
                     if constexpr (TWO) packed |= rminq << 16;
                     pool0[slot] = make_float4(__builtin_bit_cast(float, idx), o0x, o0y, __builtin_bit_cast(float, packed));
                     pool1[slot] = make_float4(maxScale, translation, sn, cs);
                 }
                 // the retry stream of a ray that has not drawn yet is seeded when it is popped (tries == 0): nothing to store
-                if (__ballot(keep && tries != 0u) != 0ull) { if (keep) pool2[poolCnt + mask_rank(m)] = make_uint4(rng.x, rng.y, rng.z, rng.w); }
-                poolCnt += static_cast<uint32_t>(__popcll(m));
+                const unsigned long long drawnM = keepM & wave_ballot(tries != 0u);
+                if (drawnM != 0ull) { if (__builtin_amdgcn_inverse_ballot_w64(keepM)) pool2[slot] = make_uint4(rng.x, rng.y, rng.z, rng.w); }
+                poolCnt += static_cast<uint32_t>(__popcll(keepM));
             }
         }
         // ---- hand-over lists: emptied in whole batches ---------------------------------------------------------------------
@@ -659,7 +739,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             while (deadCnt >= 64u) {
                 deadCnt -= 64u;
                 const bool nanDraw = finish_dead_ray<STRICT>(T, B, lutLds, bokehLds, samples, ZOIC_KARG(rngStates), ZOIC_KARG(rayBase), out, deadLds[deadCnt + lane]);
-                const uint32_t ns = static_cast<uint32_t>(__popcll(__ballot(nanDraw)));
+                const uint32_t ns = static_cast<uint32_t>(__popcll(wave_ballot(nanDraw)));
                 succ += ns; vign += 64u - ns;
             }
         }
@@ -680,7 +760,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
             const bool mine = lane < deadCnt;
             bool nanDraw = false;
             if (mine) nanDraw = finish_dead_ray<STRICT>(T, B, lutLds, bokehLds, samples, ZOIC_KARG(rngStates), ZOIC_KARG(rayBase), out, deadLds[lane]);
-            const uint32_t ns = static_cast<uint32_t>(__popcll(__ballot(mine && nanDraw)));
+            const uint32_t ns = static_cast<uint32_t>(__popcll(wave_ballot(mine && nanDraw)));
             succ += ns; vign += deadCnt - ns;
         }
     }
@@ -704,7 +784,7 @@ __device__ __forceinline__ void kolb_pool_body(const KolbTable &T, const BokehTa
 #define ZOIC_POOL_PARAMS const KolbTable T, const BokehTables B, const float4 *__restrict__ samples, const uint4 *__restrict__ rngStates, \
         uint64_t rayBase, uint32_t n, RayRecord *__restrict__ out, DeviceCounters *counters, unsigned int *__restrict__ workCursor,        \
         uint32_t ldsWords, uint32_t chunkRays, uint32_t chunksPerPart, uint32_t minSearching, uint32_t *__restrict__ redoList,             \
-        unsigned int *__restrict__ redoCount, unsigned int *__restrict__ clearCursor
+        unsigned int *__restrict__ redoCount, unsigned int *__restrict__ clearCursor, uint32_t seedKey
 #define ZOIC_POOL_KERNEL(NAME_, ATTR_, STRICT_, GUARD_)                                                                        \
     template <int NS, bool DEAD, bool IMAGE, bool TWO = false>                                                               \
     __global__ __launch_bounds__(kRefillBlock) ATTR_ void NAME_(ZOIC_POOL_PARAMS)                                             \
@@ -744,6 +824,7 @@ int launch_kolb_pool_impl(const KolbTable &table, const BokehTables &bokeh, cons
         RayRecord *o = out + done;
         const float4 *sp = reinterpret_cast<const float4 *>(d_samples) + done;
         const uint4 *rp = d_rng ? reinterpret_cast<const uint4 *>(d_rng) + done : nullptr;
+        const uint32_t seedKey = rng_key(table.seed, static_cast<uint32_t>((rayBase + done) >> 32));   // the retry streams' key (optics.hpp) for this launch's first high index word
         const uint32_t ldsWords = IMAGE ? static_cast<uint32_t>(bokeh.ldsWords) : 0u;   // bokeh row cell records: 4 KB at 256 rows, 32 KB at the 2048-row limit
         const auto lds_bytes = [&](bool guard) {
             return static_cast<size_t>(ldsWords + kLutLdsWords + kWavesPerBlock * (kPoolWaveWords + (guard ? kPoolListWords : 0u) + (DEAD ? kPoolListWords : 0u))) * sizeof(float);
@@ -751,7 +832,7 @@ int launch_kolb_pool_impl(const KolbTable &table, const BokehTables &bokeh, cons
         unsigned int *redoCount = d_workCursor + kRedoCountOffset, *redoCursor = d_workCursor + kRedoCursorOffset;
 #define ZOIC_LAUNCH_POOL(KERNEL_, NS_, CURSOR_, GUARD_)                                                                          \
     hipLaunchKernelGGL((KERNEL_<NS_, DEAD, IMAGE, TWO>), dim3(grid), dim3(kRefillBlock), lds_bytes(GUARD_), st, table, bokeh, sp, rp, rayBase + done, \
-                       static_cast<uint32_t>(m), o, d_counters, CURSOR_, ldsWords, chunkRays, chunksPerPart, kMinSearching, d_redoList, redoCount, d_clearCursor)
+                       static_cast<uint32_t>(m), o, d_counters, CURSOR_, ldsWords, chunkRays, chunksPerPart, kMinSearching, d_redoList, redoCount, d_clearCursor, seedKey)
 #define ZOIC_LAUNCH_POOL_BY_COUNT(KERNEL_, CURSOR_, GUARD_)                                                                      \
     switch (table.lensCount) {  /* unrolled instantiations for the interface counts of real prescriptions */                   \
     case 7: ZOIC_LAUNCH_POOL(KERNEL_, 7, CURSOR_, GUARD_); break;                                                               \

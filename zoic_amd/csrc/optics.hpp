@@ -68,17 +68,21 @@ ZOIC_HD uint32_t pcg_hash(uint32_t v)
     return (word >> 22u) ^ word;
 }
 
-// private retry stream of ray `gid`: never all-zero
-ZOIC_HD Rng rng_for_ray(uint32_t seed, uint64_t gid)
+// private retry stream of ray `gid`: never all-zero.  The key depends on the seed and the HIGH word of the ray index only (one value per
+// 2^32 rays: the pool kernels get it from the host, kolb_pool_body.hpp), the four state words on the key and the low word.
+ZOIC_HD uint32_t rng_key(uint32_t seed, uint32_t hi) { return pcg_hash(seed ^ pcg_hash(hi + 0x9E3779B9u)); }
+ZOIC_HD Rng rng_from_key(uint32_t k, uint32_t lo)
 {
-    uint32_t lo = static_cast<uint32_t>(gid), hi = static_cast<uint32_t>(gid >> 32);
-    uint32_t k = pcg_hash(seed ^ pcg_hash(hi + 0x9E3779B9u));
     Rng r;
     r.x = pcg_hash(k ^ (lo * 4u + 0u));
     r.y = pcg_hash(k ^ (lo * 4u + 1u) ^ 0x85EBCA6Bu);
     r.z = pcg_hash(k ^ (lo * 4u + 2u) ^ 0xC2B2AE35u);
     r.w = pcg_hash(k ^ (lo * 4u + 3u) ^ 0x27D4EB2Fu) | 1u;
     return r;
+}
+ZOIC_HD Rng rng_for_ray(uint32_t seed, uint64_t gid)
+{
+    return rng_from_key(rng_key(seed, static_cast<uint32_t>(gid >> 32)), static_cast<uint32_t>(gid));
 }
 
 // ---- fastSin / fastCos, zoic.cpp:661-681 --------------------------------------------------------
