@@ -61,7 +61,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_create_rays_hero_device (k wavelengths through one lens point per sample),
  *      ZOIC_HERO_MAX_WAVELENGTHS; flag bit 8 of zoic_ray (ZOIC_RAY_COMPANION_LOST).
  *      Added later without a new number (additive): zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian and their
- *      _spectral forms (the trace-back with its Jacobian dPs / d(origin, dir)). */
+ *      _spectral forms (the trace-back with its Jacobian dPs / d(origin, dir)).
+ *      Added later without a new number (additive): zoic_ray_transmittance_device, zoic_camera_set_coatings and
+ *      zoic_camera_get_coatings (the Fresnel transmittance of traced rays, with single-layer coatings). */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -358,6 +360,37 @@ int zoic_camera_get_dispersion(const zoic_camera *cam, int capacity, float *ior_
  * prescriptions.  count = 0 clears the override (V may be NULL).  A count that differs from the loaded lens's surface count returns
  * ZOIC_ERR_INVALID_ARGUMENT, here and at every zoic_camera_update while the override is set.  Changes nothing but the dispersion table. */
 zoic_status zoic_camera_set_abbe_numbers(zoic_camera *cam, int count, const float *V);
+/* ---- Fresnel transmittance of traced rays (opt-in; csrc/transmittance.hpp has the full definition) --------------------------------
+ * The share of unpolarised light the lens's interfaces let through along the path a record took: T = the product over the interfaces
+ * of 1 - (R_s + R_p) / 2, with every interface's indices at the ray's own wavelength (the dispersion table above), bare or with a
+ * single-layer film (zoic_camera_set_coatings).  No absorption.  The accepted try is replayed once per sample and traced in the STRICT
+ * arithmetic in every precision mode.  A pass over records that already exist: it changes no record and no counter; multiply a
+ * record's weight by its T.
+ * Pass what the forward call was given (d_samples, d_wavelengths, d_rng_states, ray_index_base) and what it wrote (d_rays):
+ *   k == 1, d_wavelengths == NULL   the records of zoic_create_rays_device, at the d-line (587.5618 nm);
+ *   k == 1, d_wavelengths           the records of zoic_create_rays_spectral_device;
+ *   k >= 2                          the records of zoic_create_rays_hero_device (d_wavelengths may not be NULL).
+ * d_rays and d_transmittance are n x k, sample-major; 1 <= k <= ZOIC_HERO_MAX_WAVELENGTHS.  The start comes from the sample, column 0's
+ * try count and the ray's retry stream; every column whose record has weight != 0 and whose wavelength is valid is traced from it at
+ * its own wavelength.  Every other column gets +0.0: weight 0 (a lost companion, a rejected record) or a wavelength HERE outside
+ * [360, 830] or NaN, whatever its record says.  A replayed path that does not come through (possible only for records of
+ * ZOIC_PRECISION_FAST_UNCHECKED or for inputs that do not match the records) gets +0.0 too.
+ * THINLENS: 1.0 where the record has weight != 0 and the wavelength is valid, else +0.0.  NONE: zeros.
+ * The dispersion and film tables are read at the call.  Stream semantics, threading contract and alignment (d_transmittance 4-byte
+ * aligned) as zoic_ray_differentials_spectral_device.  ZOIC_ERR_INVALID_ARGUMENT for k == 0 or k > ZOIC_HERO_MAX_WAVELENGTHS (checked
+ * first) and for a NULL or misaligned pointer (d_rng_states may be NULL); ZOIC_ERR_NOT_UPDATED before an update; n = 0 returns ZOIC_OK. */
+zoic_status zoic_ray_transmittance_device(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples,
+        const float *d_wavelengths, const uint32_t *d_rng_states, uint64_t ray_index_base, const zoic_ray *d_rays,
+        float *d_transmittance, void *stream);
+/* Single-layer coatings, one per interface in FILE order (front to rear): the film's index (it does not disperse) and the wavelength
+ * lambda0 (nm) at which it is a quarter wave thick.  Index 0: uncoated (the default for every interface); any other entry needs a
+ * finite index >= 1 and a finite lambda0 > 0, else ZOIC_ERR_INVALID_ARGUMENT.  An interface between equal media (the stop) ignores its
+ * entry.  count = the surface count; 0 clears (the arrays may be NULL).  A count that differs from the loaded lens's surface count
+ * returns ZOIC_ERR_INVALID_ARGUMENT, here and at every zoic_camera_update while the override is set.  Changes nothing but the film table. */
+zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *film_index, const float *film_lambda0_nm);
+/* The film table of the camera's lens (works on a ZOIC_DEVICE_NONE camera): returns the surface count and writes up to `capacity`
+ * entries, trace order (rear first), into the arrays that are not NULL; -1 for a NULL camera or a negative capacity. */
+int zoic_camera_get_coatings(const zoic_camera *cam, int capacity, float *film_index, float *film_lambda0_nm);
 /* camera_create_ray(node, input, output, tid), zoic.cpp:1752: the per-sample signature.  No launch per call: the sample goes
  * to a resident kernel through mapped pinned memory (csrc/mailbox.hip; ~7 us per call; the kernel retires by itself after 1 ms
  * without a call and is started again by the next one).  Re-entrant: every tid owns a retry stream that carries over from call

@@ -110,6 +110,9 @@ SYMBOLS = {
     "zoic_ray_differentials_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "zoic_camera_get_dispersion": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "zoic_camera_set_abbe_numbers": (C.c_int, [_vp, C.c_int, _vp]),
+    "zoic_ray_transmittance_device": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "zoic_camera_set_coatings": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "zoic_camera_get_coatings": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "zoic_camera_create_ray": (C.c_int, [_vp, C.POINTER(CameraInput), C.POINTER(CameraOutput), C.c_uint16]),
     "zoic_tile_create": (C.c_int, [_vp, _u32, C.c_uint16, C.POINTER(_vp)]),
     "zoic_tile_destroy": (None, [_vp]),

@@ -714,6 +714,73 @@ class ZoicCamera:
                                                             float(dsx), float(dsy), out.data_ptr(), C.c_void_p(st)))
         return out
 
+    def transmittance(self, samples, rays, wavelengths=None, rng_states=None, ray_index_base=0, out=None, stream=None):
+        """Fresnel transmittance (zoic_ray_transmittance_device) of rays create_rays / create_rays_hero made from device tensors: the
+        share of unpolarised light the lens's interfaces let through along each record's path, with the coatings of set_coatings.
+
+        samples, wavelengths, rng_states, ray_index_base: what the forward call was given; rays: the record tensor it returned (or its
+        result dict).  wavelengths None: (n,8) records of create_rays(samples), at the d-line; (n,): the spectral records of
+        create_rays(samples, wavelengths=); (n,k): the hero records of create_rays_hero, rays (n,k,8).  Returns a float32 device tensor
+        of the wavelengths' shape ((n,) for None); asynchronous on `stream` (default: torch's current stream).  Records of weight 0
+        and columns whose wavelength is outside [360, 830] or NaN get +0.0.  Changes no record and no counter."""
+        import torch
+        if isinstance(rays, dict):
+            rays = rays["rays"]
+        if not _is_torch(samples) or not _is_torch(rays):
+            raise ValueError("samples and rays must be device tensors (create_rays with a torch tensor)")
+        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
+            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
+        if samples.device.index != self.device:
+            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
+        n = samples.shape[0]
+        shape, k, w_ptr = (n,), 1, None
+        if wavelengths is not None:
+            if not _is_torch(wavelengths):
+                raise TypeError("torch samples need a torch wavelength tensor")
+            if (wavelengths.dtype != torch.float32 or wavelengths.dim() not in (1, 2) or wavelengths.shape[0] != n
+                    or not wavelengths.is_contiguous() or wavelengths.device != samples.device):
+                raise ValueError("wavelengths must be a contiguous (n,) or (n,k) float32 tensor on the samples' device")
+            shape = tuple(wavelengths.shape)
+            k = shape[1] if len(shape) == 2 else 1
+            w_ptr = wavelengths.data_ptr()
+        if tuple(rays.shape) != shape + (8,) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
+            raise ValueError("rays must be the contiguous %s float32 record tensor on the samples' device" % (shape + (8,),))
+        rs_ptr = None
+        if rng_states is not None:
+            if (not _is_torch(rng_states) or rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4)
+                    or not rng_states.is_contiguous() or rng_states.device != samples.device):
+                raise ValueError("rng_states must be a contiguous (n,4) int32/uint32 tensor on the samples' device")
+            rs_ptr = rng_states.data_ptr()
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=samples.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != samples.device:
+            raise ValueError("out must be a contiguous %s float32 tensor on the samples' device" % (shape,))
+        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        self._check(self._lib.zoic_ray_transmittance_device(self._h, n, k, samples.data_ptr(), w_ptr, rs_ptr, int(ray_index_base),
+                                                            rays.data_ptr(), out.data_ptr(), C.c_void_p(st)))
+        return out
+
+    def set_coatings(self, index, lambda0_nm):
+        """Single-layer coatings in FILE order (front to rear, as the prescription lists the interfaces): the film's index and the
+        wavelength (nm) at which it is a quarter wave thick, one per interface (a scalar lambda0_nm serves all); index 0: uncoated.
+        set_coatings(None, None) clears them."""
+        if index is None:
+            self._check(self._lib.zoic_camera_set_coatings(self._h, 0, None, None))
+            return
+        nc = np.ascontiguousarray(index, dtype=np.float32).reshape(-1)
+        l0 = np.ascontiguousarray(np.broadcast_to(np.asarray(lambda0_nm, dtype=np.float32).reshape(-1), nc.shape), dtype=np.float32)
+        self._check(self._lib.zoic_camera_set_coatings(self._h, nc.shape[0], nc.ctypes.data, l0.ctypes.data))
+
+    def coatings(self):
+        """The lens's film table (zoic_camera_get_coatings), trace order (rear first): dict of float32 arrays index (0: uncoated) and
+        lambda0_nm.  Works on a tables-only camera (device=-1)."""
+        n = self._lib.zoic_camera_get_coatings(self._h, 0, None, None)
+        if n < 0:
+            self._check(1)   # ZOIC_ERR_INVALID_ARGUMENT with the library's detail
+        a = {k: np.zeros(n, dtype=np.float32) for k in ("index", "lambda0_nm")}
+        self._lib.zoic_camera_get_coatings(self._h, n, a["index"].ctypes.data, a["lambda0_nm"].ctypes.data)
+        return a
+
     def tile(self, capacity, tid=0):
         """A ZoicTile of this camera (closed with the camera at the latest: ZoicCamera.close() closes the tiles still alive)."""
         return ZoicTile(self, capacity, tid)

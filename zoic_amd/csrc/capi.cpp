@@ -42,6 +42,7 @@
 #include "backward_spectral.hpp"
 #include "traceback.hpp"
 #include "traceback_jacobian.hpp"
+#include "transmittance.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
 
@@ -304,6 +305,7 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     std::vector<zoic_tile *> liveTiles;
     std::atomic<int> waitMode{ZOIC_WAIT_SPIN};   // zoic_camera_set_wait_mode: how a render thread waits for the resident kernel
     std::vector<float> abbeOverride;             // zoic_camera_set_abbe_numbers: V-numbers in file order (empty: the prescription's own)
+    std::vector<float> coatingIndex, coatingLambda0;   // zoic_camera_set_coatings: film index and lambda0 (nm) in file order (empty: uncoated)
     ReverseTable reverse{};                      // reverse.hpp: the projection table of the tables above (filled by every successful update)
     bool reverseOn = false;                      // zoic_camera_set_reverse_projection: zoic_camera_reverse_ray answers with it
     TraceBackTable traceBack{};                  // traceback.hpp: the trace-back table of the tables above (filled by every successful update)
@@ -794,6 +796,21 @@ void fill_spectral(const zoic_camera *cam, SpectralTable &W)
     }
 }
 
+// the film table of the camera's lens (transmittance.hpp), trace order: the override (file order, front first: reversed here) or all
+// uncoated
+void fill_film(const zoic_camera *cam, FilmTable &F)
+{
+    F = FilmTable{};
+    const size_t rows = cam->lens.rows.size();
+    const size_t n = std::min<size_t>(rows, kMaxSurfaces);
+    F.count = static_cast<int32_t>(n);
+    if (cam->coatingIndex.size() != rows) return;
+    for (size_t i = 0; i < n; ++i) {
+        F.index[i] = cam->coatingIndex[rows - 1 - i];
+        F.lambda0[i] = cam->coatingLambda0[rows - 1 - i];
+    }
+}
+
 // the lens rows (trace order) as the arrays the backward tables' fillers take
 struct FlatRows {
     int n;
@@ -1213,6 +1230,9 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
     if (p->lensModel == ZOIC_RAYTRACED && !cam->abbeOverride.empty() && cam->abbeOverride.size() != cam->lens.rows.size())
         return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_abbe_numbers: " + std::to_string(cam->abbeOverride.size()) +
                                                    " V-numbers for a lens of " + std::to_string(cam->lens.rows.size()) + " surfaces");
+    if (p->lensModel == ZOIC_RAYTRACED && !cam->coatingIndex.empty() && cam->coatingIndex.size() != cam->lens.rows.size())
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coatings: " + std::to_string(cam->coatingIndex.size()) +
+                                                   " coatings for a lens of " + std::to_string(cam->lens.rows.size()) + " surfaces");
 
     // camera->params = parms, zoic.cpp:1719
     cam->params.p = *p;
@@ -1535,6 +1555,67 @@ zoic_status zoic_camera_set_abbe_numbers(zoic_camera *cam, int count, const floa
         return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_abbe_numbers: " + std::to_string(count) + " V-numbers for a lens of " +
                                                    std::to_string(cam->lens.rows.size()) + " surfaces");
     cam->abbeOverride.assign(V, V + count);
+    return ZOIC_OK;
+}
+
+zoic_status zoic_ray_transmittance_device(zoic_camera *cam, uint64_t n, uint32_t k, const float *d_samples, const float *d_wavelengths,
+                                          const uint32_t *d_rng_states, uint64_t ray_index_base, const zoic_ray *d_rays,
+                                          float *d_transmittance, void *stream)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (k == 0 || k > ZOIC_HERO_MAX_WAVELENGTHS) return fail(ZOIC_ERR_INVALID_ARGUMENT, "k must be 1 ... ZOIC_HERO_MAX_WAVELENGTHS");
+    return forward_batch(
+        cam, n, {{"d_samples", d_samples, 16}, {"d_wavelengths", d_wavelengths, 4, k == 1}, {"d_rng_states", d_rng_states, 16, true},
+                 {"d_rays", d_rays, 16}, {"d_transmittance", d_transmittance, 4}},
+        [&]() -> zoic_status {
+            const hipStream_t st = static_cast<hipStream_t>(stream);
+            const int model = cam->params.p.lensModel;
+            if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS) {   // lensModel NONE: no ray, no light
+                ZOIC_HIP(hipMemsetAsync(d_transmittance, 0, n * k * sizeof(float), st));
+                return ZOIC_OK;
+            }
+            SpectralTable W;
+            fill_spectral(cam, W);
+            FilmTable F;
+            fill_film(cam, F);
+            return launch_status(launch_ray_transmittance(model, cam->kolb, W, F, cam->bokehDev, d_samples, d_wavelengths, d_rng_states,
+                                                          ray_index_base, n, k, reinterpret_cast<const RayRecord *>(d_rays), d_transmittance, st));
+        });
+}
+
+int zoic_camera_get_coatings(const zoic_camera *cam, int capacity, float *film_index, float *film_lambda0_nm)
+{
+    if (!cam) { fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL"); return -1; }
+    if (capacity < 0) { fail(ZOIC_ERR_INVALID_ARGUMENT, "capacity is negative"); return -1; }
+    FilmTable F;
+    fill_film(cam, F);
+    for (int i = 0; i < F.count && i < capacity; ++i) {
+        if (film_index) film_index[i] = F.index[i];
+        if (film_lambda0_nm) film_lambda0_nm[i] = F.lambda0[i];
+    }
+    return F.count;
+}
+
+zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *film_index, const float *film_lambda0_nm)
+{
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (count < 0 || count > ZOIC_MAX_LENS_SURFACES) return fail(ZOIC_ERR_INVALID_ARGUMENT, "count out of range");
+    if (count == 0) { cam->coatingIndex.clear(); cam->coatingLambda0.clear(); return ZOIC_OK; }
+    if (!film_index || !film_lambda0_nm) return fail(ZOIC_ERR_INVALID_ARGUMENT, "film_index and film_lambda0_nm must be non-NULL");
+    const bool loaded = cam->updated && cam->params.p.lensModel == ZOIC_RAYTRACED && !cam->lens.rows.empty();
+    if (loaded && static_cast<size_t>(count) != cam->lens.rows.size())
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coatings: " + std::to_string(count) + " coatings for a lens of " +
+                                                   std::to_string(cam->lens.rows.size()) + " surfaces");
+    for (int i = 0; i < count; ++i) {
+        if (film_index[i] == 0.0f) continue;   // uncoated: its lambda0 is not looked at
+        if (!std::isfinite(film_index[i]) || !(film_index[i] >= 1.0f) || !std::isfinite(film_lambda0_nm[i]) || !(film_lambda0_nm[i] > 0.0f))
+            return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coatings: entry " + std::to_string(i) +
+                                                       " needs a finite index >= 1 and a finite lambda0 > 0 (index 0: uncoated)");
+    }
+    cam->coatingIndex.assign(film_index, film_index + count);
+    cam->coatingLambda0.assign(film_lambda0_nm, film_lambda0_nm + count);
+    for (int i = 0; i < count; ++i)
+        if (cam->coatingIndex[i] == 0.0f) cam->coatingLambda0[i] = 0.0f;
     return ZOIC_OK;
 }
 

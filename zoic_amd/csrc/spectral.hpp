@@ -88,8 +88,13 @@ ZOIC_HD bool spectral_tir_possible(float ior1, float ior2) { return ior1 > ior2;
 
 // trace_lens_strict (optics.hpp) with the per-ray eta / tirPossible of every interface: the reference's arithmetic, operation for
 // operation; (o, d) are left as the reference leaves them on every exit path.  SP: pointer to the KolbTable's Surface array.
-template <class SP, class WP>
-ZOIC_HD bool trace_lens_spectral_strict(SP surf, WP W, int count, float dl, V3 &o, V3 &d, uint32_t &tirCount)
+// observe(i, ior1, ior2, eta, c1) is called at every interface the ray refracts at (after the clip and the total-reflection test): it
+// reads the trace's values and feeds nothing back (transmittance.hpp rides along here); the empty observer compiles away.
+struct NoInterfaceObserver {
+    ZOIC_HD void operator()(int, float, float, float, float) const {}
+};
+template <class SP, class WP, class Observe>
+ZOIC_HD bool trace_lens_spectral_strict_observed(SP surf, WP W, int count, float dl, V3 &o, V3 &d, uint32_t &tirCount, Observe &observe)
 {
     for (int ii = 0; ii < count; ++ii) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -123,10 +128,17 @@ ZOIC_HD bool trace_lens_spectral_strict(SP surf, WP W, int count, float dl, V3 &
             ++tirCount;
             return false;
         }
+        observe(i, ior1, ior2, eta, c1);
         float k = static_cast<float>(static_cast<double>(eta * c1) - sqrt(fabs(1.0 - static_cast<double>(cs2))));
         d = V3{u.x * eta + N.x * k, u.y * eta + N.y * k, u.z * eta + N.z * k};
     }
     return true;
+}
+template <class SP, class WP>
+ZOIC_HD bool trace_lens_spectral_strict(SP surf, WP W, int count, float dl, V3 &o, V3 &d, uint32_t &tirCount)
+{
+    NoInterfaceObserver none;
+    return trace_lens_spectral_strict_observed(surf, W, count, dl, o, d, tirCount, none);
 }
 
 // ---- launcher (spectral.hip) ----------------------------------------------------------------------------------------------
