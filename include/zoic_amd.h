@@ -16,7 +16,7 @@
  * thread with no sample in flight, and camera_create_ray concurrently from every render thread, zoic.cpp:1752):
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
- *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_create_rays_hero_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
+ *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_create_rays_hero_device, zoic_create_ghost_rays_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
  *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian (and their _spectral forms), zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
@@ -63,7 +63,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian and their
  *      _spectral forms (the trace-back with its Jacobian dPs / d(origin, dir)).
  *      Added later without a new number (additive): zoic_ray_transmittance_device, zoic_camera_set_coatings and
- *      zoic_camera_get_coatings (the Fresnel transmittance of traced rays, with single-layer coatings). */
+ *      zoic_camera_get_coatings (the Fresnel transmittance of traced rays, with single-layer coatings).
+ *      Added later without a new number (additive): zoic_create_ghost_rays_device and zoic_camera_get_ghost_pairs (ghost rays: the
+ *      two-reflection paths through the lens with their Fresnel weights), ZOIC_GHOST_MAX_PAIRS and the ZOIC_GHOST_* flag macros. */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -391,6 +393,55 @@ zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *f
 /* The film table of the camera's lens (works on a ZOIC_DEVICE_NONE camera): returns the surface count and writes up to `capacity`
  * entries, trace order (rear first), into the arrays that are not NULL; -1 for a NULL camera or a negative capacity. */
 int zoic_camera_get_coatings(const zoic_camera *cam, int capacity, float *film_index, float *film_lambda0_nm);
+/* ---- ghost rays (opt-in; csrc/ghost.hpp has the full definition) -------------------------------------------------------------------
+ * The light the transmittance above subtracts, followed: reflected at one interface and again at another it reaches the sensor as a
+ * ghost (flare discs, veiling glare).  One ghost belongs to one main record, one wavelength and one ordered pair of interfaces (a, b),
+ * trace-order indices (rear first), a > b: scene light that reflects first at b, then at a.  It is traced from the record's accepted try
+ * in three legs -- +z through interfaces 0 ... a-1 to a reflection at a, -z through a-1 ... b+1 to a reflection at b, +z through
+ * b+1 ... count-1 and out of the front element -- with the sphere, the housing / stop clip, the per-wavelength indices and the films
+ * of every interface visit, in one f32 arithmetic in every precision mode.
+ * d_ghosts receives n x p zoic_ray records, sample-major (record i * p + j: sample i, pair j).  A traced ghost: origin on the front
+ * interface and dir (unit length, dir.z < 0) out into the scene in the frame of the forward records, flags == ZOIC_GHOST_TRACED, and
+ * weight in (0, 1] = its Fresnel throughput only: the product of the transmittances of every refraction, each at its own angle (the
+ * interfaces between b and a are crossed three times), times R_a R_b, R = 1 - T of that interface from the incidence side, 1 where the
+ * reflection is total.  Multiply the main record's weight (and whatever else the renderer gives that record) in.
+ * A ghost that ends early: origin, dir and weight +0.0, bit 0 clear, ZOIC_GHOST_REASON(flags) one of the codes below,
+ * ZOIC_GHOST_INTERFACE(flags) the trace-order index and ZOIC_GHOST_LEG(flags) the leg (0, 1, 2) where it ended.  The reasons decided
+ * before the trace are tested in this order and carry interface 0, leg 0: MODEL, INVALID_PAIR, NO_START, WAVELENGTH; then NO_REFLECTION
+ * (interface a on leg 0, else b on leg 1), then NON_FINITE, then the trace's own.
+ * Pass what the forward call was given (d_samples, d_wavelengths, d_rng_states, ray_index_base) and what it wrote (d_rays, n records,
+ * k == 1): d_wavelengths == NULL for the records of zoic_create_rays_device (the d-line, 587.5618 nm), else those of
+ * zoic_create_rays_spectral_device.  pairs: p entries in HOST memory, 1 <= p <= ZOIC_GHOST_MAX_PAIRS, each a | b << 8; they are copied
+ * into the launch, so the array may be reused at once.  A pair with a <= b or an index past the lens is no error of the call: its column
+ * gets INVALID_PAIR.  More pairs are served by successive calls.
+ * It changes no record, no counter and no existing call.  The dispersion and film tables are read at the call.  Stream semantics,
+ * threading contract and pointer alignment as zoic_ray_transmittance_device (pairs 4-byte, d_ghosts 16-byte aligned).
+ * ZOIC_ERR_INVALID_ARGUMENT for p == 0 or p > ZOIC_GHOST_MAX_PAIRS (checked first, on every camera) and for a NULL or misaligned
+ * pointer (d_wavelengths and d_rng_states may be NULL); ZOIC_ERR_NO_DEVICE on a tables-only camera; ZOIC_ERR_NOT_UPDATED before an
+ * update; n = 0 returns ZOIC_OK. */
+#define ZOIC_GHOST_MAX_PAIRS 32
+#define ZOIC_GHOST_TRACED 0x1u
+#define ZOIC_GHOST_REASON(flags) (((flags) >> 8) & 0xFu)
+#define ZOIC_GHOST_INTERFACE(flags) (((flags) >> 16) & 0x3Fu)
+#define ZOIC_GHOST_LEG(flags) (((flags) >> 24) & 0x3u)
+#define ZOIC_GHOST_PAIR(a, b) ((uint32_t)(a) | ((uint32_t)(b) << 8))
+#define ZOIC_GHOST_MISS 1u           /* the path misses an interface's sphere */
+#define ZOIC_GHOST_CLIPPED 2u        /* outside a housing or the stop */
+#define ZOIC_GHOST_TIR 3u            /* totally reflected where it had to refract */
+#define ZOIC_GHOST_TURNED 4u         /* the ray no longer travels in its leg's direction */
+#define ZOIC_GHOST_NO_REFLECTION 5u  /* the two media of a or of b are equal at this wavelength (always so at the stop) */
+#define ZOIC_GHOST_NON_FINITE 6u     /* a NaN / inf start or result */
+#define ZOIC_GHOST_WAVELENGTH 7u     /* the wavelength is outside [360, 830] or NaN */
+#define ZOIC_GHOST_NO_START 8u       /* the main record has weight 0 */
+#define ZOIC_GHOST_MODEL 9u          /* THINLENS / NONE: a lens without interfaces has no ghosts */
+#define ZOIC_GHOST_INVALID_PAIR 10u  /* a <= b, or an index past the lens */
+zoic_status zoic_create_ghost_rays_device(zoic_camera *cam, uint64_t n, uint32_t p, const uint32_t *pairs, const float *d_samples,
+        const float *d_wavelengths, const uint32_t *d_rng_states, uint64_t ray_index_base, const zoic_ray *d_rays,
+        zoic_ray *d_ghosts, void *stream);
+/* The pairs that can make a ghost (works on a ZOIC_DEVICE_NONE camera): returns the number of pairs a > b whose two interfaces each
+ * separate unequal media at the d-line (0 for THINLENS / NONE and before an update) and writes up to `capacity` of them, packed
+ * a | b << 8, ordered by a, then b; -1 for a NULL camera or a negative capacity.  pairs may be NULL with capacity 0. */
+int zoic_camera_get_ghost_pairs(const zoic_camera *cam, int capacity, uint32_t *pairs);
 /* camera_create_ray(node, input, output, tid), zoic.cpp:1752: the per-sample signature.  No launch per call: the sample goes
  * to a resident kernel through mapped pinned memory (csrc/mailbox.hip; ~7 us per call; the kernel retires by itself after 1 ms
  * without a call and is started again by the next one).  Re-entrant: every tid owns a retry stream that carries over from call

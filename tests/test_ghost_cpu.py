@@ -1,0 +1,576 @@
+"""Ghost rays without a GPU: the C-ABI declares and exports the two calls and answers a tables-only camera as the header says, the
+arithmetic of csrc/ghost.hpp (compiled for the host) agrees with the pinned STRICT path on the plain refracting path and with the f64
+restatement in plain sphere geometry (ghost_ref.py) on every valid pair of C2 - C5, bare and coated, and the physics is what an
+optician expects: the on-axis closed form, the paraxial limit of the three legs, weaker ghosts under a coating.
+
+Starts: test_differentials_spectral_cpu._rays (~10 k passing rays per lens, C2 - C5) with _wavelengths.  The main starts pass by
+construction; most ghosts do not.  The measured figures are in the constants below and in the docstrings of the tests that took them."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from zoic_amd import _capi
+from zoic_amd.camera import LENS_DIR, ZoicCamera
+
+import ghost_ref as gref
+import transmittance_ref as tref
+from test_differentials_cpu import _clangxx
+from test_differentials_spectral_cpu import _rays, _wavelengths, tables
+from test_transmittance_cpu import FILM_INDEX, FILM_LAMBDA0, LENSES, films_where_media_differ, housings
+from test_transmittance_cpu import build_driver as build_transmittance_driver, run_driver as run_transmittance_driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
+NAMES = ("zoic_create_ghost_rays_device", "zoic_camera_get_ghost_pairs")
+F32 = np.float32
+LAMBDA_D32 = F32(587.5618)
+INVALID = _capi.STATUS_NAMES.index("ZOIC_ERR_INVALID_ARGUMENT")
+NO_DEVICE = _capi.STATUS_NAMES.index("ZOIC_ERR_NO_DEVICE")
+CFGS = ["C2", "C3", "C4", "C5"]
+MARGIN = 1e-4          # a ghost whose f64 path came closer than this (relative) to any decision may be left out ...
+MAX_LEFT_OUT = 0.02    # ... and at most this share of a lens's ghosts is
+
+# Plain path ("no pair"), C2 - C5 from the same starts: the largest |host build of ghost.hpp - host build of trace_lens_spectral_strict|
+# of the exit origin (cm) and of the unit exit direction, and |weight - path_transmittance| (clang++ 22, x86-64); asserted: 4 x them,
+# the project's margin for other compilers' host builds
+PLAIN_MEASURED = dict(origin=3.815e-6, dir=3.099e-6, weight=3.577e-7)     # all three on C4
+# Host build against the f64 restatement, every ghost both trace whose f64 margin is at least MARGIN, all valid pairs of C2 - C5, bare
+# and coated: the largest absolute error of the origin (cm), the direction and the weight; asserted: 4 x them
+MEASURED = dict(origin=1.557e-4, dir=1.643e-4, weight=5.274e-6)     # origin and dir on C4, weight on C3 bare
+
+
+def _bound(measured):
+    return {k: 4 * v for k, v in measured.items()}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
+# ---- the ABI --------------------------------------------------------------------------------------------------------------------
+def test_abi_declares_and_exports_the_calls():
+    header = open(os.path.join(ROOT, "include", "zoic_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    raw = ctypes.CDLL(_capi.LIB_PATH)
+    for name in NAMES:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _capi.SYMBOLS and hasattr(raw, name) and hasattr(_capi.load(), name), name
+        assert name in header.split("#define ZOIC_AMD_ABI_VERSION")[0], name       # the ABI note names it
+    assert len(_capi.SYMBOLS[NAMES[0]][1]) == 11 and len(_capi.SYMBOLS[NAMES[1]][1]) == 3
+    assert _capi.load().zoic_abi_version() == 5 and _capi.ABI_VERSION == 5
+    # the header's reason codes are the ones this file's restatement uses
+    for code, macro in enumerate(("MISS", "CLIPPED", "TIR", "TURNED", "NO_REFLECTION", "NON_FINITE", "WAVELENGTH", "NO_START", "MODEL",
+                                  "INVALID_PAIR"), 1):
+        assert re.search(r"#define ZOIC_GHOST_%s %du\b" % (macro, code), text), macro
+    assert re.search(r"#define ZOIC_GHOST_MAX_PAIRS 32\b", text)
+
+
+def _expected_pairs(disp):
+    n1 = disp["ior_d"]
+    differ = n1 != np.append(n1[1:], F32(1.0))
+    return np.array([(a, b) for a in range(len(n1)) for b in range(a) if differ[a] and differ[b]], np.int32).reshape(-1, 2)
+
+
+def test_tables_only_camera():
+    lib = _capi.load()
+    p, info, disp, surf, hs = tables("C2")
+    cam = ZoicCamera(device=-1)
+    assert cam.ghost_pairs().shape == (0, 2)                    # before an update
+    cam.update(**p)
+    pairs = cam.ghost_pairs()
+    assert pairs.dtype == np.int32 and np.array_equal(pairs, _expected_pairs(disp)) and len(pairs) == 21
+    g = lib.zoic_camera_get_ghost_pairs
+    assert g(None, 0, None) == -1 and g(cam._h, -1, None) == -1 and g(cam._h, 0, None) == 21
+    few = np.full(5, 0xFFFFFFFF, np.uint32)
+    assert g(cam._h, 3, few.ctypes.data) == 21                  # the count, whatever the capacity; no entry past it is written
+    assert np.array_equal(few[:3], pairs[:3, 0] | (pairs[:3, 1] << 8)) and (few[3:] == 0xFFFFFFFF).all()
+    f = lib.zoic_create_ghost_rays_device
+    one = np.array([1 | 0 << 8], np.uint32)
+    for bad_p in (0, 33):         # checked first, on every camera
+        assert f(cam._h, 64, bad_p, one.ctypes.data, None, None, None, 0, None, None, None) == INVALID
+        assert f(cam._h, 0, bad_p, one.ctypes.data, None, None, None, 0, None, None, None) == INVALID
+    assert f(None, 64, 1, one.ctypes.data, None, None, None, 0, None, None, None) == INVALID
+    assert f(cam._h, 64, 1, one.ctypes.data, None, None, None, 0, None, None, None) == NO_DEVICE
+    assert f(cam._h, 0, 1, None, None, None, None, 0, None, None, None) == NO_DEVICE
+    cam.update(**dict(p, lensModel=0))
+    assert cam.ghost_pairs().shape == (0, 2)                    # a thin lens has no interfaces
+    cam.close()
+
+
+@pytest.mark.parametrize("lens", LENSES)
+def test_pair_list_of_the_shipped_lenses(lens):
+    p = tables("C2")[0]
+    cam = ZoicCamera(device=-1)
+    cam.update(**dict(p, lensDataPath=os.path.join(LENS_DIR, lens)))
+    disp, count, stop = cam.dispersion(), cam.info()["lensCount"], cam.info()["apertureElement"]
+    pairs = cam.ghost_pairs()
+    cam.close()
+    assert np.array_equal(pairs, _expected_pairs(disp))
+    assert len(pairs) >= 3 and (pairs[:, 0] > pairs[:, 1]).all() and pairs.max() < count and not (pairs == stop).any()
+    if lens == "tessar_f2.8.dat":
+        assert count == 8 and len(pairs) == 21                  # 8 surfaces, one of them the stop: 7 choose 2
+
+
+# ---- the host driver ------------------------------------------------------------------------------------------------------------
+DRIVER = r"""
+#include "ghost.hpp"
+using namespace zoic;
+// rows: count x (radius, thickness, aperture); media: count x (iorD, cauchyB, filmIndex, filmLambda0)
+static void tables(int model, int count, const float *rows, int stop, float user, const float *media, GhostTable &G, GhostMedia &M)
+{
+    float radius[kMaxSurfaces] = {}, thickness[kMaxSurfaces] = {}, aperture[kMaxSurfaces] = {};
+    M = GhostMedia{};
+    for (int i = 0; i < count && i < kMaxSurfaces; ++i) {
+        radius[i] = rows[3 * i]; thickness[i] = rows[3 * i + 1]; aperture[i] = rows[3 * i + 2];
+        M.iorD[i] = media[4 * i]; M.cauchyB[i] = media[4 * i + 1]; M.filmIndex[i] = media[4 * i + 2]; M.filmLambda0[i] = media[4 * i + 3];
+    }
+    fill_ghost_table(G, model, count, radius, thickness, aperture, stop, user);
+}
+static void put(float *out, const GhostRay &g)
+{
+    out[0] = g.ox; out[1] = g.oy; out[2] = g.oz; out[3] = g.dx; out[4] = g.dy; out[5] = g.dz; out[6] = g.weight;
+    __builtin_memcpy(out + 7, &g.flags, 4);
+}
+// ghost_trace of one pair (a = b = -1: the plain path) from n starts; out: n x 8
+extern "C" int zgh_trace(int model, int count, const float *rows, int stop, float user, const float *media, int a, int b, int n,
+                         const float *lambda, const float *o, const float *d, float *out)
+{
+    GhostTable G; GhostMedia M;
+    tables(model, count, rows, stop, user, media, G, M);
+    const GhostTable *GP = &G; const GhostMedia *MP = &M;
+    for (int r = 0; r < n; ++r)
+        put(out + 8 * r, ghost_trace(GP, MP, a, b, lambda[r], V3{o[3 * r], o[3 * r + 1], o[3 * r + 2]}, V3{d[3 * r], d[3 * r + 1], d[3 * r + 2]}));
+    return G.model;
+}
+// ghost_record of p packed pairs from n starts, as the kernel calls it; have: n bytes (the main record has weight); out: n x p x 8
+extern "C" int zgh_records(int model, int count, const float *rows, int stop, float user, const float *media, int p, const uint32_t *pairs,
+                           int n, const float *lambda, const float *o, const float *d, const unsigned char *have, float *out)
+{
+    GhostTable G; GhostMedia M;
+    tables(model, count, rows, stop, user, media, G, M);
+    const GhostTable *GP = &G; const GhostMedia *MP = &M;
+    for (int r = 0; r < n; ++r)
+        for (int j = 0; j < p; ++j)
+            put(out + 8 * (static_cast<size_t>(r) * p + j), ghost_record(GP, MP, pairs[j], have[r] != 0, lambda[r], V3{o[3 * r], o[3 * r + 1], o[3 * r + 2]},
+                                                                         V3{d[3 * r], d[3 * r + 1], d[3 * r + 2]}));
+    return G.model;
+}
+// the pinned STRICT path from the same starts: surf count x (center, radius2, sign, housing2); out: n x 7 (o, d as the trace leaves
+// them, 1.0 where it passes)
+extern "C" int zgh_strict(int count, const float *surf, const float *disp, int n, const float *lambda, const float *o, const float *d, float *out)
+{
+    Surface S[kMaxSurfaces] = {};
+    SpectralTable W = {};
+    W.count = count;
+    for (int i = 0; i < count; ++i) {
+        S[i].center = surf[4 * i]; S[i].radius2 = surf[4 * i + 1]; S[i].sign = surf[4 * i + 2]; S[i].housing2 = surf[4 * i + 3];
+        W.iorD[i] = disp[2 * i]; W.cauchyB[i] = disp[2 * i + 1];
+    }
+    const Surface *SP = S; const SpectralTable *WP = &W;
+    int passed = 0;
+    for (int r = 0; r < n; ++r) {
+        V3 po{o[3 * r], o[3 * r + 1], o[3 * r + 2]}, pd{d[3 * r], d[3 * r + 1], d[3 * r + 2]};
+        uint32_t tir = 0;
+        const bool ok = trace_lens_spectral_strict(SP, WP, count, spectral_dl(lambda[r]), po, pd, tir);
+        passed += ok ? 1 : 0;
+        float *q = out + 7 * r;
+        q[0] = po.x; q[1] = po.y; q[2] = po.z; q[3] = pd.x; q[4] = pd.y; q[5] = pd.z; q[6] = ok ? 1.0f : 0.0f;
+    }
+    return passed;
+}
+"""
+
+
+def build_driver(directory):
+    """the host build of csrc/ghost.hpp (shared with tests/test_ghost_gpu.py)"""
+    src, so = os.path.join(str(directory), "driver.cpp"), os.path.join(str(directory), "driver.so")
+    with open(src, "w") as f:
+        f.write(DRIVER)
+    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
+                           "-I" + os.path.join(ROOT, "include"), src, "-o", so])
+    return ctypes.CDLL(so)
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    return build_driver(tmp_path_factory.mktemp("ghostdriver"))
+
+
+def _tables_args(L, disp, film):
+    count = L["count"]
+    rows = np.stack([L["radius"], L["thickness"], L["aperture"]], 1)
+    fl = (np.zeros(count, F32), np.zeros(count, F32)) if film is None else film
+    media = np.stack([disp["ior_d"], disp["cauchy_b"], fl[0], fl[1]], 1)
+    return [np.ascontiguousarray(a, F32) for a in (rows, media)]
+
+
+def run_trace(drv, L, disp, lam, o, d, a, b, film=None, model=1):
+    """(n, 8) float32 records of ghost_trace for one pair ((-1, -1): the plain path); L = ghost_ref.lens(info)"""
+    fp = ctypes.POINTER(ctypes.c_float)
+    keep = _tables_args(L, disp, film) + [np.ascontiguousarray(v, F32) for v in (lam, o, d)]
+    n = len(keep[3])
+    out = np.full((n, 8), np.nan, F32)
+    drv.zgh_trace(int(model), L["count"], keep[0].ctypes.data_as(fp), int(L["stop"]), ctypes.c_float(float(L["user"])), keep[1].ctypes.data_as(fp),
+                  int(a), int(b), n, keep[2].ctypes.data_as(fp), keep[3].ctypes.data_as(fp), keep[4].ctypes.data_as(fp), out.ctypes.data_as(fp))
+    return out
+
+
+def run_records(drv, L, disp, lam, o, d, pairs, have=None, film=None, model=1):
+    """(n, p, 8) float32 records of ghost_record, the call's columns: pairs (p, 2) of (a, b) or (p,) packed, have (n,) bool"""
+    fp = ctypes.POINTER(ctypes.c_float)
+    keep = _tables_args(L, disp, film) + [np.ascontiguousarray(v, F32) for v in (lam, o, d)]
+    n = len(keep[3])
+    pairs = np.asarray(pairs)
+    packed = np.ascontiguousarray(pairs if pairs.ndim == 1 else pairs[:, 0].astype(np.uint32) | (pairs[:, 1].astype(np.uint32) << 8), np.uint32)
+    hv = np.ones(n, np.uint8) if have is None else np.ascontiguousarray(have, np.uint8)
+    out = np.full((n, len(packed), 8), np.nan, F32)
+    drv.zgh_records(int(model), L["count"], keep[0].ctypes.data_as(fp), int(L["stop"]), ctypes.c_float(float(L["user"])), keep[1].ctypes.data_as(fp),
+                    len(packed), packed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, keep[2].ctypes.data_as(fp), keep[3].ctypes.data_as(fp),
+                    keep[4].ctypes.data_as(fp), hv.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.ctypes.data_as(fp))
+    return out
+
+
+def split(rec):
+    """(origin, dir, weight, flags, reason, interface, leg) of records (..., 8)"""
+    flags = _bits(rec[..., 7])
+    traced = (flags & 1) != 0
+    reason = np.where(traced, 0, (flags >> 8) & 0xF).astype(np.int64)
+    return rec[..., 0:3], rec[..., 3:6], rec[..., 6], flags, reason, ((flags >> 16) & 0x3F).astype(np.int64), ((flags >> 24) & 3).astype(np.int64)
+
+
+_LENS = {}
+
+
+def _lens(cfg):
+    if cfg not in _LENS:
+        p, info, disp, surf, hs = tables(cfg)
+        _LENS[cfg] = gref.lens(info), disp, surf, info
+    return _LENS[cfg]
+
+
+# ---- the plain path against the pinned STRICT trace -----------------------------------------------------------------------------
+_PLAIN = {}
+
+
+def _plain(cfg, driver, oracle_lib):
+    if cfg not in _PLAIN:
+        L, disp, surf, info = _lens(cfg)
+        o, d = _rays(cfg, oracle_lib)
+        lam = _wavelengths(len(o))
+        got = run_trace(driver, L, disp, lam, o, d, -1, -1)
+        go, gd, gw, flags, _, _, _ = split(got)
+        s4 = np.ascontiguousarray(np.stack([surf[:, 0], surf[:, 1], surf[:, 2], housings(info)], 1), F32)
+        dp = np.ascontiguousarray(np.stack([disp["ior_d"], disp["cauchy_b"]], 1), F32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        o32, d32 = np.ascontiguousarray(o, F32), np.ascontiguousarray(d, F32)
+        ref = np.zeros((len(o), 7), F32)
+        driver.zgh_strict(len(surf), s4.ctypes.data_as(fp), dp.ctypes.data_as(fp), len(o), lam.ctypes.data_as(fp), o32.ctypes.data_as(fp),
+                          d32.ctypes.data_as(fp), ref.ctypes.data_as(fp))
+        # the starts pass at the d-line; at their own wavelengths a few are clipped, in both arithmetics.  The two may differ on a ray
+        # that STRICT's rounding decides: at the stop's |R| ~ 1e4 sphere its noise reaches 5e-3 of housing2 (lens_system.cpp
+        # fill_surfaces has the estimate, eps |R| / r_stop); beyond that margin of the f64 path they must agree
+        passes, traced = ref[:, 6] != 0, flags == 1
+        margin = gref.ghost(L, disp, lam, o, d, -1, -1)["margin"]
+        assert np.array_equal(passes[margin >= 5e-3], traced[margin >= 5e-3]) and (passes != traced).mean() <= 1e-3
+        both = passes & traced
+        assert both.mean() >= 0.98, (cfg, both.mean())
+        ro, rd = ref[both, 0:3].astype(np.float64), ref[both, 3:6].astype(np.float64)
+        rd /= np.linalg.norm(rd, axis=1, keepdims=True)
+        _PLAIN[cfg] = dict(origin=float(np.abs(-go[both].astype(np.float64) - ro).max()), dir=float(np.abs(-gd[both].astype(np.float64) - rd).max()),
+                           got_w=gw, lam=lam, o=o, d=d, both=both)
+    return _PLAIN[cfg]
+
+
+def _plain_weight_error(cfg, driver, oracle_lib, tdriver):
+    m = _plain(cfg, driver, oracle_lib)
+    if "weight" not in m:
+        L, disp, surf, info = _lens(cfg)
+        t = run_transmittance_driver(tdriver, surf, disp, m["lam"], m["o"], m["d"], None, housings(info))
+        m["weight"] = float(np.abs(m["got_w"].astype(np.float64) - t)[m["both"]].max())
+        print(cfg, "plain path:", {k: m[k] for k in ("origin", "dir", "weight")})
+    return m
+
+
+@pytest.fixture(scope="module")
+def tdriver(tmp_path_factory):
+    return build_transmittance_driver(tmp_path_factory.mktemp("ghost_transdriver"))
+
+
+@pytest.mark.parametrize("cfg", CFGS)
+def test_plain_path_is_the_strict_path(cfg, driver, tdriver, oracle_lib):
+    """"no pair" from every start: exit origin and unit direction against the host build of trace_lens_spectral_strict, the weight
+    against the host build of path_transmittance, within 4 x PLAIN_MEASURED"""
+    m = _plain_weight_error(cfg, driver, oracle_lib, tdriver)
+    bound = _bound(PLAIN_MEASURED)
+    for k in ("origin", "dir", "weight"):
+        assert m[k] <= bound[k], (cfg, k, m[k])
+
+
+def test_plain_measured_is_the_measured_one(driver, tdriver, oracle_lib):
+    for k in ("origin", "dir", "weight"):
+        worst = max(_plain_weight_error(cfg, driver, oracle_lib, tdriver)[k] for cfg in CFGS)
+        assert PLAIN_MEASURED[k] / 4 <= worst <= 4 * PLAIN_MEASURED[k], (k, worst)
+
+
+# ---- the host build against the f64 restatement ---------------------------------------------------------------------------------
+_AGAINST = {}
+
+
+def _against(cfg, coated, driver, oracle_lib):
+    """every valid pair of the lens from every start: the census and the errors"""
+    key = (cfg, coated)
+    if key not in _AGAINST:
+        L, disp, surf, info = _lens(cfg)
+        o, d = _rays(cfg, oracle_lib)
+        lam = _wavelengths(len(o))
+        film = films_where_media_differ(disp) if coated else None
+        pairs = _expected_pairs(disp)
+        got = run_records(driver, L, disp, lam, o, d, pairs, film=film)
+        seen = np.zeros(len(gref.REASONS), np.int64)
+        err = dict(origin=0.0, dir=0.0, weight=0.0)
+        left_out = wrong = 0
+        for j, (a, b) in enumerate(pairs):
+            ref = gref.ghost(L, disp, lam, o, d, int(a), int(b), *(film or (None, None)))
+            go, gd, gw, flags, reason, iface, leg = split(got[:, j])
+            sure = ref["margin"] >= MARGIN
+            left_out += int((~sure).sum())
+            same = (reason == ref["reason"]) & (iface == ref["interface"]) & (leg == ref["leg"])
+            wrong += int((sure & ~same).sum())
+            seen += np.bincount(reason, minlength=len(seen))
+            dead = reason != 0
+            assert not _bits(got[:, j, :7][dead]).any()                                   # +0.0 everywhere
+            both = sure & (reason == 0) & (ref["reason"] == 0)
+            if both.any():
+                err["origin"] = max(err["origin"], float(np.abs(go[both] - ref["origin"][both]).max()))
+                err["dir"] = max(err["dir"], float(np.abs(gd[both] - ref["dir"][both]).max()))
+                err["weight"] = max(err["weight"], float(np.abs(gw[both] - ref["weight"][both]).max()))
+        total = len(o) * len(pairs)
+        _AGAINST[key] = dict(pairs=len(pairs), ghosts=total, seen=seen, err=err, left_out=left_out / total, wrong=wrong, records=got)
+        print(cfg, "coated" if coated else "bare", dict(pairs=len(pairs), ghosts=total, left_out=left_out / total, wrong=wrong, err=err,
+                                                        seen=dict(zip(gref.REASONS, seen.tolist()))))
+    return _AGAINST[key]
+
+
+@pytest.mark.parametrize("coated", [False, True], ids=["bare", "film"])
+@pytest.mark.parametrize("cfg", CFGS)
+def test_host_build_against_f64(cfg, coated, driver, oracle_lib):
+    """every valid pair, every start: reason, interface and leg equal for every ghost whose f64 margin is at least 1e-4 (at most 2 % of
+    a lens's ghosts lie below and are left out); origin, direction and weight of the ghosts both trace within 4 x MEASURED; per lens at
+    least 1000 traced and 100 clipped ghosts.  Measured (clang++ 22, x86-64; the paths are the same bare and coated):
+
+                pairs  ghosts   traced   miss / clipped / TIR / turned      below 1e-4   origin cm  dir       weight bare / film
+        C2      21     210 000   93 898        0 / 114 378 /  1 724 /     0   0.028 %      3.87e-6    1.40e-6   4.39e-9 / 2.85e-9
+        C3      45     450 000  193 685   23 510 / 181 496 / 51 041 /   268   0.049 %      5.99e-5    1.79e-5   5.27e-6 / 1.20e-6
+        C4      55     550 000   91 661  163 235 / 217 874 / 70 943 / 6 287   0.031 %      1.56e-4    1.64e-4   6.13e-8 / 1.04e-8
+        C5      45     450 000  177 837      289 / 268 682 /  3 192 /     0   0.020 %      5.04e-6    7.71e-7   3.11e-9 / 3.01e-9
+
+    No ghost above the margin differs in reason, interface or leg.  The largest errors are MEASURED; they belong to ghosts that graze
+    an interface.  Plain path (test_plain_path_is_the_strict_path), origin / dir / weight: C2 7.93e-7 / 2.35e-7 / 1.79e-7, C3 1.55e-6 /
+    5.12e-7 / 2.38e-7, C4 3.81e-6 / 3.10e-6 / 3.58e-7, C5 9.83e-7 / 2.01e-7 / 1.79e-7."""
+    m = _against(cfg, coated, driver, oracle_lib)
+    assert m["left_out"] <= MAX_LEFT_OUT, m["left_out"]
+    assert m["wrong"] == 0, m["wrong"]
+    bound = _bound(MEASURED)
+    for k in ("origin", "dir", "weight"):
+        assert m["err"][k] <= bound[k], (cfg, k, m["err"][k])
+    assert m["seen"][gref.TRACED] >= 1000 and m["seen"][gref.CLIPPED] >= 100, m["seen"]
+
+
+def test_measured_is_the_measured_one(driver, oracle_lib):
+    for k in ("origin", "dir", "weight"):
+        worst = max(_against(cfg, coated, driver, oracle_lib)["err"][k] for cfg in CFGS for coated in (False, True))
+        assert MEASURED[k] / 4 <= worst <= 4 * MEASURED[k], (k, worst)
+
+
+def _by_hand(driver):
+    """the reasons the corpus cannot reach, each on one row: (name, got record (8,), expected reason, interface, leg)"""
+    L, disp, surf, info = _lens("C2")
+    el = info["elements"]
+    o = np.array([[0.0, 0.0, info["originShift"]]], F32)
+    axis = np.array([[0.0, 0.0, -el[0, 1]]], F32)
+    pairs = _expected_pairs(disp)
+    a, b = (int(v) for v in pairs[-1])
+    stop = L["stop"]
+    lam = np.array([LAMBDA_D32])
+    past = np.array([[el[0, 3] * 0.6, 0.0, -el[0, 1]]], F32)           # aimed 1.2 housing radii off the axis of the rear element
+    out = [("clipped", run_records(driver, L, disp, lam, o, past, [(a, b)])[0, 0], gref.CLIPPED, 0, 0),
+           ("invalid a == b", run_records(driver, L, disp, lam, o, axis, [(a, a)])[0, 0], gref.INVALID_PAIR, 0, 0),
+           ("invalid a < b", run_records(driver, L, disp, lam, o, axis, [(b, a)])[0, 0], gref.INVALID_PAIR, 0, 0),
+           ("invalid past the lens", run_records(driver, L, disp, lam, o, axis, [(L["count"], 0)])[0, 0], gref.INVALID_PAIR, 0, 0),
+           ("invalid high bits", run_records(driver, L, disp, lam, o, axis, np.array([a | b << 8 | 1 << 16], np.uint32))[0, 0], gref.INVALID_PAIR, 0, 0),
+           ("300 nm", run_records(driver, L, disp, np.array([300.0], F32), o, axis, [(a, b)])[0, 0], gref.WAVELENGTH, 0, 0),
+           ("NaN nm", run_records(driver, L, disp, np.array([np.nan], F32), o, axis, [(a, b)])[0, 0], gref.WAVELENGTH, 0, 0),
+           ("no start", run_records(driver, L, disp, lam, o, axis, [(a, b)], have=[False])[0, 0], gref.NO_START, 0, 0),
+           ("thin lens", run_records(driver, L, disp, lam, o, axis, [(a, b)], model=0)[0, 0], gref.MODEL, 0, 0),
+           ("no lens", run_records(driver, L, disp, lam, o, axis, [(a, b)], model=2)[0, 0], gref.MODEL, 0, 0),
+           ("NaN start", run_records(driver, L, disp, lam, o * np.nan, axis, [(a, b)])[0, 0], gref.NON_FINITE, 0, 0),
+           ("no direction", run_records(driver, L, disp, lam, o, axis * 0, [(a, b)])[0, 0], gref.NON_FINITE, 0, 0)]
+    if stop < a:
+        out.append(("b on the stop", run_records(driver, L, disp, lam, o, axis, [(a, stop)])[0, 0], gref.NO_REFLECTION, stop, 1))
+    if stop > b:
+        out.append(("a on the stop", run_records(driver, L, disp, lam, o, axis, [(stop, b)])[0, 0], gref.NO_REFLECTION, stop, 0))
+    return out
+
+
+def test_reasons_built_by_hand(driver):
+    """a one-row start aimed past a housing, invalid pairs, 300 nm, a pair on the stop, a record without weight, the other lens models,
+    a NaN start: the documented flag word and +0.0 everywhere else"""
+    cases = _by_hand(driver)
+    assert {c[2] for c in cases} >= {gref.CLIPPED, gref.INVALID_PAIR, gref.WAVELENGTH, gref.NO_START, gref.MODEL, gref.NON_FINITE, gref.NO_REFLECTION}
+    for name, rec, reason, iface, leg in cases:
+        assert _bits(rec[7:8])[0] == gref.flag_word(reason, iface, leg), (name, hex(int(_bits(rec[7:8])[0])))
+        assert not _bits(rec[:7]).any(), name
+
+
+def test_every_reason_is_seen(driver, oracle_lib):
+    """over the corpus runs and the hand-built rows every reason the header defines occurs at least once"""
+    seen = sum(_against(cfg, coated, driver, oracle_lib)["seen"] for cfg in CFGS for coated in (False, True))
+    for c in _by_hand(driver):
+        seen[c[2]] += 1
+    assert (seen > 0).all(), dict(zip(gref.REASONS, seen.tolist()))
+
+
+def test_restatement_alone_keeps_the_left_out_share():
+    """the f64 restatement by itself, on starts made here without the host build: the share of ghosts below the margin stays under the
+    cap on the lens with the most pairs"""
+    L, disp, surf, info = _lens("C3")
+    el = info["elements"]
+    rs = np.random.RandomState(3)
+    n = 2000
+    o = np.stack([rs.uniform(-0.5, 0.5, n), rs.uniform(-0.5, 0.5, n), np.full(n, info["originShift"])], 1).astype(F32)
+    r = 0.45 * el[0, 3] * np.sqrt(rs.uniform(0, 1, n))
+    phi = rs.uniform(0, 2 * np.pi, n)
+    d = np.stack([r * np.cos(phi) - o[:, 0], r * np.sin(phi) - o[:, 1], np.full(n, -el[0, 1])], 1).astype(F32)
+    lam = _wavelengths(n)
+    pairs = _expected_pairs(disp)
+    below = sum(int((gref.ghost(L, disp, lam, o, d, int(a), int(b))["margin"] < MARGIN).sum()) for a, b in pairs)
+    assert below <= MAX_LEFT_OUT * n * len(pairs), below / (n * len(pairs))
+
+
+# ---- physics that does not lean on the restatement ------------------------------------------------------------------------------
+@pytest.mark.parametrize("lens", LENSES)
+def test_axial_ray_is_the_closed_form(lens, driver):
+    """a start on the axis along the axis, bare, at lambda_d, every valid pair of every shipped prescription: origin and dir on the axis
+    and weight = R_a R_b prod_{i<b} T_i . T_b . prod_{b<i<a} T_i^3 . T_a . prod_{i>a} T_i with the normal-incidence T_i on the camera's
+    own ior_d -- a is crossed on the way out after its reflection, b after its own; to the bound"""
+    p, info, disp, surf, hs = tables("C2", lensDataPath=os.path.join(LENS_DIR, lens))
+    L = gref.lens(info)
+    o = np.array([[0.0, 0.0, info["originShift"]]], F32)
+    d = np.array([[0.0, 0.0, -info["elements"][0, 1]]], F32)
+    pairs = _expected_pairs(disp)
+    got = run_records(driver, L, disp, np.array([LAMBDA_D32]), o, d, pairs)[0]
+    n1 = disp["ior_d"].astype(np.float64)
+    n2 = np.append(n1[1:], 1.0)
+    T = 1.0 - ((n1 - n2) / (n1 + n2)) ** 2
+    R = 1.0 - T
+    go, gd, gw, flags, _, _, _ = split(got)
+    assert (flags == 1).all(), flags
+    zfront = float(L["vertex"][-1])
+    for j, (a, b) in enumerate(pairs):
+        want = R[a] * R[b] * np.prod(T[:b]) * T[b] * np.prod(T[b + 1:a] ** 3) * T[a] * np.prod(T[a + 1:])
+        assert abs(float(gw[j]) - want) <= _bound(MEASURED)["weight"], (lens, a, b, float(gw[j]), want)
+        assert go[j, 0] == 0 and go[j, 1] == 0 and abs(float(go[j, 2]) + zfront) <= _bound(MEASURED)["origin"]
+        assert gd[j, 0] == 0 and gd[j, 1] == 0 and abs(float(gd[j, 2]) + 1.0) <= _bound(MEASURED)["dir"]
+
+
+def _paraxial_pairs(disp, stop):
+    """a pair with a non-empty leg 1 that straddles the stop, and a pair of neighbours (a == b + 1)"""
+    pairs = _expected_pairs(disp)
+    far = [tuple(p) for p in pairs if p[0] - p[1] >= 3 and p[1] < stop < p[0]]
+    near = [tuple(p) for p in pairs if p[0] == p[1] + 1]
+    return far[0], near[0]
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["leg1", "neighbours"])
+def test_paraxial_limit(which):
+    """at heights h, h/2 and h/4 the f64 restatement's exit height and slope approach the product of the refraction, transfer and
+    reflection matrices of the three legs; the difference is of third order, so successive differences fall by 8 (asserted: 6 ... 10).
+    This pins the root, the normal and the sign conventions without the restatement judging itself."""
+    L, disp, surf, info = _lens("C2")
+    a, b = (int(v) for v in _paraxial_pairs(disp, L["stop"])[which])
+    index = np.append(disp["ior_d"].astype(np.float64), 1.0)
+    z0 = float(info["originShift"])
+    zrear, zfront = float(L["vertex"][0]), float(L["vertex"][-1])
+    h = 0.02 * float(np.sqrt(L["housing2"].min()))
+    slope = 0.3 * h / (zrear - z0)
+    diffs = []
+    for k in (1.0, 0.5, 0.25):
+        o = np.array([[0.0, k * h, z0]])
+        d = np.array([[0.0, k * slope, 1.0]])
+        g = gref.ghost(L, disp, [LAMBDA_D32], o, d, a, b)
+        assert g["reason"][0] == gref.TRACED
+        y0 = k * h + k * slope * (zrear - z0)                       # at the rear vertex plane
+        py, ps = gref.paraxial(L, index, a, b, y0, k * slope)
+        # the restatement's exit point lies on the front cap: bring it to the front vertex plane along its direction
+        p, u = -g["origin"][0], -g["dir"][0]
+        y = p[1] + u[1] / u[2] * (zfront - p[2])
+        diffs.append((abs(y - py), abs(u[1] / u[2] - ps)))
+        assert abs(py) > 1e-6 and abs(ps) > 1e-6
+    for col in (0, 1):
+        r1, r2 = diffs[0][col] / diffs[1][col], diffs[1][col] / diffs[2][col]
+        assert 6 <= r1 <= 10 and 6 <= r2 <= 10, (a, b, col, diffs)
+
+
+def test_coatings_weaken_every_glass_air_ghost(driver, oracle_lib):
+    """the 1.38-index quarter-wave film at 550 nm on every glass-air interface: at 550 nm the median weight of every pair of two
+    glass-air interfaces is below its bare median"""
+    L, disp, surf, info = _lens("C2")
+    o, d = _rays("C2", oracle_lib)
+    n1 = disp["ior_d"]
+    n2 = np.append(n1[1:], F32(1.0))
+    glass_air = (n1 != n2) & ((n1 == 1) | (n2 == 1))
+    pairs = np.array([p for p in _expected_pairs(disp) if glass_air[p[0]] and glass_air[p[1]]])
+    assert len(pairs) >= 6
+    film = (np.where(glass_air, FILM_INDEX, F32(0)).astype(F32), np.where(glass_air, FILM_LAMBDA0, F32(0)).astype(F32))
+    lam = np.full(len(o), 550.0, F32)
+    bare, coat = run_records(driver, L, disp, lam, o, d, pairs), run_records(driver, L, disp, lam, o, d, pairs, film=film)
+    checked = 0
+    for j in range(len(pairs)):
+        tb, tc = _bits(bare[:, j, 7]) == 1, _bits(coat[:, j, 7]) == 1
+        assert np.array_equal(tb, tc)                              # a film changes no path
+        if tb.sum() < 50:
+            continue
+        assert np.median(coat[tc, j, 6]) < np.median(bare[tb, j, 6]), pairs[j]
+        checked += 1
+    assert checked >= 3
+
+
+@pytest.mark.parametrize("cfg", CFGS)
+def test_traced_records(cfg, driver, oracle_lib):
+    """every traced ghost of the corpus runs: 0 < weight <= 1, unit dir with dir.z < 0 in the record frame, origin on the front cap
+    within its housing"""
+    L, disp, surf, info = _lens(cfg)
+    for coated in (False, True):
+        rec = _against(cfg, coated, driver, oracle_lib)["records"].reshape(-1, 8)
+        rec = rec[_bits(rec[:, 7]) == 1].astype(np.float64)
+        assert len(rec) >= 1000
+        w = rec[:, 6]
+        assert (w > 0).all() and (w <= 1).all()
+        assert (rec[:, 5] < 0).all() and np.abs(np.linalg.norm(rec[:, 3:6], axis=1) - 1).max() <= 1e-5
+        R, zv = float(L["radius"][-1]), float(L["vertex"][-1])
+        p = -rec[:, 0:3]                                            # trace frame
+        assert (p[:, 0] ** 2 + p[:, 1] ** 2 <= float(L["housing2"][-1])).all()
+        on_sphere = np.abs(np.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2 + (p[:, 2] - (zv - R)) ** 2) - abs(R))
+        assert on_sphere.max() <= 1e-5 * max(1.0, abs(zv)) + 4 * _bound(MEASURED)["origin"], on_sphere.max()
+        assert (np.sign(R) * (p[:, 2] - (zv - R)) > 0).all()        # the vertex-side cap
+
+
+def test_ghost_kernels_budget():
+    """0 scratch, 0 VGPR spills and at most 128 VGPRs for the ghost kernels of the built library (its code object's metadata); the kernel
+    arguments fit their 4 KB"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import code_object_regs
+    finally:
+        sys.path.pop(0)
+    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "ghost" in k}
+    assert len(res) == 2, sorted(res)
+    for k, v in res.items():
+        assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)
+        assert v["vgpr"] + v["agpr"] <= 128, (k, v)
+        assert v["kernarg"] <= 4096, (k, v)

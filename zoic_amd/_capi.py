@@ -113,6 +113,8 @@ SYMBOLS = {
     "zoic_ray_transmittance_device": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "zoic_camera_set_coatings": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "zoic_camera_get_coatings": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "zoic_create_ghost_rays_device": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "zoic_camera_get_ghost_pairs": (C.c_int, [_vp, C.c_int, _vp]),
     "zoic_camera_create_ray": (C.c_int, [_vp, C.POINTER(CameraInput), C.POINTER(CameraOutput), C.c_uint16]),
     "zoic_tile_create": (C.c_int, [_vp, _u32, C.c_uint16, C.POINTER(_vp)]),
     "zoic_tile_destroy": (None, [_vp]),

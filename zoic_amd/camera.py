@@ -51,6 +51,11 @@ class ZoicError(RuntimeError):
         self.status_name = name
 
 
+# a ghost pair as the C-ABI packs it: a | b << 8 (ZOIC_GHOST_PAIR)
+_GHOST_INDEX_BITS = 8
+_GHOST_INDEX_MASK = (1 << _GHOST_INDEX_BITS) - 1
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -780,6 +785,83 @@ class ZoicCamera:
         a = {k: np.zeros(n, dtype=np.float32) for k in ("index", "lambda0_nm")}
         self._lib.zoic_camera_get_coatings(self._h, n, a["index"].ctypes.data, a["lambda0_nm"].ctypes.data)
         return a
+
+    def ghost_pairs(self):
+        """The interface pairs that can make a ghost (zoic_camera_get_ghost_pairs): an (m,2) int32 array of rows (a, b), trace-order
+        indices (rear first), a > b, both interfaces between unequal media at the d-line; ordered by a, then b.  Works on a
+        tables-only camera (device=-1)."""
+        m = self._lib.zoic_camera_get_ghost_pairs(self._h, 0, None)
+        if m < 0:
+            self._check(1)   # ZOIC_ERR_INVALID_ARGUMENT with the library's detail
+        packed = np.zeros(m, dtype=np.uint32)
+        self._lib.zoic_camera_get_ghost_pairs(self._h, m, packed.ctypes.data)
+        return np.stack([packed & _GHOST_INDEX_MASK, (packed >> _GHOST_INDEX_BITS) & _GHOST_INDEX_MASK], 1).astype(np.int32)
+
+    def create_ghost_rays(self, samples, rays, pairs, wavelengths=None, rng_states=None, ray_index_base=0, out=None, stream=None):
+        """Ghost rays (zoic_create_ghost_rays_device) of rays create_rays made from device tensors: for every sample and every pair
+        (a, b) of `pairs` -- (p,2) integers, trace-order interface indices, a > b: ghost_pairs() lists the ones that reflect -- the
+        path that is reflected at a and again at b, with its Fresnel weight (csrc/ghost.hpp).
+
+        samples, wavelengths, rng_states, ray_index_base: what the forward call was given; rays: the (n,8) record tensor it returned
+        (or its result dict); wavelengths None: the records of create_rays(samples), at the d-line, else the (n,) tensor of
+        create_rays(samples, wavelengths=).  Returns an (n,p,8) float32 device tensor of records: origin, dir, weight and the flag
+        word (bit 0: traced; else the reason in bits 8-11, the interface in bits 16-21, the leg in bits 24-25 and zeros before
+        them).  More than 32 pairs are served by successive calls on the same stream.  out: an optional contiguous (n,p,8) float32
+        tensor on the samples' device to write into (p <= 32).  Changes no record and no counter."""
+        import torch
+        if isinstance(rays, dict):
+            rays = rays["rays"]
+        if not _is_torch(samples) or not _is_torch(rays):
+            raise ValueError("samples and rays must be device tensors (create_rays with a torch tensor)")
+        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
+            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
+        if samples.device.index != self.device:
+            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
+        n = samples.shape[0]
+        if tuple(rays.shape) != (n, 8) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
+            raise ValueError("rays must be the contiguous (n,8) float32 record tensor on the samples' device")
+        pr = np.asarray(pairs)
+        if pr.ndim != 2 or pr.shape[1] != 2 or pr.shape[0] == 0 or not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError("pairs must be a non-empty (p,2) integer array of (a, b)")
+        if (pr < 0).any() or (pr > _GHOST_INDEX_MASK).any():
+            raise ValueError("pair indices must lie in 0 ... %d" % _GHOST_INDEX_MASK)
+        packed = np.ascontiguousarray(pr[:, 0].astype(np.uint32) | (pr[:, 1].astype(np.uint32) << _GHOST_INDEX_BITS))
+        w_ptr = None
+        if wavelengths is not None:
+            if not _is_torch(wavelengths):
+                raise TypeError("torch samples need a torch wavelength tensor")
+            if (wavelengths.dtype != torch.float32 or tuple(wavelengths.shape) != (n,) or not wavelengths.is_contiguous()
+                    or wavelengths.device != samples.device):
+                raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the samples' device")
+            w_ptr = wavelengths.data_ptr()
+        rs_ptr = None
+        if rng_states is not None:
+            if (not _is_torch(rng_states) or rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4)
+                    or not rng_states.is_contiguous() or rng_states.device != samples.device):
+                raise ValueError("rng_states must be a contiguous (n,4) int32/uint32 tensor on the samples' device")
+            rs_ptr = rng_states.data_ptr()
+        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        p = len(packed)
+        chunk = 32   # ZOIC_GHOST_MAX_PAIRS
+        if out is not None and (p > chunk or tuple(out.shape) != (n, p, 8) or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != samples.device):
+            raise ValueError("out must be a contiguous (n,p,8) float32 tensor on the samples' device, p <= 32")
+        if p <= chunk:
+            if out is None:
+                out = torch.empty((n, p, 8), dtype=torch.float32, device=samples.device)
+            self._check(self._lib.zoic_create_ghost_rays_device(self._h, n, p, packed.ctypes.data, samples.data_ptr(), w_ptr, rs_ptr,
+                                                                int(ray_index_base), rays.data_ptr(), out.data_ptr(), C.c_void_p(st)))
+            return out
+        if stream is not None:
+            raise ValueError("more than 32 pairs are gathered with torch on the current stream: leave stream=None")
+        parts = []
+        for lo in range(0, p, chunk):
+            q = packed[lo:lo + chunk]
+            part = torch.empty((n, len(q), 8), dtype=torch.float32, device=samples.device)
+            self._check(self._lib.zoic_create_ghost_rays_device(self._h, n, len(q), q.ctypes.data, samples.data_ptr(), w_ptr, rs_ptr,
+                                                                int(ray_index_base), rays.data_ptr(), part.data_ptr(), C.c_void_p(st)))
+            parts.append(part)
+        return torch.cat(parts, 1)
 
     def tile(self, capacity, tid=0):
         """A ZoicTile of this camera (closed with the camera at the latest: ZoicCamera.close() closes the tiles still alive)."""

@@ -42,6 +42,7 @@
 #include "backward_spectral.hpp"
 #include "traceback.hpp"
 #include "traceback_jacobian.hpp"
+#include "ghost.hpp"
 #include "transmittance.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
@@ -309,6 +310,8 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     ReverseTable reverse{};                      // reverse.hpp: the projection table of the tables above (filled by every successful update)
     bool reverseOn = false;                      // zoic_camera_set_reverse_projection: zoic_camera_reverse_ray answers with it
     TraceBackTable traceBack{};                  // traceback.hpp: the trace-back table of the tables above (filled by every successful update)
+    GhostTable ghost{};                          // ghost.hpp: the ghost tracer's geometry of the tables above (filled by every successful update) ...
+    GhostTable *dGhost = nullptr;                // ... and its copy on the device, which the ghost kernel reads (its arguments have no room for it)
 
     TidState *tid_state(uint16_t tid);
     CallContext *lease_context(hipError_t &err);
@@ -855,6 +858,35 @@ void fill_traceback(zoic_camera *cam)
                          cam->fastDomain, 0.0f, 0.0f, false, 0.0f, 0.0f);
 }
 
+// the ghost tracer's geometry (ghost.hpp) of the camera's current tables, and its copy on the device
+zoic_status fill_ghost(zoic_camera *cam)
+{
+    const zoic_params &p = cam->params.p;
+    const LensSystem &L = cam->lens;
+    if (p.lensModel != ZOIC_RAYTRACED) {
+        fill_ghost_table(cam->ghost, p.lensModel == ZOIC_THINLENS ? 0 : 2, 0, nullptr, nullptr, nullptr, -1, 0.0f);
+    } else {
+        const FlatRows R(L);
+        fill_ghost_table(cam->ghost, 1, R.n, R.radius, R.thickness, R.aperture, L.apertureElement, L.userApertureRadius);
+    }
+    if (cam->device != ZOIC_DEVICE_NONE) ZOIC_HIP(hipMemcpy(cam->dGhost, &cam->ghost, sizeof(GhostTable), hipMemcpyHostToDevice));
+    return ZOIC_OK;
+}
+
+// what the ghost tracer reads at the call (ghost.hpp): the dispersion and the films, trace order
+void fill_ghost_media(const zoic_camera *cam, GhostMedia &M)
+{
+    SpectralTable W;
+    fill_spectral(cam, W);
+    FilmTable F;
+    fill_film(cam, F);
+    M = GhostMedia{};
+    for (int i = 0; i < W.count; ++i) {
+        M.iorD[i] = W.iorD[i]; M.cauchyB[i] = W.cauchyB[i];
+        M.filmIndex[i] = F.index[i]; M.filmLambda0[i] = F.lambda0[i];
+    }
+}
+
 // the dispersion of the camera's lens in the backward tables' order (backward_spectral.hpp); as on the forward side it is taken at
 // the call, so a zoic_camera_set_abbe_numbers override needs no update
 BackwardDispersion backward_dispersion(const zoic_camera *cam)
@@ -1022,6 +1054,8 @@ zoic_status zoic_camera_create(int device, zoic_camera **out)
     if (e == hipSuccess) e = hipMemset(cam->dCounters, 0, kCounterSets * sizeof(DeviceCounters));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&cam->dWorkCursor), kLaunchSlots * 2 * kCursorStride * sizeof(unsigned int));
     if (e == hipSuccess) e = hipMemset(cam->dWorkCursor, 0, kLaunchSlots * 2 * kCursorStride * sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&cam->dGhost), sizeof(GhostTable));
+    if (e == hipSuccess) e = hipMemset(cam->dGhost, 0, sizeof(GhostTable));
     for (unsigned i = 0; e == hipSuccess && i < kLaunchSlots; ++i) {
         cam->slots[i].cursor = cam->dWorkCursor + i * 2 * kCursorStride;
         e = hipEventCreateWithFlags(&cam->slots[i].done, hipEventDisableTiming);
@@ -1057,6 +1091,7 @@ void zoic_camera_destroy(zoic_camera *cam)
         if (cam->dProbeTir) (void)hipFree(cam->dProbeTir);
         if (cam->dCounters) (void)hipFree(cam->dCounters);
         if (cam->dWorkCursor) (void)hipFree(cam->dWorkCursor);
+        if (cam->dGhost) (void)hipFree(cam->dGhost);
     }
     if (cam->tidStates) for (unsigned i = 0; i < kTidStates; ++i) delete cam->tidStates[i].load(std::memory_order_relaxed);
     delete cam;
@@ -1265,6 +1300,7 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
     }
     fill_reverse(cam);   // (RAYTRACED: fastDomain is still the geometric test here; the self-check below may narrow it)
     fill_traceback(cam);
+    if (zoic_status s = fill_ghost(cam)) { cam->updated = false; cam->params.valid = false; return s; }
     cam->updated = true;
     // the FAST modes are kept only for a camera they are good for (fast_self_check above; the geometric test comes first).
     // The verdict depends on the lens tables, the LUT and the bokeh tables only: an update that rebuilt none of them (exposure,
@@ -1617,6 +1653,48 @@ zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *f
     for (int i = 0; i < count; ++i)
         if (cam->coatingIndex[i] == 0.0f) cam->coatingLambda0[i] = 0.0f;
     return ZOIC_OK;
+}
+
+zoic_status zoic_create_ghost_rays_device(zoic_camera *cam, uint64_t n, uint32_t p, const uint32_t *pairs, const float *d_samples,
+                                          const float *d_wavelengths, const uint32_t *d_rng_states, uint64_t ray_index_base,
+                                          const zoic_ray *d_rays, zoic_ray *d_ghosts, void *stream)
+{
+    static_assert(ZOIC_GHOST_MAX_PAIRS == kGhostMaxPairs, "ZOIC_GHOST_MAX_PAIRS");
+    static_assert(ZOIC_GHOST_MISS == kGhostMiss && ZOIC_GHOST_CLIPPED == kGhostClipped && ZOIC_GHOST_TIR == kGhostTir &&
+                      ZOIC_GHOST_TURNED == kGhostTurned && ZOIC_GHOST_NO_REFLECTION == kGhostNoReflection &&
+                      ZOIC_GHOST_NON_FINITE == kGhostNonFinite && ZOIC_GHOST_WAVELENGTH == kGhostWavelength &&
+                      ZOIC_GHOST_NO_START == kGhostNoStart && ZOIC_GHOST_MODEL == kGhostModel && ZOIC_GHOST_INVALID_PAIR == kGhostInvalidPair,
+                  "the header's ghost reason codes are ghost.hpp's");
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (p == 0 || p > ZOIC_GHOST_MAX_PAIRS) return fail(ZOIC_ERR_INVALID_ARGUMENT, "p must be 1 ... ZOIC_GHOST_MAX_PAIRS");
+    return forward_batch(
+        cam, n, {{"pairs", pairs, 4}, {"d_samples", d_samples, 16}, {"d_wavelengths", d_wavelengths, 4, true}, {"d_rng_states", d_rng_states, 16, true},
+                 {"d_rays", d_rays, 16}, {"d_ghosts", d_ghosts, 16}},
+        [&]() -> zoic_status {
+            GhostMedia M;
+            fill_ghost_media(cam, M);
+            return launch_status(launch_ghost_rays(cam->ghost.model, cam->kolb, M, cam->bokehDev, cam->dGhost, p, pairs, d_samples, d_wavelengths,
+                                                   d_rng_states, ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays),
+                                                   reinterpret_cast<RayRecord *>(d_ghosts), static_cast<hipStream_t>(stream)));
+        });
+}
+
+int zoic_camera_get_ghost_pairs(const zoic_camera *cam, int capacity, uint32_t *pairs)
+{
+    if (!cam) { fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL"); return -1; }
+    if (capacity < 0) { fail(ZOIC_ERR_INVALID_ARGUMENT, "capacity is negative"); return -1; }
+    if (!cam->updated || cam->ghost.model != 1) return 0;   // a lens without interfaces has no ghosts
+    SpectralTable W;
+    fill_spectral(cam, W);
+    const auto reflects = [&](int i) { return W.iorD[i] != (i + 1 < W.count ? W.iorD[i + 1] : 1.0f); };
+    int m = 0;
+    for (int a = 1; a < W.count; ++a)
+        for (int b = 0; b < a; ++b) {
+            if (!reflects(a) || !reflects(b)) continue;
+            if (pairs && m < capacity) pairs[m] = ghost_pack(a, b);
+            ++m;
+        }
+    return m;
 }
 
 }  // extern "C"
