@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 F32 = np.float32
+COS_MIN = 0.05      # the conditioning rule: a ray whose min_cos_incidence is below it has no reliable finite difference
 
 
 def surfaces(info):
@@ -158,6 +159,28 @@ def kolb_start(oc, params, samples, tries, states, oracle_lib):
         Lxy = np.stack([lx * cs - ly * sn, lx * sn + ly * cs], 1).astype(F32)
     d0 = np.stack([Lxy[:, 0] - o0[:, 0], Lxy[:, 1] - o0[:, 1], np.full(len(samples), -el[0, 1], F32)], 1).astype(F32)
     return o0, d0
+
+
+def passing_rays(oc, info, hs, rs, want):
+    """random sensor points aimed at random points of the rear element; the ones the oracle's trace lets through"""
+    import oracle
+    L = oracle.lib()
+    el = info["elements"]
+    n = want * 40
+    o = np.stack([rs.uniform(-1, 1, n) * hs, rs.uniform(-0.7, 0.7, n) * hs, np.full(n, info["originShift"])], 1).astype(np.float32)
+    r = np.sqrt(rs.uniform(0, 1, n)) * el[0, 3] * 0.5
+    a = rs.uniform(0, 2 * np.pi, n)
+    d = np.stack([r * np.cos(a) - o[:, 0], r * np.sin(a) - o[:, 1], np.full(n, -el[0, 1])], 1).astype(np.float32)
+    keep, po, pd = [], [], []
+    hits = (oracle.V3 * 128)()
+    nh = C.c_int()
+    for i in range(n):
+        oo, dd = oracle.V3(*o[i]), oracle.V3(*d[i])
+        if L.zo_trace_record(oc._h, C.byref(oo), C.byref(dd), hits, C.byref(nh)):
+            keep.append(i); po.append((oo.x, oo.y, oo.z)); pd.append((dd.x, dd.y, dd.z))
+            if len(keep) == want:
+                break
+    return o[keep], d[keep], np.array(po, np.float64), np.array(pd, np.float64)
 
 
 def min_cos_incidence(surf, o, d):

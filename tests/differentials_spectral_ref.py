@@ -7,7 +7,73 @@ differentials_ref._interface multiplies the (n,3) unit direction by eta, so it t
 is the same arithmetic with an (n,) eta (tests/test_differentials_spectral_cpu.py checks the two against each other bit for bit)."""
 import numpy as np
 
+from zoic_amd.camera import ZoicCamera
+from zoic_amd.workloads import camera_params
+
+import differentials_ref as dref
+from spectral_ref import WAVES
+
+F32 = np.float32
 LAMBDA_D, LAMBDA_F, LAMBDA_C = 587.5618, 486.1327, 656.2725   # nm (csrc/spectral.hpp)
+
+
+def tables(cfg, abbe=None, lens_text=None, **over):
+    """(params, info, dispersion, surfaces, halfSensor) of a tables-only camera"""
+    p = camera_params(cfg)
+    p["useImage"] = False
+    p.pop("bokehPath", None)
+    p.update(over)
+    cam = ZoicCamera(device=-1)
+    if lens_text is not None:
+        cam.set_lens_text(lens_text)
+    cam.update(**p)
+    if abbe is not None:
+        cam.set_abbe_numbers(np.full(cam.info()["lensCount"], abbe, F32))
+    info, disp = cam.info(), cam.dispersion()
+    cam.close()
+    return p, info, disp, dref.surfaces(info), F32(F32(p["sensorWidth"]) * F32(0.5))
+
+
+_RAYS = {}
+
+
+def lens_rays(cfg, oracle_lib, want=10000):
+    """~10 k rays the oracle's d-line trace lets through (differentials_ref.passing_rays, seed 11), computed once per lens and shared
+    by the CPU tests of the spectral differentials, the transmittance and the ghosts: not to be written to"""
+    if cfg not in _RAYS:
+        p, info, _, _, hs = tables(cfg)
+        oc = oracle_lib.OracleCamera()
+        oc.update(**p)
+        o, d, _, _ = dref.passing_rays(oc, info, hs, np.random.RandomState(11), want)
+        assert len(o) >= want // 2, (cfg, len(o))
+        o.setflags(write=False)
+        d.setflags(write=False)
+        _RAYS[cfg] = (o, d)
+    return _RAYS[cfg]
+
+
+def ray_wavelengths(n, seed=4):
+    lam = np.random.RandomState(seed).uniform(400, 700, n).astype(F32)
+    lam[:8 * (n // 64):n // 64][:8] = WAVES   # the eight fixed ones, spread over the batch
+    return lam
+
+
+def passes(surf, eta, o, d, aperture=None):
+    """the f64 trace meets every sphere and refracts everywhere (no |.| of the restatement flips a sign): the path is a real one;
+    aperture (count,): the hit points also lie within each interface's housing"""
+    o = np.asarray(o, np.float64).copy()
+    d = np.asarray(d, np.float64).copy()
+    ok = np.ones(len(o), bool)
+    for i, (c, r2, sg, _) in enumerate(np.asarray(surf, np.float64)):
+        u = d / np.linalg.norm(d, axis=1, keepdims=True)
+        L = np.stack([-o[:, 0], -o[:, 1], c - o[:, 2]], 1)
+        tca = (L * u).sum(1)
+        ok &= (L * L).sum(1) - tca * tca <= r2
+        o, d, c1, _ = interface(o, d, c, r2, sg, eta[:, i])
+        ok &= eta[:, i] ** 2 * (1 - c1 * c1) <= 1.0
+        if aperture is not None:
+            ok &= o[:, 0] ** 2 + o[:, 1] ** 2 <= (0.5 * float(aperture[i])) ** 2
+    return ok
 
 
 def cauchy_index(disp, lam):

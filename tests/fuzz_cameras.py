@@ -11,7 +11,8 @@ import numpy as np
 from zoic_amd import RAYTRACED, lens_path
 from zoic_amd.workloads import hexagon_bokeh
 
-from spectral_ref import spectral_iors
+from device_cases import bits_f32 as bits
+from spectral_ref import LAMBDA_D, spectral_iors
 
 # every shipped prescription with an aperture row (zoic rejects a lens without one)
 LENSES = ["double_gauss_f2.0.dat", "tessar_f2.8.dat", "fisheye_muller_f4.0.dat", "petzval_f1.25.dat", "triplet_f2.5.dat", "mori_f2.8.dat"]
@@ -28,6 +29,11 @@ LAMBDA_HOSTILE = np.array([np.nan, -np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-40, -
                            np.nextafter(np.float32(360.0), np.float32(0.0)), np.nextafter(np.float32(830.0), np.float32(np.inf))], np.float32)
 
 ABBE_RANGE = (20.0, 90.0)
+# the spectral fuzz's FAST-against-STRICT bounds, shared with the hero reference test
+FLIP_TOL = 5e-5          # test_parity_gpu.FLIP_TOL: 8192 rays, 20 x FLIP_TOL as in test_perturbed_prescription_fuzz
+DIR_RMSE_TOL = 1e-5      # north_star
+# interleaved ray by ray in the STRICT parity check: both ends of the range, their in-range neighbours, the F, d and C lines
+WAVES = np.array([360.0, LAMBDA_EDGES[1], 405.0, 486.1327, LAMBDA_D, 656.2725, 760.0, LAMBDA_EDGES[3], 830.0], np.float32)
 SURGERIES = ["keep", "keep", "drop", "double", "drop2", "double2"]   # of the new fuzzers' lenses (lens_args)
 
 REAR_ELEMENT_LENS = """# TESSAR with a strongly curved last surface: housing radius a = 8.25 mm on a sphere of |R| = {r} mm
@@ -202,10 +208,6 @@ def _oracle_spectral(oracle_lib, p, dispersion, s, lam, states, lens_text=None, 
     after = oc.counters()
     oc.close()
     return dict(planes=planes, flags=flags), {k: after[k] - before[k] for k in after}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def same_bits(a, b):

@@ -13,7 +13,21 @@ import transmittance_ref as tref
 
 F32 = np.float32
 TRACED, MISS, CLIPPED, TIR, TURNED, NO_REFLECTION, NON_FINITE, WAVELENGTH, NO_START, MODEL, INVALID_PAIR = range(11)
+MARGIN = 1e-4          # a ghost whose f64 path came closer than this (relative) to any decision may be left out ...
+MAX_LEFT_OUT = 0.02    # ... and at most this share of a lens's ghosts is
 REASONS = ("traced", "miss", "clipped", "tir", "turned", "no reflection", "non-finite", "wavelength", "no start", "model", "invalid pair")
+
+
+def bound(measured):
+    """what is asserted for a table of measured errors: 4 x them, the project's margin for other compilers' host builds"""
+    return {k: 4 * v for k, v in measured.items()}
+
+
+def expected_pairs(disp):
+    """the pair list of a lens by the d-line rule: (a, b), a > b, both interfaces between differing media"""
+    n1 = disp["ior_d"]
+    differ = n1 != np.append(n1[1:], F32(1.0))
+    return np.array([(a, b) for a in range(len(n1)) for b in range(a) if differ[a] and differ[b]], np.int32).reshape(-1, 2)
 
 
 def flag_word(reason, interface=0, leg=0):

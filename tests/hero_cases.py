@@ -11,11 +11,11 @@ from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states
 import machine_lens_corpus as mlc
 from fuzz_cameras import EXAMPLE_CAMERA, EXAMPLE_LENSES, LAMBDA_EDGES, perturbed_prescription
 from hero_ref import LOST, REJECTED, Indices, hero_reference, oracle_camera, same_words, valid, words_of  # noqa: F401 (re-exported)
-from spectral_ref import LAMBDA_D
+from spectral_ref import LAMBDA_D, WAVES as SPECTRAL_WAVES
 
 N = 4096
 OUT_OF_TRIES = 26          # the try count of a ray that ends without an accepted try (zoic.cpp:1951: tries > 25)
-# test_spectral_fuzz_gpu.WAVES (tests/test_hero_reference_gpu.py holds the two equal): both ends of the range, their in-range
+# fuzz_cameras.WAVES (tests/test_hero_reference_gpu.py holds the two equal): both ends of the range, their in-range
 # neighbours, the F, d and C lines
 WAVES = np.array([360.0, LAMBDA_EDGES[1], 405.0, 486.1327, LAMBDA_D, 656.2725, 760.0, LAMBDA_EDGES[3], 830.0], np.float32)
 
@@ -161,6 +161,30 @@ def reference(oracle_lib, name, n=N, k=4, seed=11):
             a.setflags(write=False)
         _REFERENCE[key] = s, lam, st, words, counters, det
     return _REFERENCE[key]
+
+
+# the two cameras of the device tests of the lens losses (tests/test_transmittance_gpu.py, tests/test_ghost_gpu.py) and their reference
+LOSS_CAMERAS = {"C2": "C2", "C3": "C3-bokeh-V50"}     # C3 ships no V-numbers: V = 50 on every glass, so that the wavelength matters
+_LOSS_REFERENCE = {}
+
+
+def cycled(n, k):
+    """(n, k) wavelengths cycled from spectral_ref.WAVES, every row starting one further on: rows and columns both differ"""
+    return SPECTRAL_WAVES[(np.arange(n)[:, None] * (k + 1) + np.arange(k)[None, :]) % len(SPECTRAL_WAVES)].astype(np.float32)
+
+
+def loss_reference(oracle_lib, name, k, lam=None, key=None):
+    """samples, wavelengths, states and the hero reference (words, starts) of N rows: computed once, never written to"""
+    key = (name, k, key)
+    if key not in _LOSS_REFERENCE:
+        sp = spec(name)
+        s, _, st = inputs(N, k, 11, name)
+        lam = cycled(N, k) if lam is None else lam
+        words, _, det = hero_reference(oracle_lib, sp.params, sp.dispersion(), s, lam, st, lens_text=sp.text, details=True)
+        for a in (s, lam, st, words, det["starts"]):
+            a.setflags(write=False)
+        _LOSS_REFERENCE[key] = s, lam, st, words, det["starts"]
+    return _LOSS_REFERENCE[key]
 
 
 def oracle_columns(oracle_lib, sp, s, lam, st):

@@ -20,6 +20,7 @@ import numpy as np
 from zoic_amd import RAY_COMPANION_LOST, RAYTRACED
 from zoic_amd.workloads import hexagon_bokeh
 
+from device_cases import bits_f32 as _bits
 from spectral_ref import spectral_iors
 
 LOST = RAY_COMPANION_LOST
@@ -31,10 +32,6 @@ def valid(lam):
     lam = np.asarray(lam, np.float32)
     with np.errstate(invalid="ignore"):
         return (lam >= np.float32(360.0)) & (lam <= np.float32(830.0))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def oracle_camera(oracle_lib, params, lens_text, image):

@@ -6,10 +6,13 @@ Lenses: the ten of machine_lens_corpus.NAMES and one defined here, plates-32, th
 that the wavelength matters.  It is not part of machine_lens_corpus.CORPUS (the backward-path tests do not run it); its text is pinned
 by its zlib.crc32 as the corpus is.
 
-Frame, wavelengths and row selection are those of tests/test_differentials_spectral_corpus_cpu.py (frame, reference_rows); starts are
+Frame, wavelengths and row selection are those of differentials_spectral_corpus.py (frame, reference_rows); starts are
 differentials_ref.kolb_start on the records' own tries; tables come from a tables-only camera.  The host builds are compared on all of
 reference_rows (at most MAX_HOST) and so is the f64 transmittance, one vectorised pass; the f64 ghost restatement, a pass per pair, runs
-on a stride of them (at most MAX_F64; plates-32, with 465 pairs, MAX_F64_PLATES)."""
+on a stride of them (at most MAX_F64; plates-32, with 465 pairs, MAX_F64_PLATES).
+
+The two GPU files also share what is at the end: a camera on device 0, the frame uploaded once, one STRICT launch per lens and the
+starts rebuilt from its records, all cached."""
 import zlib
 
 import numpy as np
@@ -17,10 +20,11 @@ import numpy as np
 import differentials_ref as dref
 import ghost_ref as gref
 import machine_lens_corpus as mc
+from device_cases import BIG, bits_f32  # noqa: F401 (BIG: shared by the two GPU files)
+from differentials_spectral_corpus import frame, reference_rows
 from fuzz_cameras import ABBE_RANGE, CUSTOM_LENS_14, MachineLens
-from test_differentials_spectral_corpus_cpu import frame, reference_rows
-from test_transmittance_cpu import films_where_media_differ, housings
-from zoic_amd import ZoicCamera
+from transmittance_ref import films_where_media_differ, housings
+from zoic_amd import PRECISION_STRICT, ZoicCamera
 
 F32 = np.float32
 PLATES = "plates-32"
@@ -152,3 +156,90 @@ def starts(oracle_lib, name):
 def f64_subset(name, n):
     """indices into n rows that get an f64 restatement: a stride, at most MAX_F64 (plates-32: MAX_F64_PLATES)"""
     return mc.strided(np.arange(n), MAX_F64_PLATES if name == PLATES else MAX_F64)
+
+
+def constructed(name):
+    """pairs of the lens the pair list leaves out, with the dead record each must give: (a, b, reason, interface, leg)"""
+    T = tables(name)
+    count, stop, out = T["count"], T["stop"], []
+    ok = [i for i in range(count) if i != stop and i not in T["equal"]]
+    for e in T["equal"]:
+        out += [(e, b, gref.NO_REFLECTION, e, 0) for b in ok if b < e][:2]              # a on the equal-media interface: leg 0
+        out += [(a, e, gref.NO_REFLECTION, e, 1) for a in ok if a > e][-2:]             # b on it: leg 1
+    if stop == 0:
+        out += [(a, 0, gref.NO_REFLECTION, 0, 1) for a in ok]                           # every pair (a, 0)
+    return out
+
+
+# ---- what the two GPU files share ---------------------------------------------------------------------------------------------------
+SPLIT = [0, 1, 64, 5037]
+
+
+def record_tries(rays):
+    return ((bits_f32(rays[:, 7]) >> 1) & 31).astype(np.int64)
+
+
+def device_camera(name, precision=PRECISION_STRICT, coated=False, **over):
+    cam, p = camera(name, device=0, precision=precision, **over)
+    if coated:
+        nc, l0 = tables(name)["film"]
+        cam.set_coatings(nc[::-1], l0[::-1])      # file order
+    return cam
+
+
+_INPUTS = []
+
+
+def device_inputs():
+    """the frame on the device: (samples, rng states as int32, wavelengths) tensors, uploaded once and never written to"""
+    if not _INPUTS:
+        import torch
+        s, st, lam = frame()
+        _INPUTS.extend([torch.from_numpy(np.array(s)).cuda(), torch.from_numpy(np.array(st).view(np.int32)).cuda(), torch.from_numpy(np.array(lam)).cuda()])
+    return tuple(_INPUTS)
+
+
+_LAUNCH = {}
+
+
+def device_launch(name):
+    """One STRICT launch of the frame at its wavelengths behind lens `name`: the records (N, 8) as numpy, not to be written to"""
+    if name not in _LAUNCH:
+        import torch
+        cam = device_camera(name)
+        ts, tst, tl = device_inputs()
+        rays = cam.create_rays(ts, wavelengths=tl, rng_states=tst)["rays"]
+        torch.cuda.synchronize()
+        _LAUNCH[name] = rays.cpu().numpy()
+        _LAUNCH[name].setflags(write=False)
+        cam.close()
+    return _LAUNCH[name]
+
+
+_DEVICE_STARTS = {}
+
+
+def device_starts(oracle_lib, name):
+    """reference_rows of the launch's live records and their starts from the records' own tries: dict of rows, o, d, lam; not to be
+    written to"""
+    if name not in _DEVICE_STARTS:
+        rays = device_launch(name)
+        rows = reference_rows(np.flatnonzero(rays[:, 6] != 0), record_tries(rays))
+        o, d = kolb_starts(oracle_lib, name, rows, record_tries(rays)[rows])
+        _DEVICE_STARTS[name] = dict(rows=rows, o=o, d=d, lam=np.array(frame()[2][rows]))
+        for a in _DEVICE_STARTS[name].values():
+            a.setflags(write=False)
+    return _DEVICE_STARTS[name]
+
+
+def take(rows, rays):
+    """device tensors of the frame's rows `rows`: samples, wavelengths, rng states and the records `rays` (numpy (len(rows), 8))"""
+    import torch
+    ts, tst, tl = device_inputs()
+    idx = torch.from_numpy(np.array(rows, np.int64)).cuda()      # a copy: rows may be a read-only cached array
+    return ts[idx].contiguous(), tl[idx].contiguous(), tst[idx].contiguous(), torch.from_numpy(np.array(rays)).cuda()
+
+
+def same_words(a, b):
+    import torch
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))

@@ -18,6 +18,7 @@ import numpy as np
 from zoic_amd import ZoicCamera
 
 import traceback_cases as tc
+from device_cases import records
 from fuzz_cameras import EXAMPLE_CAMERA, REAR_ELEMENT_LENS, perturbed_prescription
 from reverse_ref import kolb_point_set
 
@@ -50,6 +51,9 @@ BITWISE = [e.name for e in CORPUS if not e.accuracy]
 OUTSIDE = "petzval-5"            # every trace-back kTbOutsideDomain, every projection kRevOutsideDomain
 LARGE_BATCH = ("fisheye-5", "triplet-4")   # the most and the fewest interfaces: also run as more than one grid
 MAX_RAYS, MAX_POINTS = 8192, 2048          # what a GPU test gives the per-item host calls
+PREFIXES = (1, 63, 64, 65)                 # the batch sizes every device-equals-host comparison also runs
+GRID_PLUS_ONE = 524289                     # one grid of 2048 x 256 lanes and one item more
+EDGE_CAP = 0.02                            # the largest share of a lens's live rays a conditioning rule may leave out
 
 LENSES = {e.name: perturbed_prescription(e.lens, e.seed, e.amount, e.surgery, abbe=True) for e in CORPUS}
 
@@ -127,3 +131,23 @@ def point_set(name):
 def strided(a, most):
     """every k-th row of a, k fixed by its length: at most `most` rows"""
     return a[:: max(1, -(-len(a) // most))]
+
+
+_RAYS = {}
+
+
+def ray_set(oracle_lib, cam, name):
+    """(records (m,8) f32, number of leading live forward records): a stride of the lens's live forward records, then the rejection
+    families made from a stride of them, random lines and the non-finite rays; m <= MAX_RAYS.  Cached and not to be written to"""
+    if name not in _RAYS:
+        info = cam.info()
+        _, o, d, w = oracle_records(oracle_lib, name)
+        o, d = o[w > 0], d[w > 0]
+        lo, ld = strided(o, 3072), strided(d, 3072)
+        fo, fd = strided(o, 512), strided(d, 512)
+        sets = [(lo, ld)] + list(tc.rejection_families(info, fo, fd).values()) + [tc.random_lines(info, 1024), tc.non_finite_rays()]
+        rays = np.ascontiguousarray(np.concatenate([records(a, b) for a, b in sets]), F32)
+        assert len(rays) <= MAX_RAYS
+        rays.setflags(write=False)
+        _RAYS[name] = rays, len(lo)
+    return _RAYS[name]

@@ -8,6 +8,7 @@ Snell with the media of the prescription (air in front of the front element and 
 import numpy as np
 
 F32 = np.float32
+BEHIND, NO_ROOT, NON_FINITE, MODEL_NONE, OUTSIDE = 1, 2, 3, 4, 5      # the reasons a projection is refused (csrc/reverse.hpp)
 
 
 class Lens:

@@ -3,7 +3,17 @@ tests/test_spectral_gpu.py): every operation in float32 with one rounding, B in 
 import numpy as np
 
 LAMBDA_D = np.float32(587.5618)
+LAMBDA_D32 = LAMBDA_D      # the name the modules use that also hold an f64 LAMBDA_D
 LAMBDA_F, LAMBDA_C = 486.1327, 656.2725
+# the eight fixed wavelengths of the spectral tests: both ends of the range, the F, d and C lines among them
+WAVES = np.array([360.0, 420.0, 486.1327, 530.0, LAMBDA_D, 610.0, 656.2725, 830.0], np.float32)
+# wavelengths every spectral call rejects
+BAD = np.array([np.nan, np.inf, -np.inf, 0.0, -500.0, 359.9, 830.1], np.float32)
+SINGLET = """# singlet, V = 30
+50.0\t6.0\t1.5168\t30.0\t20.0
+-50.0\t2.0\t0.0\t0.0\t20.0
+0.0\t45.0\t0.0\t0.0\t18.0
+"""
 
 
 def cauchy_b(ior_d, abbe):

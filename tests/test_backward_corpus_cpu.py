@@ -61,10 +61,11 @@ from zoic_amd import _capi
 import backward_spectral_ref as bs
 import machine_lens_corpus as mc
 import traceback_cases as tc
-from test_backward_spectral_cpu import lib_project, lib_trace
+from device_cases import bits as _bits
+from machine_lens_corpus import EDGE_CAP
+from traceback_cases import lib_project, lib_trace
 from traceback_ref import CLIPPED, MISS, OUTSIDE_DOMAIN, TIR
 
-EDGE_CAP = 0.02
 REV_OUTSIDE = 5                       # kRevOutsideDomain (csrc/reverse.hpp)
 F32 = np.float32
 WAVELENGTHS = (None,) + bs.LAMBDAS    # None: the d-line calls and the d-line restatement
@@ -73,10 +74,6 @@ BITWISE_WAVELENGTHS = (None, 400.0, 700.0)
 
 def _tag(lam):
     return "d" if lam is None else "%g" % lam
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 class _Lens:

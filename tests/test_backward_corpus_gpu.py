@@ -30,44 +30,19 @@ from zoic_amd.workloads import ray_rng_states
 import backward_spectral_ref as bs
 import machine_lens_corpus as mc
 import traceback_cases as tc
-from test_backward_spectral_cpu import lib_project, lib_trace
+from device_cases import bits as _bits
+from machine_lens_corpus import EDGE_CAP, GRID_PLUS_ONE, PREFIXES
+from traceback_cases import lib_project, lib_trace
 from traceback_ref import OUTSIDE_DOMAIN
 
 F32 = np.float32
-PREFIXES = (1, 63, 64, 65)
-GRID_PLUS_ONE = 524289            # one grid of 2048 x 256 lanes and one item more
 REV_OUTSIDE = 5                   # kRevOutsideDomain (csrc/reverse.hpp)
-EDGE_CAP = 0.02
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _records(o, d):
-    r = np.zeros((len(o), 8), F32)
-    r[:, 0:3], r[:, 3:6] = o, d
-    r[:, 6] = 1.0
-    return r
-
-
-_RAYS = {}
 
 
 def _ray_set(oracle_lib, cam, name):
-    """(records (m,8) f32, number of leading live forward records): a stride of the lens's live forward records, then the rejection
-    families made from a stride of them, random lines and the non-finite rays; m <= mc.MAX_RAYS"""
-    if name not in _RAYS:
-        info = cam.info()
-        _, o, d, w = mc.oracle_records(oracle_lib, name)
-        o, d = o[w > 0], d[w > 0]
-        lo, ld = mc.strided(o, 3072), mc.strided(d, 3072)
-        fo, fd = mc.strided(o, 512), mc.strided(d, 512)
-        sets = [(lo, ld)] + list(tc.rejection_families(info, fo, fd).values()) + [tc.random_lines(info, 1024), tc.non_finite_rays()]
-        rays = np.ascontiguousarray(np.concatenate([_records(a, b) for a, b in sets]), F32)
-        assert len(rays) <= mc.MAX_RAYS
-        _RAYS[name] = rays, len(lo)
-    return _RAYS[name]
+    """a writable copy of the shared ray set (torch.from_numpy wants one) and the number of its leading live forward records"""
+    rays, n_live = mc.ray_set(oracle_lib, cam, name)
+    return np.array(rays), n_live
 
 
 def _point_set(name):

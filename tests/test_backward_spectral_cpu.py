@@ -31,9 +31,7 @@ before the library is looked at.  Measured (max / p99 of |library - f64|, in uni
 The f64 projection is backward_spectral_ref.chief_through: the chief ray through the stop's centre found by bracketing and bisection.
 """
 import ctypes
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -43,10 +41,11 @@ from zoic_amd.camera import ZoicCamera
 
 import backward_spectral_ref as bs
 import traceback_cases as tc
+from library_facts import header_text, kernel_resources
 from reverse_ref import kolb_point_set, thin_point_set
+from traceback_cases import lib_project, lib_trace
 from traceback_ref import CLIPPED, MISS, TIR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("zoic_trace_back_rays_spectral_device", "zoic_trace_back_ray_spectral", "zoic_project_points_spectral_device",
        "zoic_project_point_spectral")
 EDGE_CAP = 0.02
@@ -56,44 +55,6 @@ F32 = np.float32
 def _camera(name, **over):
     p = dict(tc.params_of(name), **over)
     return tc.update(ZoicCamera(device=-1), p), p
-
-
-def lib_trace(cam, o, d, lam=None):
-    """zoic_trace_back_ray (lam None) or zoic_trace_back_ray_spectral on every ray: (ps (m,2) float32, flags (m,) uint32)"""
-    if lam is None:
-        return tc.lib_trace(cam, o, d)
-    lib, h = _capi.load(), cam._h
-    m = len(o)
-    ps, fl = np.zeros((m, 2), F32), np.zeros(m, np.uint32)
-    o, d = np.ascontiguousarray(o, F32), np.ascontiguousarray(d, F32)
-    lam = np.broadcast_to(np.asarray(lam, F32), (m,))
-    V, FP, UP = ctypes.POINTER(_capi.Vec3), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
-    po, pd, pp, pf = o.ctypes.data, d.ctypes.data, ps.ctypes.data, fl.ctypes.data
-    fn = lib.zoic_trace_back_ray_spectral
-    for i in range(m):
-        rc = fn(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pd + 12 * i, V), float(lam[i]), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
-        assert rc == 0, rc
-    return ps, fl
-
-
-def lib_project(cam, pts, lam=None):
-    """zoic_project_point (lam None) or zoic_project_point_spectral on every point: (ps (m,2) float32, flags (m,) uint32)"""
-    lib, h = _capi.load(), cam._h
-    m = len(pts)
-    ps, fl = np.zeros((m, 2), F32), np.zeros(m, np.uint32)
-    pts = np.ascontiguousarray(pts, F32)
-    V, FP, UP = ctypes.POINTER(_capi.Vec3), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
-    po, pp, pf = pts.ctypes.data, ps.ctypes.data, fl.ctypes.data
-    if lam is None:
-        for i in range(m):
-            rc = lib.zoic_project_point(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
-            assert rc == 0, rc
-        return ps, fl
-    lam = np.broadcast_to(np.asarray(lam, F32), (m,))
-    for i in range(m):
-        rc = lib.zoic_project_point_spectral(h, ctypes.cast(po + 12 * i, V), float(lam[i]), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
-        assert rc == 0, rc
-    return ps, fl
 
 
 def _same_bits(a, b):
@@ -127,7 +88,7 @@ def _points(name):
 
 # ---- 1. symbols --------------------------------------------------------------------------------------------------------------
 def test_abi_declares_and_exports_the_spectral_backward_calls():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     lib = ctypes.CDLL(_capi.LIB_PATH)
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -328,12 +289,7 @@ def test_mixed_wavelengths_follow_the_restatement(oracle_lib):
 
 # ---- 6. budget -------------------------------------------------------------------------------------------------------------------
 def test_spectral_backward_kernels_budget():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = code_object_regs.kernel_resources(_capi.LIB_PATH)
+    res = kernel_resources()
     for kernel in ("trace_back_spectral_kernel", "project_points_spectral_kernel"):
         hit = {k: v for k, v in res.items() if kernel in k}
         assert len(hit) == 1, (kernel, sorted(res))

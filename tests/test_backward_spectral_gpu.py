@@ -14,7 +14,8 @@ from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states, syn
 import backward_spectral_ref as bs
 import traceback_cases as tc
 from reverse_ref import kolb_point_set, thin_point_set
-from test_backward_spectral_cpu import lib_project, lib_trace
+from device_cases import bits as _bits, records as _records
+from traceback_cases import lib_project, lib_trace
 from traceback_ref import TraceBack
 
 F32 = np.float32
@@ -31,17 +32,6 @@ def _camera(name, device=0):
         cam.set_precision(PRECISION_STRICT)
     cam.update(**p)
     return bs.set_dispersion(cam, name), p
-
-
-def _records(o, d):
-    r = np.zeros((len(o), 8), F32)
-    r[:, 0:3], r[:, 3:6] = o, d
-    r[:, 6] = 1.0
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _tb_set(oracle_lib, cam, name):

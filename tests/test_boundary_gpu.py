@@ -11,11 +11,9 @@ from zoic_amd import PRECISION_STRICT, PinnedArray, ZoicCamera, ZoicError
 from zoic_amd import _capi
 from zoic_amd.workloads import CONFIGS, camera_params, hexagon_bokeh, ray_rng_states, synthetic_samples
 
+from device_cases import bits
+
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _c2_camera():

@@ -6,12 +6,13 @@ import subprocess
 
 from zoic_amd import _capi
 
+from library_facts import header_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "zoic_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = header_text()
     return sorted(set(re.findall(r"\b(zoic_[a-z0-9_]+)\s*\(", text)))
 
 

@@ -16,11 +16,10 @@ import pytest
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, RAYTRACED, THINLENS, ZoicCamera
 from zoic_amd.workloads import ray_rng_states
 
-from differentials_ref import (kolb_jacobian_fd, kolb_start, min_cos_incidence, rel_err, replay_and_restatement, restatement_holds, surfaces,
+from differentials_ref import (COS_MIN, kolb_jacobian_fd, kolb_start, min_cos_incidence, rel_err, replay_and_restatement, restatement_holds, surfaces,
                                thin_jacobian_fd)
 from fuzz_cameras import EXAMPLE_CAMERA, EXAMPLE_LENSES, camera_params, camera_strategy, examples, lens_args, lens_name, lens_strategy, perturbed_prescription, same_bits, update_both
 
-COS_MIN = 0.05
 # A machine-made double Gauss with an element dropped: at focal length 2 and focus distance 20 its f64 restatement misses the records
 # by a median 7.7e-5 relative (C2-C5: 3e-7 ... 6e-7), while the oracle's own f32 trace from kolb_start's start rays gives them bit for bit.
 ILL_CONDITIONED = (

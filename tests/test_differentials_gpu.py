@@ -7,41 +7,12 @@ import numpy as np
 import pytest
 
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, ZoicCamera, _capi
-from zoic_amd.workloads import CONFIGS, camera_params, hexagon_bokeh, ray_rng_states
+from zoic_amd.workloads import CONFIGS, ray_rng_states
 
+from device_cases import camera as _camera, oracle as _oracle, params as _params, samples as _samples
 from differentials_ref import kolb_jacobian_fd, kolb_start, rel_err, surfaces, thin_jacobian_fd, trace
 
 N = 1 << 16
-
-
-def _params(cfg, **over):
-    p = camera_params(cfg)
-    p.update(over)
-    return p
-
-
-def _camera(p, precision=PRECISION_STRICT):
-    cam = ZoicCamera(device=0)
-    if p.get("useImage"):
-        cam.set_bokeh_image(hexagon_bokeh())
-    cam.set_precision(precision)
-    cam.update(**p)
-    return cam
-
-
-def _oracle(oracle_lib, p):
-    oc = oracle_lib.OracleCamera()
-    if p.get("useImage"):
-        oc.set_bokeh_image(hexagon_bokeh())
-    oc.update(**p)
-    return oc
-
-
-def _samples(n, aspect=16 / 9, seed=5):
-    """random screen samples over the whole frame (a frame's first rays in lattice order would all sit in one corner)"""
-    rs = np.random.RandomState(seed)
-    s = np.stack([rs.uniform(-1, 1, n), rs.uniform(-1, 1, n) / aspect, rs.uniform(0, 1, n), rs.uniform(0, 1, n)], 1)
-    return np.ascontiguousarray(s, np.float32)
 
 
 def _rays_and_diffs(cam, s_np, **kw):

@@ -1,6 +1,6 @@
 """Traced ray differentials of spectral records on the MI355X (zoic_ray_differentials_spectral_device) over the pinned corpus of
-machine-made lenses (machine_lens_corpus.py), after tests/test_differentials_spectral_corpus_cpu.py, whose frame, wavelengths,
-reference, conditioning rule and groups these tests share:
+machine-made lenses (machine_lens_corpus.py), after tests/test_differentials_spectral_corpus_cpu.py, with which these tests share the
+frame, wavelengths, reference, conditioning rule and groups of differentials_spectral_corpus.py:
 
   A  on the accuracy group a STRICT camera's screen tangents and wavelength tangent against the f64 reference started from the
      records' own tries -- the tries the spectral forward kernel accepted at each ray's wavelength -- within
@@ -60,14 +60,15 @@ import backward_spectral_ref as bs
 import differentials_ref as dref
 import differentials_spectral_ref as sref
 import machine_lens_corpus as mc
-import test_traceback_jacobian_gpu as tj
+import host_drivers
+import traceback_jacobian_ref as jr
+from device_cases import BIG, bits as _bits, spectral_run as _run
+from differentials_spectral_corpus import (ACCURACY, HOST_DEVICE, IDENTITIES_ONLY, conditions, figures, frame, line, reference, reference_rows, tables,
+                                           wave_with as _wave_with)
 from fuzz_cameras import MachineLens, rows_of
-from test_backward_corpus_gpu import EDGE_CAP, PREFIXES
-from test_differentials_spectral_corpus_cpu import (ACCURACY, HOST_DEVICE, IDENTITIES_ONLY, conditions, figures, frame, line, reference,
-                                                    reference_rows, tables)
-from test_differentials_spectral_cpu import build_driver, run_driver
-from test_differentials_spectral_gpu import BIG, LAMBDA_D32, _bits, _run
-from test_spectral_gpu import BAD
+from host_drivers import run_differentials_spectral as run_driver
+from machine_lens_corpus import EDGE_CAP, PREFIXES
+from spectral_ref import BAD, LAMBDA_D32
 
 pytestmark = pytest.mark.gpu
 
@@ -165,8 +166,8 @@ def test_spectral_differentials_correct(gpu, oracle_lib, name):
 
 # ---- B: against the host build ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("sdiffcorpusgpu"))
+def driver():
+    return host_drivers.differentials_spectral()
 
 
 @pytest.mark.parametrize("name", HOST_DEVICE)
@@ -209,12 +210,6 @@ def test_kernel_against_the_host_build(gpu, oracle_lib, driver, name):
 
 
 # ---- C: exact identities ------------------------------------------------------------------------------------------------------------
-def _wave_with(live, least, after=4):
-    """the first wave (64 consecutive rows) after wave `after` with at least `least` live rows"""
-    per = live[:len(live) // 64 * 64].reshape(-1, 64).sum(1)
-    return int(np.flatnonzero(per[after + 1:] >= least)[0]) + after + 1
-
-
 @pytest.mark.parametrize("name", mc.NAMES)
 def test_d_line_and_flag_identities(gpu, name):
     """all wavelengths 587.5618: the 12 floats are ray_differentials' without wavelengths and the wavelength tangent is not all zero
@@ -384,8 +379,8 @@ def test_round_trip_with_the_spectral_jacobian(gpu, oracle_lib, name):
     import torch
     cam, p = mc.camera(name, device=0, precision=PRECISION_FAST)
     info, disp = cam.info(), cam.dispersion()
-    n = tj.N
-    smp = torch.from_numpy(synthetic_samples(n, tj.W, tj.H, tj.SPP)).to("cuda:0")
+    n = jr.N
+    smp = torch.from_numpy(synthetic_samples(n, jr.W, jr.H, jr.SPP)).to("cuda:0")
     st = torch.from_numpy(ray_rng_states(n).view(np.int32)).to("cuda:0")
     lam_h = np.random.default_rng(23).uniform(400.0, 700.0, n).astype(F32)
     lam = torch.from_numpy(lam_h).to("cuda:0")
@@ -408,8 +403,8 @@ def test_round_trip_with_the_spectral_jacobian(gpu, oracle_lib, name):
     keep = keep0 & keep1
     pick = np.flatnonzero(keep)[:: max(1, keep.sum() // 512)][:512]
     assert len(pick) >= 384, len(pick)
-    r0 = tj._residual(jac0[pick], T0[pick])
-    r1 = tj._residual(jac1[pick], T1[pick])
+    r0 = jr.residual(jac0[pick], T0[pick])
+    r1 = jr.residual(jac1[pick], T1[pick])
     print("%-10s %d rays; |J T - I| spectral median %.3g p99 %.3g; d-line median %.3g p99 %.3g; ratios %.2f / %.2f" % (
         name, len(pick), np.median(r1), np.percentile(r1, 99), np.median(r0), np.percentile(r0, 99), np.median(r1) / np.median(r0),
         np.percentile(r1, 99) / np.percentile(r0, 99)))

@@ -4,36 +4,32 @@ csrc/differentials_spectral.hpp (compiled for the host) agrees with f64 central 
 needed on the shipped TESSAR, the wavelength tangent has the sign and the size physics asks for, and the gfx950 kernels keep their
 budget.
 
-Rays: ~10 k passing rays per lens, wavelengths uniform in [400, 700] nm plus the eight of test_spectral_gpu.WAVES.  The measured
+Rays: ~10 k passing rays per lens, wavelengths uniform in [400, 700] nm plus the eight of spectral_ref.WAVES.  The measured
 figures are in test_wavelength_tangent_ratio_to_its_own_size.
 """
 import ctypes
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from zoic_amd import _capi
-from zoic_amd.camera import ZoicCamera
-from zoic_amd.workloads import camera_params
 
 import differentials_ref as dref
 import differentials_spectral_ref as sref
-from test_differentials_cpu import _clangxx, _passing_rays
-from test_spectral_gpu import SINGLET, WAVES
+import host_drivers
+from device_cases import bits_f32 as _bits
+from differentials_spectral_ref import lens_rays as _rays, passes as _passes, ray_wavelengths as _wavelengths, tables
+from host_drivers import run_differentials_spectral as run_driver
+from library_facts import header_text, kernel_resources
+from spectral_ref import LAMBDA_D32, SINGLET, WAVES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
 NAME = "zoic_ray_differentials_spectral_device"
 F32 = np.float32
-LAMBDA_D32 = F32(587.5618)
 
 
 def test_abi_declares_and_exports_the_call():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     assert re.search(r"\b%s\s*\(" % NAME, text)
     assert NAME in _capi.SYMBOLS
     assert len(_capi.SYMBOLS[NAME][1]) == 12
@@ -42,126 +38,9 @@ def test_abi_declares_and_exports_the_call():
     assert _capi.load().zoic_abi_version() == 5 and _capi.ABI_VERSION == 5
 
 
-DRIVER = r"""
-#include "differentials_spectral.hpp"
-// surf: count x (center, radius2, sign, eta_d); disp: count x (iorD, cauchyB); lambda: one per ray.  out 12, chroma 6, prim 6 floats
-// per ray.  mode 0: kolb_differentials on the d-line table; 1: spectral, screen tangents only; 2: with the wavelength tangent
-extern "C" int zds_trace(int mode, int count, const float *surf, const float *disp, float halfSensor, int n, const float *lambda,
-                         const float *o, const float *d, float *out, float *chroma, float *prim)
-{
-    using namespace zoic;
-    Surface S[kMaxSurfaces] = {};
-    SpectralTable W = {};
-    W.count = count;
-    for (int i = 0; i < count; ++i) {
-        S[i].center = surf[4 * i]; S[i].radius2 = surf[4 * i + 1]; S[i].sign = surf[4 * i + 2]; S[i].eta = surf[4 * i + 3];
-        W.iorD[i] = disp[2 * i]; W.cauchyB[i] = disp[2 * i + 1];
-    }
-    const auto surfAt = [&](int i) { return S[i]; };
-    const SpectralTable *WP = &W;
-    for (int r = 0; r < n; ++r) {
-        const V3 o0{o[3 * r], o[3 * r + 1], o[3 * r + 2]}, d0{d[3 * r], d[3 * r + 1], d[3 * r + 2]};
-        V3 po, pd;
-        SpectralDifferential g{};
-        if (mode == 0) g.screen = kolb_differentials(surfAt, count, halfSensor, o0, d0, &po, &pd);
-        else if (mode == 1) g = kolb_differentials_spectral<false>(surfAt, WP, count, lambda[r], halfSensor, o0, d0, &po, &pd);
-        else g = kolb_differentials_spectral<true>(surfAt, WP, count, lambda[r], halfSensor, o0, d0, &po, &pd);
-        const V3 v[8] = {g.screen.dOdx, g.screen.dOdy, g.screen.dDdx, g.screen.dDdy, g.dOdl, g.dDdl, po, pd};
-        for (int k = 0; k < 4; ++k) { out[12 * r + 3 * k] = v[k].x; out[12 * r + 3 * k + 1] = v[k].y; out[12 * r + 3 * k + 2] = v[k].z; }
-        for (int k = 0; k < 2; ++k) { chroma[6 * r + 3 * k] = v[4 + k].x; chroma[6 * r + 3 * k + 1] = v[4 + k].y; chroma[6 * r + 3 * k + 2] = v[4 + k].z; }
-        for (int k = 0; k < 2; ++k) { prim[6 * r + 3 * k] = v[6 + k].x; prim[6 * r + 3 * k + 1] = v[6 + k].y; prim[6 * r + 3 * k + 2] = v[6 + k].z; }
-    }
-    return 0;
-}
-"""
-
-
-def build_driver(directory):
-    """the host build of csrc/differentials_spectral.hpp (shared with tests/test_differentials_spectral_gpu.py)"""
-    src, so = os.path.join(str(directory), "driver.cpp"), os.path.join(str(directory), "driver.so")
-    with open(src, "w") as f:
-        f.write(DRIVER)
-    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
-                           "-I" + os.path.join(ROOT, "include"), src, "-o", so])
-    return ctypes.CDLL(so)
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("sdiffdriver"))
-
-
-def run_driver(drv, mode, surf, disp, hs, lam, o, d):
-    """(out (n,12), chroma (n,6), prim (n,6)) float32 of the host driver"""
-    n = len(o)
-    out, chroma, prim = np.zeros((n, 12), F32), np.zeros((n, 6), F32), np.zeros((n, 6), F32)
-    fp = ctypes.POINTER(ctypes.c_float)
-    keep = [np.ascontiguousarray(a, F32) for a in (surf, np.stack([disp["ior_d"], disp["cauchy_b"]], 1), lam, o, d)]
-    c = [a.ctypes.data_as(fp) for a in keep]
-    rc = drv.zds_trace(int(mode), len(surf), c[0], c[1], ctypes.c_float(float(hs)), n, c[2], c[3], c[4], out.ctypes.data_as(fp),
-                       chroma.ctypes.data_as(fp), prim.ctypes.data_as(fp))
-    assert rc == 0
-    return out, chroma, prim
-
-
-def tables(cfg, abbe=None, lens_text=None, **over):
-    """(params, info, dispersion, surfaces, halfSensor) of a tables-only camera"""
-    p = camera_params(cfg)
-    p["useImage"] = False
-    p.pop("bokehPath", None)
-    p.update(over)
-    cam = ZoicCamera(device=-1)
-    if lens_text is not None:
-        cam.set_lens_text(lens_text)
-    cam.update(**p)
-    if abbe is not None:
-        cam.set_abbe_numbers(np.full(cam.info()["lensCount"], abbe, F32))
-    info, disp = cam.info(), cam.dispersion()
-    cam.close()
-    return p, info, disp, dref.surfaces(info), F32(F32(p["sensorWidth"]) * F32(0.5))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-_RAYS = {}
-
-
-def _rays(cfg, oracle_lib, want=10000):
-    """~10 k rays the oracle's d-line trace lets through (test_differentials_cpu's set), shared by the tests below"""
-    if cfg not in _RAYS:
-        p, info, _, _, hs = tables(cfg)
-        oc = oracle_lib.OracleCamera()
-        oc.update(**p)
-        o, d, _, _ = _passing_rays(oc, info, hs, np.random.RandomState(11), want)
-        assert len(o) >= want // 2, (cfg, len(o))
-        _RAYS[cfg] = (o, d)
-    return _RAYS[cfg]
-
-
-def _wavelengths(n, seed=4):
-    lam = np.random.RandomState(seed).uniform(400, 700, n).astype(F32)
-    lam[:8 * (n // 64):n // 64][:8] = WAVES   # the eight fixed ones, spread over the batch
-    return lam
-
-
-def _passes(surf, eta, o, d, aperture=None):
-    """the f64 trace meets every sphere and refracts everywhere (no |.| of the restatement flips a sign): the path is a real one;
-    aperture (count,): the hit points also lie within each interface's housing"""
-    o = np.asarray(o, np.float64).copy()
-    d = np.asarray(d, np.float64).copy()
-    ok = np.ones(len(o), bool)
-    for i, (c, r2, sg, _) in enumerate(np.asarray(surf, np.float64)):
-        u = d / np.linalg.norm(d, axis=1, keepdims=True)
-        L = np.stack([-o[:, 0], -o[:, 1], c - o[:, 2]], 1)
-        tca = (L * u).sum(1)
-        ok &= (L * L).sum(1) - tca * tca <= r2
-        o, d, c1, _ = sref.interface(o, d, c, r2, sg, eta[:, i])
-        ok &= eta[:, i] ** 2 * (1 - c1 * c1) <= 1.0
-        if aperture is not None:
-            ok &= o[:, 0] ** 2 + o[:, 1] ** 2 <= (0.5 * float(aperture[i])) ** 2
-    return ok
+def driver():
+    return host_drivers.differentials_spectral()
 
 
 def test_per_ray_interface_is_the_d_line_restatement():
@@ -381,12 +260,7 @@ def test_wavelength_tangent_integrates_to_the_colour_shift(driver):
 def test_spectral_differential_kernels_budget():
     """0 scratch and 0 VGPR spills for every spectral differential kernel of the built library (its code object's metadata), at most
     128 VGPRs for the 12-float ones; the d-line pass still has its four kernels"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    all_k = code_object_regs.kernel_resources(_capi.LIB_PATH)
+    all_k = kernel_resources()
     res = {k: v for k, v in all_k.items() if "spectral_diff" in k}
     assert len(res) == 4, sorted(res)
     for k, v in res.items():

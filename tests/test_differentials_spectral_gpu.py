@@ -14,39 +14,21 @@ from zoic_amd.workloads import ray_rng_states
 
 import differentials_ref as dref
 import differentials_spectral_ref as sref
-from test_differentials_gpu import _oracle, _params, _samples
-from test_differentials_spectral_cpu import build_driver, run_driver
-from test_spectral_gpu import BAD, WAVES, _camera
+import host_drivers
+from device_cases import BIG, bits as _bits, camera as _camera, oracle as _oracle, params as _params, samples as _samples, spectral_run as _run
+from host_drivers import run_differentials_spectral as run_driver
+from spectral_ref import BAD, LAMBDA_D32, WAVES
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-LAMBDA_D32 = F32(587.5618)
-BIG = 2048 * 256 + 65
 SIZES = [1, 63, 65, 4096, BIG]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _abbe(p, V):
     if V is None:
         return None
     return np.full(ZoicCamera(device=-1).update(**dict(p, useImage=False)).info()["lensCount"], V, F32)
-
-
-def _run(cam, s_np, lam_np, chromatic=True, states=None, base=0, **kw):
-    """records and differentials of one spectral batch: (rays (n,8), diffs (n,12), chroma (n,6) or None) as numpy"""
-    import torch
-    s = torch.from_numpy(s_np).cuda()
-    lam = torch.from_numpy(lam_np).cuda()
-    st = None if states is None else torch.from_numpy(states.view(np.int32)).cuda()
-    rays = cam.create_rays(s, wavelengths=lam, rng_states=st, ray_index_base=base)["rays"]
-    r = cam.ray_differentials(s, rays, rng_states=st, ray_index_base=base, wavelengths=lam, chromatic=chromatic, **kw)
-    torch.cuda.synchronize()
-    d, c = r if chromatic else (r, None)
-    return rays.cpu().numpy(), d.cpu().numpy(), None if c is None else c.cpu().numpy()
 
 
 CASES = [("C2", {}, None, False), ("C3", {}, 50.0, False), ("C5", {}, None, True), ("C2", dict(kolbSamplingLUT=False), None, False)]
@@ -315,7 +297,7 @@ def test_error_codes(gpu):
     cam.close()
 
 
-def test_host_equals_device(gpu, oracle_lib, tmp_path):
+def test_host_equals_device(gpu, oracle_lib):
     """The host build of csrc/differentials_spectral.hpp from the same starts against the kernel.  diff_rsqrt / diff_sqrt / diff_rcp are
     1-ulp instructions on the device, so not bitwise: the screen tangents within the d-line test's figures for this arithmetic
     (median <= 1e-5, 99.9 % within 1e-3: device and host each meet them against f64), the wavelength tangent within the same bounds
@@ -335,7 +317,7 @@ def test_host_equals_device(gpu, oracle_lib, tmp_path):
     o0, d0 = dref.kolb_start(oc, p, s[live], tries, states[live], oracle_lib)
     surf = dref.surfaces(oc.lens_table())
     hs = F32(F32(p["sensorWidth"]) * F32(0.5))
-    out, ch, prim = run_driver(build_driver(tmp_path), 2, surf, disp, hs, lam[live], o0, d0)
+    out, ch, prim = run_driver(host_drivers.differentials_spectral(), 2, surf, disp, hs, lam[live], o0, d0)
     assert np.allclose(prim, rays[live, 0:6], rtol=1e-5, atol=1e-5)
     e = dref.rel_err(diffs[live], out)
     part = sref.wavelength_contributions(surf, disp, lam[live], o0, d0)

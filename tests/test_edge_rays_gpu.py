@@ -13,6 +13,7 @@ from zoic_amd import PRECISION_FAST, PRECISION_FAST_UNCHECKED, PRECISION_STRICT,
 from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states
 
 import edge_rays as E
+from device_cases import bits_f32 as _bits, delta as _delta
 from fuzz_cameras import CUSTOM_LENS_5, CUSTOM_LENS_14, _oracle_spectral, perturbed_prescription
 from spectral_ref import LAMBDA_D, spectral_iors
 
@@ -27,10 +28,6 @@ CUSTOM_KW = dict(sensorWidth=3.6, sensorHeight=2.4, focalLength=5.0, fStop=2.8, 
 PERTURBED = [("tessar_f2.8.dat", 11, 0.1, "keep"), ("double_gauss_f2.0.dat", 12, 0.1, "drop"), ("petzval_f1.25.dat", 13, 0.1, "double"),
              ("triplet_f2.5.dat", 14, 0.1, "keep")]
 PERTURBED_KW = dict(focalLength=5.0, fStop=2.8, focalDistance=120.0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _same(a, b):
@@ -48,13 +45,6 @@ def _camera(p, lens_text=None, image=None, abbe=None, precision=PRECISION_STRICT
     cam.set_precision(precision)
     cam.update(**p)
     return cam
-
-
-def _delta(cam, fn):
-    before = cam.counters()
-    r = fn()
-    after = cam.counters()
-    return r, {k: after[k] - before[k] for k in after}
 
 
 def _setups():

@@ -6,7 +6,7 @@ counts 5 ... 14 and 32, the stop at trace index 0, NO_REFLECTION on an interface
 between equal media, more than 32 pairs.
 
 Starts: differentials_ref.kolb_start on the oracle's d-line records of the frame traceback_cases.frame_samples(), reference_rows of
-the live ones (at most 4096), at the wavelengths of test_differentials_spectral_corpus_cpu.frame().  The f64 restatement runs on a
+the live ones (at most 4096), at the wavelengths of differentials_spectral_corpus.frame().  The f64 restatement runs on a
 stride of at most 1024 of them (plates-32: 128), all pairs.  MARGIN and MAX_LEFT_OUT are test_ghost_cpu's, unchanged.
 
 The corpus (test_the_corpus_is_the_pinned_one).  `equal`: interfaces other than the stop between equal media at the d-line.  Only two
@@ -85,9 +85,12 @@ import ghost_ref as gref
 import lens_losses_corpus as lc
 import machine_lens_corpus as mc
 from fuzz_cameras import MachineLens
-from test_ghost_cpu import MARGIN, MAX_LEFT_OUT, _bits, _bound, _expected_pairs, build_driver, run_records, run_trace, split
-from test_transmittance_cpu import FILM_INDEX, FILM_LAMBDA0
-from test_transmittance_cpu import build_driver as build_transmittance_driver, run_driver as run_transmittance_driver
+import host_drivers
+from device_cases import bits_f32 as _bits
+from ghost_ref import MARGIN, MAX_LEFT_OUT, bound as _bound, expected_pairs as _expected_pairs
+from host_drivers import run_ghost_records as run_records, run_ghost_trace as run_trace, run_transmittance as run_transmittance_driver, split_ghost as split
+from lens_losses_corpus import constructed as _constructed
+from transmittance_ref import FILM_INDEX, FILM_LAMBDA0
 from zoic_amd import ZoicCamera
 from zoic_amd.camera import ZoicError
 
@@ -102,13 +105,13 @@ MIN_ROWS = 2048            # starts of a lens that pass at their wavelength in b
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("ghostcorpus"))
+def driver():
+    return host_drivers.ghost()
 
 
 @pytest.fixture(scope="module")
-def tdriver(tmp_path_factory):
-    return build_transmittance_driver(tmp_path_factory.mktemp("ghostcorpus_trans"))
+def tdriver():
+    return host_drivers.transmittance()
 
 
 # ---- 1: the corpus -----------------------------------------------------------------------------------------------------------------
@@ -174,19 +177,6 @@ def test_reference_alone_meets_the_cap(oracle_lib, name):
     print("%-10s reference: ghosts %6d  below %.5f  %s" % (name, R["ghosts"], R["below"], dict(zip(gref.REASONS[:6], R["seen"][:6].tolist()))))
     assert R["below"] <= MAX_LEFT_OUT, (name, R["below"])
     assert R["seen"][gref.TRACED] >= 1000 and R["seen"][gref.CLIPPED] >= 100, (name, R["seen"])
-
-
-def _constructed(name):
-    """pairs of the lens the pair list leaves out, with the dead record each must give: (a, b, reason, interface, leg)"""
-    T = lc.tables(name)
-    count, stop, out = T["count"], T["stop"], []
-    ok = [i for i in range(count) if i != stop and i not in T["equal"]]
-    for e in T["equal"]:
-        out += [(e, b, gref.NO_REFLECTION, e, 0) for b in ok if b < e][:2]              # a on the equal-media interface: leg 0
-        out += [(a, e, gref.NO_REFLECTION, e, 1) for a in ok if a > e][-2:]             # b on it: leg 1
-    if stop == 0:
-        out += [(a, 0, gref.NO_REFLECTION, 0, 1) for a in ok]                           # every pair (a, 0)
-    return out
 
 
 def test_reference_alone_sees_every_reason(oracle_lib):

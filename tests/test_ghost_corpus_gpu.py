@@ -37,101 +37,30 @@ same updates; without the LUT records and ghosts are bitwise the first ones.
 import numpy as np
 import pytest
 
-from zoic_amd import PRECISION_FAST, PRECISION_STRICT
+from zoic_amd import PRECISION_FAST
 from zoic_amd.workloads import ray_rng_states
 
 import ghost_ref as gref
 import lens_losses_corpus as lc
 import machine_lens_corpus as mc
+import host_drivers
+from device_cases import bits_f32 as _bits
+from differentials_spectral_corpus import WAVE_PERIOD, frame, reference_rows
 from fuzz_cameras import _oracle_spectral
-from test_backward_corpus_gpu import PREFIXES
-from test_differentials_spectral_corpus_cpu import WAVE_PERIOD, frame, reference_rows
-from test_ghost_cpu import build_driver, run_records, split
-from test_ghost_corpus_cpu import _constructed
-from test_spectral_gpu import BAD, WAVES
+from host_drivers import run_ghost_records as run_records, split_ghost as split
+from lens_losses_corpus import (BIG, SPLIT, constructed as _constructed, device_camera as _camera, device_inputs as _inputs, device_launch as _launch,
+                                device_starts as _starts, record_tries as _tries, same_words as _same, take as _take)
+from machine_lens_corpus import PREFIXES
+from spectral_ref import BAD, LAMBDA_D32, WAVES
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-BIG = 2048 * 256 + 65
-SPLIT = [0, 1, 64, 5037]
-LAMBDA_D32 = F32(587.5618)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-def _tries(rays):
-    return ((_bits(rays[:, 7]) >> 1) & 31).astype(np.int64)
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("ghostcorpus_gpu"))
-
-
-def _camera(name, precision=PRECISION_STRICT, coated=False, **over):
-    cam, p = lc.camera(name, device=0, precision=precision, **over)
-    if coated:
-        nc, l0 = lc.tables(name)["film"]
-        cam.set_coatings(nc[::-1], l0[::-1])      # file order
-    return cam
-
-
-_INPUTS = []
-
-
-def _inputs():
-    """the frame on the device: (samples, rng states as int32, wavelengths) tensors, uploaded once and never written to"""
-    if not _INPUTS:
-        import torch
-        s, st, lam = frame()
-        _INPUTS.extend([torch.from_numpy(np.array(s)).cuda(), torch.from_numpy(np.array(st).view(np.int32)).cuda(), torch.from_numpy(np.array(lam)).cuda()])
-    return tuple(_INPUTS)
-
-
-_LAUNCH = {}
-
-
-def _launch(name):
-    """One STRICT launch of the frame at its wavelengths behind lens `name`: the records (N, 8) as numpy, not to be written to"""
-    if name not in _LAUNCH:
-        import torch
-        cam = _camera(name)
-        ts, tst, tl = _inputs()
-        rays = cam.create_rays(ts, wavelengths=tl, rng_states=tst)["rays"]
-        torch.cuda.synchronize()
-        _LAUNCH[name] = rays.cpu().numpy()
-        _LAUNCH[name].setflags(write=False)
-        cam.close()
-    return _LAUNCH[name]
-
-
-_STARTS = {}
-
-
-def _starts(oracle_lib, name):
-    """reference_rows of the launch's live records and their starts from the records' own tries: dict of rows, o, d, lam"""
-    if name not in _STARTS:
-        rays = _launch(name)
-        rows = reference_rows(np.flatnonzero(rays[:, 6] != 0), _tries(rays))
-        o, d = lc.kolb_starts(oracle_lib, name, rows, _tries(rays)[rows])
-        _STARTS[name] = dict(rows=rows, o=o, d=d, lam=np.array(frame()[2][rows]))
-    return _STARTS[name]
-
-
-def _take(rows, rays):
-    """device tensors of the frame's rows `rows`: samples, wavelengths, rng states and the records `rays` (numpy (len(rows), 8))"""
-    import torch
-    ts, tst, tl = _inputs()
-    idx = torch.from_numpy(np.asarray(rows, np.int64)).cuda()
-    return ts[idx].contiguous(), tl[idx].contiguous(), tst[idx].contiguous(), torch.from_numpy(np.array(rays)).cuda()
-
-
-def _same(a, b):
-    import torch
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+def driver():
+    return host_drivers.ghost()
 
 
 def _dead(reason, interface=0, leg=0):

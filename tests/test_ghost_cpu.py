@@ -3,13 +3,11 @@ arithmetic of csrc/ghost.hpp (compiled for the host) agrees with the pinned STRI
 restatement in plain sphere geometry (ghost_ref.py) on every valid pair of C2 - C5, bare and coated, and the physics is what an
 optician expects: the on-axis closed form, the paraxial limit of the three legs, weaker ghosts under a coating.
 
-Starts: test_differentials_spectral_cpu._rays (~10 k passing rays per lens, C2 - C5) with _wavelengths.  The main starts pass by
+Starts: differentials_spectral_ref.lens_rays (~10 k passing rays per lens, C2 - C5) with ray_wavelengths.  The main starts pass by
 construction; most ghosts do not.  The measured figures are in the constants below and in the docstrings of the tests that took them."""
 import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,22 +16,22 @@ from zoic_amd import _capi
 from zoic_amd.camera import LENS_DIR, ZoicCamera
 
 import ghost_ref as gref
+import host_drivers
 import transmittance_ref as tref
-from test_differentials_cpu import _clangxx
-from test_differentials_spectral_cpu import _rays, _wavelengths, tables
-from test_transmittance_cpu import FILM_INDEX, FILM_LAMBDA0, LENSES, films_where_media_differ, housings
-from test_transmittance_cpu import build_driver as build_transmittance_driver, run_driver as run_transmittance_driver
+from device_cases import bits_f32 as _bits
+from differentials_spectral_ref import lens_rays as _rays, ray_wavelengths as _wavelengths, tables
+from ghost_ref import MARGIN, MAX_LEFT_OUT, bound as _bound, expected_pairs as _expected_pairs
+from host_drivers import run_ghost_records as run_records, run_ghost_trace as run_trace, run_transmittance as run_transmittance_driver, split_ghost as split
+from library_facts import header_text, kernel_resources
+from transmittance_ref import FILM_INDEX, FILM_LAMBDA0, LENSES, films_where_media_differ, housings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
 NAMES = ("zoic_create_ghost_rays_device", "zoic_camera_get_ghost_pairs")
 F32 = np.float32
 LAMBDA_D32 = F32(587.5618)
 INVALID = _capi.STATUS_NAMES.index("ZOIC_ERR_INVALID_ARGUMENT")
 NO_DEVICE = _capi.STATUS_NAMES.index("ZOIC_ERR_NO_DEVICE")
 CFGS = ["C2", "C3", "C4", "C5"]
-MARGIN = 1e-4          # a ghost whose f64 path came closer than this (relative) to any decision may be left out ...
-MAX_LEFT_OUT = 0.02    # ... and at most this share of a lens's ghosts is
 
 # Plain path ("no pair"), C2 - C5 from the same starts: the largest |host build of ghost.hpp - host build of trace_lens_spectral_strict|
 # of the exit origin (cm) and of the unit exit direction, and |weight - path_transmittance| (clang++ 22, x86-64); asserted: 4 x them,
@@ -44,18 +42,10 @@ PLAIN_MEASURED = dict(origin=3.815e-6, dir=3.099e-6, weight=3.577e-7)     # all 
 MEASURED = dict(origin=1.557e-4, dir=1.643e-4, weight=5.274e-6)     # origin and dir on C4, weight on C3 bare
 
 
-def _bound(measured):
-    return {k: 4 * v for k, v in measured.items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 # ---- the ABI --------------------------------------------------------------------------------------------------------------------
 def test_abi_declares_and_exports_the_calls():
     header = open(os.path.join(ROOT, "include", "zoic_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(_capi.LIB_PATH)
     for name in NAMES:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -68,12 +58,6 @@ def test_abi_declares_and_exports_the_calls():
                                   "INVALID_PAIR"), 1):
         assert re.search(r"#define ZOIC_GHOST_%s %du\b" % (macro, code), text), macro
     assert re.search(r"#define ZOIC_GHOST_MAX_PAIRS 32\b", text)
-
-
-def _expected_pairs(disp):
-    n1 = disp["ior_d"]
-    differ = n1 != np.append(n1[1:], F32(1.0))
-    return np.array([(a, b) for a in range(len(n1)) for b in range(a) if differ[a] and differ[b]], np.int32).reshape(-1, 2)
 
 
 def test_tables_only_camera():
@@ -116,131 +100,9 @@ def test_pair_list_of_the_shipped_lenses(lens):
         assert count == 8 and len(pairs) == 21                  # 8 surfaces, one of them the stop: 7 choose 2
 
 
-# ---- the host driver ------------------------------------------------------------------------------------------------------------
-DRIVER = r"""
-#include "ghost.hpp"
-using namespace zoic;
-// rows: count x (radius, thickness, aperture); media: count x (iorD, cauchyB, filmIndex, filmLambda0)
-static void tables(int model, int count, const float *rows, int stop, float user, const float *media, GhostTable &G, GhostMedia &M)
-{
-    float radius[kMaxSurfaces] = {}, thickness[kMaxSurfaces] = {}, aperture[kMaxSurfaces] = {};
-    M = GhostMedia{};
-    for (int i = 0; i < count && i < kMaxSurfaces; ++i) {
-        radius[i] = rows[3 * i]; thickness[i] = rows[3 * i + 1]; aperture[i] = rows[3 * i + 2];
-        M.iorD[i] = media[4 * i]; M.cauchyB[i] = media[4 * i + 1]; M.filmIndex[i] = media[4 * i + 2]; M.filmLambda0[i] = media[4 * i + 3];
-    }
-    fill_ghost_table(G, model, count, radius, thickness, aperture, stop, user);
-}
-static void put(float *out, const GhostRay &g)
-{
-    out[0] = g.ox; out[1] = g.oy; out[2] = g.oz; out[3] = g.dx; out[4] = g.dy; out[5] = g.dz; out[6] = g.weight;
-    __builtin_memcpy(out + 7, &g.flags, 4);
-}
-// ghost_trace of one pair (a = b = -1: the plain path) from n starts; out: n x 8
-extern "C" int zgh_trace(int model, int count, const float *rows, int stop, float user, const float *media, int a, int b, int n,
-                         const float *lambda, const float *o, const float *d, float *out)
-{
-    GhostTable G; GhostMedia M;
-    tables(model, count, rows, stop, user, media, G, M);
-    const GhostTable *GP = &G; const GhostMedia *MP = &M;
-    for (int r = 0; r < n; ++r)
-        put(out + 8 * r, ghost_trace(GP, MP, a, b, lambda[r], V3{o[3 * r], o[3 * r + 1], o[3 * r + 2]}, V3{d[3 * r], d[3 * r + 1], d[3 * r + 2]}));
-    return G.model;
-}
-// ghost_record of p packed pairs from n starts, as the kernel calls it; have: n bytes (the main record has weight); out: n x p x 8
-extern "C" int zgh_records(int model, int count, const float *rows, int stop, float user, const float *media, int p, const uint32_t *pairs,
-                           int n, const float *lambda, const float *o, const float *d, const unsigned char *have, float *out)
-{
-    GhostTable G; GhostMedia M;
-    tables(model, count, rows, stop, user, media, G, M);
-    const GhostTable *GP = &G; const GhostMedia *MP = &M;
-    for (int r = 0; r < n; ++r)
-        for (int j = 0; j < p; ++j)
-            put(out + 8 * (static_cast<size_t>(r) * p + j), ghost_record(GP, MP, pairs[j], have[r] != 0, lambda[r], V3{o[3 * r], o[3 * r + 1], o[3 * r + 2]},
-                                                                         V3{d[3 * r], d[3 * r + 1], d[3 * r + 2]}));
-    return G.model;
-}
-// the pinned STRICT path from the same starts: surf count x (center, radius2, sign, housing2); out: n x 7 (o, d as the trace leaves
-// them, 1.0 where it passes)
-extern "C" int zgh_strict(int count, const float *surf, const float *disp, int n, const float *lambda, const float *o, const float *d, float *out)
-{
-    Surface S[kMaxSurfaces] = {};
-    SpectralTable W = {};
-    W.count = count;
-    for (int i = 0; i < count; ++i) {
-        S[i].center = surf[4 * i]; S[i].radius2 = surf[4 * i + 1]; S[i].sign = surf[4 * i + 2]; S[i].housing2 = surf[4 * i + 3];
-        W.iorD[i] = disp[2 * i]; W.cauchyB[i] = disp[2 * i + 1];
-    }
-    const Surface *SP = S; const SpectralTable *WP = &W;
-    int passed = 0;
-    for (int r = 0; r < n; ++r) {
-        V3 po{o[3 * r], o[3 * r + 1], o[3 * r + 2]}, pd{d[3 * r], d[3 * r + 1], d[3 * r + 2]};
-        uint32_t tir = 0;
-        const bool ok = trace_lens_spectral_strict(SP, WP, count, spectral_dl(lambda[r]), po, pd, tir);
-        passed += ok ? 1 : 0;
-        float *q = out + 7 * r;
-        q[0] = po.x; q[1] = po.y; q[2] = po.z; q[3] = pd.x; q[4] = pd.y; q[5] = pd.z; q[6] = ok ? 1.0f : 0.0f;
-    }
-    return passed;
-}
-"""
-
-
-def build_driver(directory):
-    """the host build of csrc/ghost.hpp (shared with tests/test_ghost_gpu.py)"""
-    src, so = os.path.join(str(directory), "driver.cpp"), os.path.join(str(directory), "driver.so")
-    with open(src, "w") as f:
-        f.write(DRIVER)
-    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
-                           "-I" + os.path.join(ROOT, "include"), src, "-o", so])
-    return ctypes.CDLL(so)
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("ghostdriver"))
-
-
-def _tables_args(L, disp, film):
-    count = L["count"]
-    rows = np.stack([L["radius"], L["thickness"], L["aperture"]], 1)
-    fl = (np.zeros(count, F32), np.zeros(count, F32)) if film is None else film
-    media = np.stack([disp["ior_d"], disp["cauchy_b"], fl[0], fl[1]], 1)
-    return [np.ascontiguousarray(a, F32) for a in (rows, media)]
-
-
-def run_trace(drv, L, disp, lam, o, d, a, b, film=None, model=1):
-    """(n, 8) float32 records of ghost_trace for one pair ((-1, -1): the plain path); L = ghost_ref.lens(info)"""
-    fp = ctypes.POINTER(ctypes.c_float)
-    keep = _tables_args(L, disp, film) + [np.ascontiguousarray(v, F32) for v in (lam, o, d)]
-    n = len(keep[3])
-    out = np.full((n, 8), np.nan, F32)
-    drv.zgh_trace(int(model), L["count"], keep[0].ctypes.data_as(fp), int(L["stop"]), ctypes.c_float(float(L["user"])), keep[1].ctypes.data_as(fp),
-                  int(a), int(b), n, keep[2].ctypes.data_as(fp), keep[3].ctypes.data_as(fp), keep[4].ctypes.data_as(fp), out.ctypes.data_as(fp))
-    return out
-
-
-def run_records(drv, L, disp, lam, o, d, pairs, have=None, film=None, model=1):
-    """(n, p, 8) float32 records of ghost_record, the call's columns: pairs (p, 2) of (a, b) or (p,) packed, have (n,) bool"""
-    fp = ctypes.POINTER(ctypes.c_float)
-    keep = _tables_args(L, disp, film) + [np.ascontiguousarray(v, F32) for v in (lam, o, d)]
-    n = len(keep[3])
-    pairs = np.asarray(pairs)
-    packed = np.ascontiguousarray(pairs if pairs.ndim == 1 else pairs[:, 0].astype(np.uint32) | (pairs[:, 1].astype(np.uint32) << 8), np.uint32)
-    hv = np.ones(n, np.uint8) if have is None else np.ascontiguousarray(have, np.uint8)
-    out = np.full((n, len(packed), 8), np.nan, F32)
-    drv.zgh_records(int(model), L["count"], keep[0].ctypes.data_as(fp), int(L["stop"]), ctypes.c_float(float(L["user"])), keep[1].ctypes.data_as(fp),
-                    len(packed), packed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, keep[2].ctypes.data_as(fp), keep[3].ctypes.data_as(fp),
-                    keep[4].ctypes.data_as(fp), hv.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.ctypes.data_as(fp))
-    return out
-
-
-def split(rec):
-    """(origin, dir, weight, flags, reason, interface, leg) of records (..., 8)"""
-    flags = _bits(rec[..., 7])
-    traced = (flags & 1) != 0
-    reason = np.where(traced, 0, (flags >> 8) & 0xF).astype(np.int64)
-    return rec[..., 0:3], rec[..., 3:6], rec[..., 6], flags, reason, ((flags >> 16) & 0x3F).astype(np.int64), ((flags >> 24) & 3).astype(np.int64)
+def driver():
+    return host_drivers.ghost()
 
 
 _LENS = {}
@@ -297,8 +159,8 @@ def _plain_weight_error(cfg, driver, oracle_lib, tdriver):
 
 
 @pytest.fixture(scope="module")
-def tdriver(tmp_path_factory):
-    return build_transmittance_driver(tmp_path_factory.mktemp("ghost_transdriver"))
+def tdriver():
+    return host_drivers.transmittance()
 
 
 @pytest.mark.parametrize("cfg", CFGS)
@@ -563,12 +425,7 @@ def test_traced_records(cfg, driver, oracle_lib):
 def test_ghost_kernels_budget():
     """0 scratch, 0 VGPR spills and at most 128 VGPRs for the ghost kernels of the built library (its code object's metadata); the kernel
     arguments fit their 4 KB"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "ghost" in k}
+    res = {k: v for k, v in kernel_resources().items() if "ghost" in k}
     assert len(res) == 2, sorted(res)
     for k, v in res.items():
         assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)

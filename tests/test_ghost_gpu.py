@@ -17,28 +17,23 @@ from zoic_amd.workloads import ray_rng_states
 import differentials_ref as dref
 import ghost_ref as gref
 import hero_cases as hr
-from test_differentials_gpu import _oracle, _params, _samples
-from test_ghost_cpu import build_driver, run_records
-from test_spectral_gpu import BAD, WAVES, _camera
-from test_transmittance_cpu import films_where_media_differ
-from test_transmittance_gpu import CAMERAS, _reference
+import host_drivers
+from device_cases import BIG, bits_f32 as _bits, camera as _camera, oracle as _oracle, params as _params, samples as _samples
+from hero_cases import LOSS_CAMERAS as CAMERAS, loss_reference as _reference
+from host_drivers import run_ghost_records as run_records
+from spectral_ref import BAD, LAMBDA_D32, WAVES
+from transmittance_ref import films_where_media_differ
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-LAMBDA_D32 = F32(587.5618)
 N = 4096
-BIG = 2048 * 256 + 65
 SIZES = [1, 63, 65, N]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("ghostdriver_gpu"))
+def driver():
+    return host_drivers.ghost()
 
 
 _TABLES = {}

@@ -16,8 +16,8 @@ from zoic_amd.workloads import ray_rng_states
 import backward_spectral_ref as bs
 from fuzz_cameras import _oracle_spectral, same_bits
 from hero_ref import hero_reference, same_words, words_of as _words
-from spectral_ref import LAMBDA_D
-from test_spectral_gpu import BAD, WAVES, _bits, _camera, _delta, _params, _samples
+from device_cases import bits_f32 as _bits, camera as _camera, delta as _delta, params as _params, samples as _samples
+from spectral_ref import BAD, LAMBDA_D, WAVES
 
 pytestmark = pytest.mark.gpu
 

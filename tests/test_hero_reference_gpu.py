@@ -15,8 +15,7 @@ from zoic_amd import PRECISION_FAST, PRECISION_STRICT
 from zoic_amd.workloads import camera_params
 
 import hero_cases as hr
-from fuzz_cameras import HOSTILE_SAMPLES, LAMBDA_EDGES, LAMBDA_HOSTILE
-from test_spectral_fuzz_gpu import DIR_RMSE_TOL, FLIP_TOL, WAVES
+from fuzz_cameras import DIR_RMSE_TOL, FLIP_TOL, HOSTILE_SAMPLES, LAMBDA_EDGES, LAMBDA_HOSTILE, WAVES
 
 pytestmark = pytest.mark.gpu
 

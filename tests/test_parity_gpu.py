@@ -13,6 +13,7 @@ from zoic_amd import PRECISION_FAST, PRECISION_STRICT, RAYTRACED, THINLENS, Zoic
 from zoic_amd.workloads import CONFIGS, camera_params, hexagon_bokeh, ray_count, ray_rng_states, synthetic_samples
 
 from fuzz_cameras import CUSTOM_LENS_5, CUSTOM_LENS_14, HOSTILE_SAMPLES, REAR_ELEMENT_CASES, REAR_ELEMENT_LENS, perturbed_prescription
+from device_cases import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +23,6 @@ DIR_RMSE_TOL = 1e-5        # BASELINE.json north_star: "ray-direction RMSE <1e-5
 # of the same rays (DESIGN.md "decision-safe fast mode").  A constant, not a knob.
 FLIP_TOL = 5e-5
 UNCHECKED_FLIP_TOL = 2e-3   # ZOIC_PRECISION_FAST_UNCHECKED (round 1's fast mode, kept for A/B): flips where the reference's own rounding decides
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def make_pair(oracle_lib, cfg, **override):

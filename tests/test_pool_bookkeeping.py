@@ -10,15 +10,13 @@ import pytest
 from zoic_amd import PRECISION_FAST, PRECISION_FAST_UNCHECKED, PRECISION_STRICT, ZoicCamera
 from zoic_amd.workloads import CONFIGS, camera_params, hexagon_bokeh, ray_rng_states, synthetic_samples
 
+from device_cases import bits
+
 N_SLAB = 4096 + 63          # 64 whole batches and a partial one
 N_SPLIT = 8192 + 65
 # The retry-heavy slab: C3's camera, the first rows of a 3840 x 2880 lattice.  The 16:9 frame's own corner stops at 46 % retried rays; these
 # rows lie further out on the sensor (54 % retried, 28 % out of tries: test_corner_slab_is_retry_heavy holds the oracle to that).
 CORNER_LATTICE = (3840, 2880, 16)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def make_oracle(oracle_lib, cfg):

@@ -5,9 +5,6 @@ header documents them.  zoic_camera_reverse_ray stays the reference's `return fa
 import ctypes
 import os
 import re
-import shutil
-import subprocess
-import sys
 import time
 
 import numpy as np
@@ -17,16 +14,17 @@ from zoic_amd import _capi
 from zoic_amd.camera import ZoicCamera, ZoicError, lens_path
 from zoic_amd.workloads import camera_params
 
-from reverse_ref import Lens, kolb_point_set, thin_point_set
+import host_drivers
+from host_drivers import drive_reverse as _drive
+from library_facts import header_text, kernel_resources
+from reverse_ref import BEHIND, MODEL_NONE, NON_FINITE, OUTSIDE, Lens, kolb_point_set, thin_point_set
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
 NEW = ("zoic_project_points_device", "zoic_project_point", "zoic_camera_set_reverse_projection")
 LENSES = sorted(f for f in os.listdir(os.path.join(ROOT, "zoic_amd", "lenses")) if f.endswith(".dat"))
 # the prescriptions a camera can load: zoic rejects a lens without an aperture row (radius 0, zoic.cpp:922)
 LOADABLE = [f for f in LENSES if any(l.split() and float(l.split()[0]) == 0.0 for l in open(os.path.join(ROOT, "zoic_amd", "lenses", f))
                                      if not l.lstrip().startswith("#"))]
-BEHIND, NO_ROOT, NON_FINITE, MODEL_NONE, OUTSIDE = 1, 2, 3, 4, 5
 
 
 def _camera(lens=None, **over):
@@ -40,7 +38,7 @@ def _camera(lens=None, **over):
 
 
 def test_abi_declares_and_exports_reverse_calls():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     lib = ctypes.CDLL(_capi.LIB_PATH)
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -50,12 +48,7 @@ def test_abi_declares_and_exports_reverse_calls():
 
 
 def test_reverse_kernel_budget():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "project_points_kernel" in k}
+    res = {k: v for k, v in kernel_resources().items() if "project_points_kernel" in k}
     assert res, "project_points_kernel not in the library"
     for k, v in res.items():
         assert v["scratch"] == 0, (k, v)
@@ -63,53 +56,9 @@ def test_reverse_kernel_budget():
         assert v["lds"] == 0, (k, v)
 
 
-DRIVER = r"""
-#include "reverse.hpp"
-extern "C" int zr_project(int model, float tanFov, int count, const float *radius, const float *thickness, const float *ior, const float *aperture,
-                          int apertureElement, float userApertureRadius, float originShift, float sensorWidth, int useLUT, int lutSize, int domain,
-                          long n, const float *pts, float *screen, unsigned *flags)
-{
-    zoic::ReverseTable T;
-    zoic::fill_reverse_table(T, model, tanFov, count, radius, thickness, ior, aperture, apertureElement, userApertureRadius, originShift,
-                             sensorWidth, useLUT != 0, lutSize, domain != 0);
-    for (long i = 0; i < n; ++i) flags[i] = zoic::project_point(T, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], screen[2 * i], screen[2 * i + 1]);
-    return 0;
-}
-"""
-
-
-def _clangxx():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    pytest.fail("no clang++ to build the host driver of csrc/reverse.hpp")
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    d = tmp_path_factory.mktemp("revdriver")
-    src, so = d / "driver.cpp", d / "driver.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
-                           "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(so)])
-    return ctypes.CDLL(str(so))
-
-
-def _drive(driver, cam, p, pts):
-    """the host build on points (m,3): (screen (m,2), flags (m,))"""
-    info = cam.info()
-    n = info["lensCount"]
-    el = [np.ascontiguousarray(info["elements"][:, k], dtype=np.float32) for k in range(4)]
-    pts = np.ascontiguousarray(pts, dtype=np.float32)
-    scr = np.zeros((len(pts), 2), np.float32)
-    fl = np.zeros(len(pts), np.uint32)
-    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    model = p["lensModel"]
-    domain = not info["fastRunsStrict"]
-    driver.zr_project(model, ctypes.c_float(info["tan_fov"]), n, P(el[0]), P(el[1]), P(el[2]), P(el[3]), info["apertureElement"],
-                      ctypes.c_float(info["userApertureRadius"]), ctypes.c_float(info["originShift"]), ctypes.c_float(p["sensorWidth"]),
-                      int(bool(p["kolbSamplingLUT"]) and len(info["lutKeys"]) > 0), len(info["lutKeys"]), int(domain), ctypes.c_long(len(pts)), P(pts), P(scr), P(fl))
-    return scr, fl
+def driver():
+    return host_drivers.reverse()
 
 
 CASES = [(lens, fd) for lens in LOADABLE for fd in (100.0, 30.0)] + [(None, 100.0), (None, 30.0)]

@@ -1,7 +1,7 @@
 """Fuzz of the reverse projection (csrc/reverse.hpp) on cameras nobody drew: machine-made prescriptions (test_parity_gpu's perturbed
 lenses: 5 ... 14 interfaces) behind random focal length, f-stop, sensor, focus distance and LUT switch.
 
-  * without a GPU: the host build (the clang++ driver of test_reverse_cpu) recovers the screen samples of kolb_point_set's points
+  * without a GPU: the host build (host_drivers.reverse) recovers the screen samples of kolb_point_set's points
     within test_host_build_recovers_chief_ray_samples' bounds and equals the library's zoic_project_point; a camera outside the
     geometric domain flags every point kRevOutsideDomain; a lens with no unclipped chief ray gives an empty point set (counted);
   * on the GPU: zoic_project_points_device equals zoic_project_point bit for bit, flags included, on the accuracy set, wild points and
@@ -15,8 +15,14 @@ import pytest
 from zoic_amd import RAYTRACED, ZoicCamera
 
 from fuzz_cameras import EXAMPLE_CAMERA, EXAMPLE_LENSES, examples, lens_args, lens_name, lens_strategy, perturbed_prescription, rows_of
-from reverse_ref import kolb_point_set
-from test_reverse_cpu import OUTSIDE, _drive, driver  # noqa: F401  (driver: the module-scoped fixture of the host build)
+import host_drivers
+from host_drivers import drive_reverse as _drive
+from reverse_ref import OUTSIDE, kolb_point_set
+
+
+@pytest.fixture(scope="module")
+def driver():
+    return host_drivers.reverse()
 
 
 EXAMPLE = tuple(EXAMPLE_CAMERA[k] for k in ("focalLength", "fStop", "sensorWidth", "focalDistance", "kolbSamplingLUT"))

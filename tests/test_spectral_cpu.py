@@ -5,9 +5,6 @@ scratch."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,10 +13,11 @@ from zoic_amd import _capi
 from zoic_amd.camera import ZoicCamera, ZoicError, lens_path
 from zoic_amd.workloads import camera_params
 
+import host_drivers
+from library_facts import header_text, kernel_resources
 from spectral_ref import LAMBDA_C, LAMBDA_D, LAMBDA_F, cauchy_b, interface_terms, spectral_iors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
 NEW = ("zoic_create_rays_spectral_device", "zoic_camera_get_dispersion", "zoic_camera_set_abbe_numbers")
 LENSES = sorted(f for f in os.listdir(os.path.join(ROOT, "zoic_amd", "lenses")) if f.endswith(".dat"))
 # the prescriptions a camera can load: zoic rejects a lens without an aperture row (radius 0, zoic.cpp:922)
@@ -28,7 +26,7 @@ LOADABLE = [f for f in LENSES if any(l.split() and float(l.split()[0]) == 0.0 fo
 
 
 def test_abi_declares_and_exports_spectral_calls():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     lib = ctypes.CDLL(_capi.LIB_PATH)
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -135,45 +133,9 @@ def test_abbe_override_changes_no_existing_table():
     cam.close()
 
 
-DRIVER = r"""
-#include "spectral.hpp"
-extern "C" int zs_terms(int count, const float *iorD, const float *b, int n, const float *lambda, float *ior1, float *ior2, float *eta,
-                        int *tir, int *valid)
-{
-    zoic::SpectralTable W{};
-    W.count = count;
-    for (int i = 0; i < count; ++i) { W.iorD[i] = iorD[i]; W.cauchyB[i] = b[i]; }
-    for (int r = 0; r < n; ++r) {
-        valid[r] = zoic::spectral_valid(lambda[r]) ? 1 : 0;
-        const float dl = zoic::spectral_dl(lambda[r]);
-        for (int i = 0; i < count; ++i) {
-            float a, c;
-            zoic::spectral_iors(&W, count, i, dl, a, c);
-            ior1[r * count + i] = a; ior2[r * count + i] = c;
-            eta[r * count + i] = zoic::spectral_eta(a, c);
-            tir[r * count + i] = zoic::spectral_tir_possible(a, c) ? 1 : 0;
-        }
-    }
-    return 0;
-}
-"""
-
-
-def _clangxx():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    pytest.fail("no clang++ to build the host driver of csrc/spectral.hpp")
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    d = tmp_path_factory.mktemp("specdriver")
-    src, so = d / "driver.cpp", d / "driver.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
-                           "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(so)])
-    return ctypes.CDLL(str(so))
+def driver():
+    return host_drivers.spectral()
 
 
 @pytest.mark.parametrize("lens,override", [("tessar_f2.8.dat", None), ("petzval_f1.25.dat", None), ("double_gauss_f2.0.dat", 50.0)])
@@ -213,12 +175,7 @@ def test_host_arithmetic_matches_numpy(driver, lens, override):
 
 
 def test_spectral_kernels_budget():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "spectral" in k or "hero" in k}
+    res = {k: v for k, v in kernel_resources().items() if "spectral" in k or "hero" in k}
     # one ray-kernel body, <FAST, HERO>: no instantiation may take more VGPRs than the separate spectral and hero kernels took before
     # they were merged
     caps = {"kolb_spectral_kernel<false, false>": 136, "kolb_spectral_kernel<true, false>": 138,

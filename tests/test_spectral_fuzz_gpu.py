@@ -14,18 +14,14 @@ import pytest
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, RAYTRACED, ZoicCamera
 from zoic_amd.workloads import ray_rng_states
 
-from fuzz_cameras import (EXAMPLE_CAMERA, EXAMPLE_LENSES, HOSTILE_SAMPLES, LAMBDA_EDGES, LAMBDA_HOSTILE, _oracle_spectral, bands, camera_params, camera_strategy, examples,
+from device_cases import delta as _delta
+from fuzz_cameras import (DIR_RMSE_TOL, EXAMPLE_CAMERA, EXAMPLE_LENSES, FLIP_TOL, HOSTILE_SAMPLES, LAMBDA_EDGES, LAMBDA_HOSTILE, WAVES, _oracle_spectral, bands, camera_params, camera_strategy, examples,
                           lens_args, lens_name, lens_strategy, perturbed_prescription, same_bits, update_both)
-from spectral_ref import LAMBDA_D
 
 pytestmark = pytest.mark.gpu
 
-FLIP_TOL = 5e-5          # test_parity_gpu.FLIP_TOL: 8192 rays, 20 x FLIP_TOL as in test_perturbed_prescription_fuzz
-DIR_RMSE_TOL = 1e-5      # north_star
 LIVE_AT_ENDS = 100
 BAND_NAMES = ["360-420", "420-500", "500-600", "600-700", "700-830"]
-# interleaved ray by ray in the STRICT parity check: both ends of the range, their in-range neighbours, the F, d and C lines
-WAVES = np.array([360.0, LAMBDA_EDGES[1], 405.0, 486.1327, LAMBDA_D, 656.2725, 760.0, LAMBDA_EDGES[3], 830.0], np.float32)
 
 
 def _samples(rs, n, aspect=1.5):
@@ -40,13 +36,6 @@ def _camera(ml, img, precision=PRECISION_STRICT):
         cam.set_bokeh_image(img)
     cam.set_precision(precision)
     return cam
-
-
-def _delta(cam, fn):
-    before = cam.counters()
-    r = fn()
-    after = cam.counters()
-    return r, {k: after[k] - before[k] for k in after}
 
 
 def _new_tally():

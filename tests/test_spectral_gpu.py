@@ -5,49 +5,13 @@ import numpy as np
 import pytest
 
 from zoic_amd import PRECISION_FAST, PRECISION_STRICT, ZoicCamera
-from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states
+from zoic_amd.workloads import ray_rng_states
 
 from fuzz_cameras import _oracle_spectral
-from spectral_ref import LAMBDA_D
+from device_cases import bits_f32 as _bits, camera as _camera, delta as _delta, params as _params, samples as _samples
+from spectral_ref import BAD, LAMBDA_D, SINGLET, WAVES
 
 pytestmark = pytest.mark.gpu
-
-WAVES = np.array([360.0, 420.0, 486.1327, 530.0, LAMBDA_D, 610.0, 656.2725, 830.0], np.float32)
-
-
-def _params(cfg, **over):
-    p = camera_params(cfg)
-    p.update(over)
-    return p
-
-
-def _camera(p, precision=PRECISION_STRICT, abbe=None):
-    cam = ZoicCamera(device=0)
-    if p.get("useImage"):
-        cam.set_bokeh_image(hexagon_bokeh())
-    cam.set_precision(precision)
-    if abbe is not None:
-        cam.set_abbe_numbers(abbe)
-    cam.update(**p)
-    return cam
-
-
-def _samples(n, aspect=16 / 9, seed=5):
-    rs = np.random.RandomState(seed)
-    s = np.stack([rs.uniform(-1, 1, n), rs.uniform(-1, 1, n) / aspect, rs.uniform(0, 1, n), rs.uniform(0, 1, n)], 1)
-    return np.ascontiguousarray(s, np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _delta(cam, fn):
-    before = cam.counters()
-    r = fn()
-    after = cam.counters()
-    return r, {k: after[k] - before[k] for k in after}
-
 
 def _records_equal(a, b):
     assert np.array_equal(a["flags"], b["flags"])
@@ -152,13 +116,6 @@ def test_fast_runs_strict_camera_gives_strict_bits():
     strict.close(); fast.close()
 
 
-SINGLET = """# singlet, V = 30
-50.0\t6.0\t1.5168\t30.0\t20.0
--50.0\t2.0\t0.0\t0.0\t20.0
-0.0\t45.0\t0.0\t0.0\t18.0
-"""
-
-
 def test_blue_focuses_closer_than_red():
     """physics without the oracle: an on-axis sensor point through a positive singlet; the rays' crossing of the axis in object space"""
     cam = ZoicCamera(device=0)
@@ -179,9 +136,6 @@ def test_blue_focuses_closer_than_red():
         cross[w] = float(np.median(t))
     assert cross[450.0] < cross[LAMBDA_D] < cross[650.0], cross
     cam.close()
-
-
-BAD = np.array([np.nan, np.inf, -np.inf, 0.0, -500.0, 359.9, 830.1], np.float32)
 
 
 @pytest.mark.parametrize("cfg", ["C1", "C2"])

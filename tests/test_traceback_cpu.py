@@ -22,11 +22,7 @@ to 5 x max E_ref for the round trip.  Measured for the library: |lib - f64| / E_
 trip 1.18 ... 1.76 x max E_ref."""
 import ctypes
 import functools
-import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -35,11 +31,12 @@ from zoic_amd import _capi
 from zoic_amd.camera import ZoicCamera, ZoicError
 from zoic_amd.workloads import camera_params
 
+import host_drivers
 import traceback_cases as tc
+from host_drivers import drive_traceback as _drive
+from library_facts import header_text, kernel_resources
 from traceback_ref import AWAY, CLIPPED, MISS, MODEL, NON_FINITE, OUTSIDE_DOMAIN, TIR, TraceBack
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
 NEW = ("zoic_trace_back_rays_device", "zoic_trace_back_ray")
 EDGE_CAP = 0.02
 
@@ -73,7 +70,7 @@ def round_trip(oracle_lib, name):
 
 
 def test_abi_declares_and_exports_trace_back_calls():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     lib = ctypes.CDLL(_capi.LIB_PATH)
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -83,12 +80,7 @@ def test_abi_declares_and_exports_trace_back_calls():
 
 
 def test_trace_back_kernel_budget():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "trace_back_kernel" in k}
+    res = {k: v for k, v in kernel_resources().items() if "trace_back_kernel" in k}
     assert res, "trace_back_kernel not in the library"
     for k, v in res.items():
         print(k, v)
@@ -279,56 +271,9 @@ def test_scale_and_placement_invariance(oracle_lib, name):
             assert np.abs(ps.astype(np.float64) - base_ps).max() <= 4.0 * R["e_max"], (move, scale, np.abs(ps - base_ps).max())
 
 
-DRIVER = r"""
-#include "traceback.hpp"
-extern "C" int zt_trace(int model, float tanFov, int count, const float *radius, const float *thickness, const float *ior, const float *aperture,
-                        int apertureElement, float userApertureRadius, float originShift, float sensorWidth, int useLUT, int lutSize, int domain,
-                        float apertureRadius, float focalDistance, int useDof, float ovDistance, float ovRadius,
-                        long n, const float *o, const float *d, float *screen, unsigned *flags)
-{
-    zoic::TraceBackTable T;
-    zoic::fill_traceback_table(T, model, tanFov, count, radius, thickness, ior, aperture, apertureElement, userApertureRadius, originShift,
-                               sensorWidth, useLUT != 0, lutSize, domain != 0, apertureRadius, focalDistance, useDof != 0, ovDistance, ovRadius);
-    for (long i = 0; i < n; ++i)
-        flags[i] = zoic::trace_back_ray(T, o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2], screen[2 * i], screen[2 * i + 1]);
-    return 0;
-}
-"""
-
-
-def _clangxx():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    pytest.fail("no clang++ to build the host driver of csrc/traceback.hpp")
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    d = tmp_path_factory.mktemp("tbdriver")
-    src, so = d / "driver.cpp", d / "driver.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
-                           "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(so)])
-    return ctypes.CDLL(str(so))
-
-
-def _drive(driver, cam, p, o, d):
-    info = cam.info()
-    n = info["lensCount"]
-    el = [np.ascontiguousarray(info["elements"][:, k], dtype=np.float32) for k in range(4)]
-    o = np.ascontiguousarray(o, np.float32)
-    d = np.ascontiguousarray(d, np.float32)
-    scr = np.zeros((len(o), 2), np.float32)
-    fl = np.zeros(len(o), np.uint32)
-    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    F = ctypes.c_float
-    driver.zt_trace(int(p["lensModel"]), F(info["tan_fov"]), n, P(el[0]), P(el[1]), P(el[2]), P(el[3]), info["apertureElement"],
-                    F(info["userApertureRadius"]), F(info["originShift"]), F(p["sensorWidth"]),
-                    int(bool(p["kolbSamplingLUT"]) and len(info["lutKeys"]) > 0), len(info["lutKeys"]), int(not info["fastRunsStrict"]),
-                    F(info["apertureRadius"]), F(p["focalDistance"]), int(bool(p["useDof"])), F(p.get("opticalVignettingDistance", 0.0)),
-                    F(p.get("opticalVignettingRadius", 1.0)), ctypes.c_long(len(o)), P(o), P(d), P(scr), P(fl))
-    return scr, fl
+def driver():
+    return host_drivers.traceback()
 
 
 @pytest.mark.parametrize("name", ["C3", "C4", "C1-vignetting"])

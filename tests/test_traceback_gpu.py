@@ -11,6 +11,7 @@ from zoic_amd import PRECISION_FAST, PRECISION_STRICT, ZoicCamera, _capi
 from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states, synthetic_samples
 
 import traceback_cases as tc
+from device_cases import records as _records
 from traceback_ref import TraceBack
 
 SLAB = 2048 * 256   # one grid of the kernel (traceback.hip): larger batches are walked slab by slab
@@ -25,13 +26,6 @@ def _camera(cfg, precision=PRECISION_STRICT, **over):
     cam.set_precision(precision)
     cam.update(**p)
     return cam, p
-
-
-def _records(o, d):
-    r = np.zeros((len(o), 8), np.float32)
-    r[:, 0:3], r[:, 3:6] = o, d
-    r[:, 6] = 1.0
-    return r
 
 
 @pytest.mark.gpu

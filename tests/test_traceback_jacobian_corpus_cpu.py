@@ -3,7 +3,7 @@ index 0, near-hemispherical rear elements, a V column, a camera outside the geom
 the host build of csrc/traceback_jacobian.hpp (zoic_trace_back_ray_jacobian and its spectral form on tables-only cameras) against f64
 central differences (traceback_jacobian_ref.py).
 
-Every lens.  On the corpus ray set of test_backward_corpus_gpu.py (a stride of the live forward records, the rejection families,
+Every lens.  On the corpus ray set machine_lens_corpus.ray_set (a stride of the live forward records, the rejection families,
 random lines, the non-finite rays) and 1 024 far rays (jr.far_rays: live records moved 30 ... 1e4 cm out along the ray, every other
 one with dir scaled by 1e3 or 1e-3), about 7 000 rays a lens: Ps and flags are zoic_trace_back_ray's bits, J is twelve +0.0 where
 bit 0 is clear, and J is finite and nonzero on every traced ray the f64 trace puts off TraceBack.edge; the same with
@@ -133,10 +133,9 @@ from zoic_amd import solid_angle_measure
 
 import backward_spectral_ref as bs
 import machine_lens_corpus as mc
-import test_backward_corpus_gpu as corpus_gpu
-import test_traceback_jacobian_cpu as tj
 import traceback_cases as tc
 import traceback_jacobian_ref as jr
+from device_cases import bits as _bits
 from traceback_ref import OUTSIDE_DOMAIN
 
 F32 = np.float32
@@ -153,10 +152,6 @@ NEAR_SOUND = {name: 1e-7 for name in mc.ACCURACY}
 NEAR_SOUND["fisheye-5"] = 2 * 1.9e-7
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 class _Lens:
     """one corpus lens: its tables-only camera, the f64 trace and the live oracle records of the frame (dir normalised in f64)"""
 
@@ -169,7 +164,7 @@ class _Lens:
         _, o, d, w = mc.oracle_records(oracle_lib, name)
         self.o, self.d = np.ascontiguousarray(o[w > 0], F32), jr.unit_f32(d[w > 0])
         self.plane = jr.front_plane(self.T, self.s)
-        self.rays = corpus_gpu._ray_set(oracle_lib, self.cam, name)[0]
+        self.rays = mc.ray_set(oracle_lib, self.cam, name)[0]
 
 
 _LENSES, _ACC = {}, {}
@@ -182,7 +177,7 @@ def _lens(oracle_lib, name):
 
 
 def bit_rays(L):
-    """the corpus ray set of test_backward_corpus_gpu and the far set: (origin, dir)"""
+    """the corpus ray set (machine_lens_corpus.ray_set) and the far set: (origin, dir)"""
     fo, fd = jr.far_rays(L.o, L.d)
     return (np.ascontiguousarray(np.concatenate([L.rays[:, 0:3], fo]), F32), np.ascontiguousarray(np.concatenate([L.rays[:, 3:6], fd]), F32))
 
@@ -196,7 +191,7 @@ def accuracy(oracle_lib, name, k=NEAR, spectral=False):
         return _ACC[key]
     L = _lens(oracle_lib, name)
     stride = 16
-    while stride > 1 and len(L.o[::stride]) * (1.0 - tj.LEFT_OUT_CAP) < tj.MIN_RAYS:
+    while stride > 1 and len(L.o[::stride]) * (1.0 - jr.LEFT_OUT_CAP) < jr.MIN_RAYS:
         stride //= 2
     d = L.d[::stride]
     out = L.s[0] if k == NEAR else k
@@ -242,7 +237,7 @@ def test_ps_flags_and_untraced_j_on_every_corpus_lens(oracle_lib, name):
     assert np.array_equal(_bits(ps), _bits(ps0)) and np.array_equal(fl, fl0)
     traced = (fl & 1) == 1
     assert not _bits(J[~traced]).any()
-    ps1, fl1, J1 = jr.host_jacobian(L.cam, O, D, tj.LAMBDA_D)
+    ps1, fl1, J1 = jr.host_jacobian(L.cam, O, D, jr.LAMBDA_D)
     assert np.array_equal(_bits(ps1), _bits(ps)) and np.array_equal(fl1, fl) and np.array_equal(_bits(J1), _bits(J))
     lam = bs.mixed_wavelengths(len(O))
     bad = ~bs.valid(lam)
@@ -275,7 +270,7 @@ def test_near_reference_is_sound(oracle_lib, name):
     """the reference at the steps 1e-6 s and 1e-5 s, on the kept rays one housing radius out"""
     for spectral in (False, True):
         A = accuracy(oracle_lib, name, NEAR, spectral)
-        e = _soundness(A, tj._best(A)["kept"])
+        e = _soundness(A, jr.best(A)["kept"])
         print("%s: Jref(1e-5) against Jref(1e-6): max %.3g (bound %.3g)" % (A["tag"], e, NEAR_SOUND[name]))
         assert e <= NEAR_SOUND[name], e
 
@@ -283,13 +278,13 @@ def test_near_reference_is_sound(oracle_lib, name):
 @pytest.mark.parametrize("name", mc.ACCURACY)
 def test_near_accuracy_against_the_finite_difference_yardstick(oracle_lib, name):
     A = accuracy(oracle_lib, name)
-    tj._check_accuracy(A, A["tag"])
+    jr.check_accuracy(A, A["tag"])
 
 
 @pytest.mark.parametrize("name", mc.ACCURACY)
 def test_near_spectral_accuracy_against_the_finite_difference_yardstick(oracle_lib, name):
     A = accuracy(oracle_lib, name, NEAR, True)
-    tj._check_accuracy(A, A["tag"])
+    jr.check_accuracy(A, A["tag"])
 
 
 @pytest.mark.parametrize("name", mc.ACCURACY)
@@ -297,7 +292,7 @@ def test_near_null_vectors(oracle_lib, name):
     """J_o . dir = 0 and J_d . dir = 0, to the p99 error of the accuracy test"""
     for spectral in (False, True):
         A = accuracy(oracle_lib, name, NEAR, spectral)
-        best = tj._best(A)
+        best = jr.best(A)
         no, nd = _null_vectors(A, best["kept"])
         print("%s: |J_o d| max %.3g, |J_d d| max %.3g, p99 error %.3g" % (A["tag"], no, nd, best["j_p99"]))
         assert no <= best["j_p99"] and nd <= best["j_p99"], (no, nd, best["j_p99"])
@@ -309,13 +304,13 @@ def test_far_accuracy_against_the_finite_difference_yardstick(oracle_lib, name, 
     """The start point k cm out, the reference through near_trace, every figure in the distance-scaled S.  The reference's two steps
     must agree to a tenth of J's median before J is held to the yardstick."""
     A = accuracy(oracle_lib, name, k)
-    best = tj._best(A)
+    best = jr.best(A)
     e = _soundness(A, best["kept"])
     no, nd = _null_vectors(A, best["kept"])
     print("%s: Jref(%g) against Jref(%g): max %.3g = %.3g of J's median; |J_o d| max %.3g, |J_d d| max %.3g" % (
         A["tag"], A["steps"][1], A["steps"][0], e, e / best["j_med"], no, nd))
     assert e <= 0.1 * min(best["j_med"], best["y_med"] / 4.0), (e, best["j_med"], best["y_med"])
-    tj._check_accuracy(A, A["tag"])
+    jr.check_accuracy(A, A["tag"])
 
 
 # ---- 3. the lenses held to the bitwise comparison: recorded, not bounded -----------------------------------------------------------
@@ -324,7 +319,7 @@ def test_bitwise_only_lenses_are_recorded(oracle_lib, name):
     """the corpus's policy for them: the same figures near and at 3 000 cm, printed; J finite on every candidate ray"""
     for k in (NEAR, BITWISE_FAR):
         A = accuracy(oracle_lib, name, k)
-        rows = [r for r in A["rows"] if r["kept"].sum() >= tj.MIN_RAYS // 2]
+        rows = [r for r in A["rows"] if r["kept"].sum() >= jr.MIN_RAYS // 2]
         assert rows, A["tag"]
         r = min(rows, key=lambda r: r["y_med"])
         print("%s: stride %d, %d rays kept at h = 2^%d (left out %.2f %%, by the f64 trace alone %.2f %%): J median %.3g p99 %.3g; yardstick "
@@ -342,7 +337,7 @@ def test_solid_angle_measure(oracle_lib, name):
     goes through zero and its relative error is conditioning."""
     for k in (NEAR,) + DISTANCES:
         A = accuracy(oracle_lib, name, k)
-        best = tj._best(A)
+        best = jr.best(A)
         kept = best["kept"]
         d = A["d"][kept].astype(np.float64)
         want = solid_angle_measure(A["Jref"][kept], d)

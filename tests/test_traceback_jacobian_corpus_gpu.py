@@ -2,7 +2,7 @@
 points, after test_backward_corpus_gpu.py:
 
   * zoic_trace_back_jacobian_device and zoic_trace_back_jacobian_spectral_device give the per-item host calls' bits -- Ps, flags and all
-    twelve words of J, no tolerance -- on every lens of the corpus: the corpus ray set of test_backward_corpus_gpu.py and 1 024 far rays
+    twelve words of J, no tolerance -- on every lens of the corpus: the corpus ray set machine_lens_corpus.ray_set and 1 024 far rays
     (live records moved 30 ... 1e4 cm out along the ray, half of them with dir scaled by 1e3 or 1e-3; traceback_jacobian_ref.far_rays),
     at most 8 192 rays a lens; the whole set, prefixes of 1, 63, 64 and 65 items and, for the lenses of the most and the fewest
     interfaces, one grid and one item (524 289, the set tiled); valid and rejected wavelengths interleaved inside one wave; Ps and flags
@@ -34,8 +34,9 @@ import backward_spectral_ref as bs
 import machine_lens_corpus as mc
 import traceback_cases as tc
 import traceback_jacobian_ref as jr
-from test_backward_corpus_gpu import GRID_PLUS_ONE, PREFIXES, _bits, _ray_set, _records
-from test_traceback_jacobian_gpu import H, N, SPP, W, _residual
+from device_cases import bits as _bits, records as _records
+from machine_lens_corpus import GRID_PLUS_ONE, PREFIXES, ray_set as _ray_set
+from traceback_jacobian_ref import H, N, SPP, W, residual as _residual
 from traceback_ref import OUTSIDE_DOMAIN
 
 F32 = np.float32

@@ -35,9 +35,7 @@ Jref at the steps 1e-5 s and 1e-6 s agrees to 9e-9 (C4) and 5e-10 or better else
 
 The requirement: J's median <= the yardstick's / 4, J's p99 <= the yardstick's."""
 import ctypes
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -49,15 +47,13 @@ from zoic_amd.workloads import camera_params
 import backward_spectral_ref as bs
 import traceback_cases as tc
 import traceback_jacobian_ref as jr
+from library_facts import header_text, kernel_resources
+from traceback_jacobian_ref import LAMBDA_D, LEFT_OUT_CAP, MIN_RAYS, best as _best, check_accuracy as _check_accuracy
 from traceback_ref import RAYTRACED, TraceBack
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("zoic_trace_back_jacobian_device", "zoic_trace_back_ray_jacobian", "zoic_trace_back_jacobian_spectral_device",
        "zoic_trace_back_ray_jacobian_spectral")
-LEFT_OUT_CAP = 0.03
-MIN_RAYS = 1024
 SPECTRAL = ("C2", "C3", "triplet")
-LAMBDA_D = np.float32(587.5618)
 # the edge rows of test_traceback_gpu.py (origin, dir)
 EDGE_ROWS = np.array([[0, 0, -1, 0, 0, -1], [0, 0, -1e30, 0, 0, -1e-30], [1e30, 0, -1, 0, 0, -1], [0, 0, -1, 1e30, 0, -1e-30],
                       [0, 0, 0, 0, 0, -1], [-0.0, -0.0, -0.0, -0.0, -0.0, -1], [0, 0, -1, 1, 0, -1e-38], [1e-30, 1e-30, -1e-30, 1e-30, 0, -1e-30]],
@@ -98,7 +94,7 @@ def ray_sets(info, p, o, d, w):
 
 
 def test_abi_declares_and_exports_the_jacobian_calls():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     lib = ctypes.CDLL(_capi.LIB_PATH)
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -108,12 +104,7 @@ def test_abi_declares_and_exports_the_jacobian_calls():
 
 
 def test_jacobian_kernel_budget():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "trace_back_jacobian" in k}
+    res = {k: v for k, v in kernel_resources().items() if "trace_back_jacobian" in k}
     assert any("trace_back_jacobian_kernel" in k for k in res) and any("trace_back_jacobian_spectral_kernel" in k for k in res), list(res)
     for k, v in res.items():
         print(k, v)
@@ -206,28 +197,6 @@ def accuracy(oracle_lib, name, spectral=False):
     A = jr.measure(cam, trace, T.edge, o, d, lam, s, tag=name + (" spectral" if spectral else ""))
     _ACC[key] = dict(A, p=p, T=T, stride=stride)
     return _ACC[key]
-
-
-def _best(A):
-    """the yardstick's step: the lowest median among the steps that leave out at most LEFT_OUT_CAP"""
-    eligible = [r for r in A["rows"] if r["left_out"] <= LEFT_OUT_CAP]
-    assert eligible, [(r["h"], r["left_out"]) for r in A["rows"]]
-    return min(eligible, key=lambda r: r["y_med"])
-
-
-def _check_accuracy(A, tag):
-    best = _best(A)
-    overall = min((r for r in A["rows"] if r["kept"].sum() >= MIN_RAYS), key=lambda r: r["y_med"])
-    print("%s: stride %d, %d rays kept at h = 2^%d (left out %.2f %%): J median %.3g p99 %.3g; yardstick median %.3g p99 %.3g; "
-          "best yardstick median of any step %.3g (h = 2^%d, J there %.3g)"
-          % (tag, A["stride"], best["kept"].sum(), round(np.log2(best["h"])), 100 * best["left_out"], best["j_med"], best["j_p99"],
-             best["y_med"], best["y_p99"], overall["y_med"], round(np.log2(overall["h"])), overall["j_med"]))
-    assert best["kept"].sum() >= MIN_RAYS, best["kept"].sum()
-    assert best["left_out"] <= LEFT_OUT_CAP and best["left_out64"] <= LEFT_OUT_CAP
-    assert best["j_med"] <= best["y_med"] / 4.0, (best["j_med"], best["y_med"])
-    assert best["j_p99"] <= best["y_p99"], (best["j_p99"], best["y_p99"])
-    # and against the best the yardstick does at ANY of its steps, on that step's own rays
-    assert overall["j_med"] <= overall["y_med"] / 4.0 and overall["j_p99"] <= overall["y_p99"], overall
 
 
 @pytest.mark.parametrize("name", list(tc.CONFIGS))

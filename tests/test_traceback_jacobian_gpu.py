@@ -16,11 +16,11 @@ from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states, syn
 import backward_spectral_ref as bs
 import traceback_cases as tc
 import traceback_jacobian_ref as jr
+from device_cases import bits as _bits, records as _records
+from traceback_jacobian_ref import H, N, SPP, W, residual as _residual
 from traceback_ref import TraceBack
 
 SLAB = 2048 * 256   # one grid of the kernels (traceback.hip): larger batches are walked slab by slab
-W, H, SPP = 64, 36, 2
-N = W * H * SPP
 EDGE_ROWS = np.array([[0, 0, -1, 0, 0, -1], [0, 0, -1e30, 0, 0, -1e-30], [1e30, 0, -1, 0, 0, -1], [0, 0, -1, 1e30, 0, -1e-30],
                       [0, 0, 0, 0, 0, -1], [-0.0, -0.0, -0.0, -0.0, -0.0, -1], [0, 0, -1, 1, 0, -1e-38], [1e-30, 1e-30, -1e-30, 1e-30, 0, -1e-30]],
                      np.float32)
@@ -38,13 +38,6 @@ def _camera(cfg, precision=PRECISION_STRICT, **over):
     return cam, p
 
 
-def _records(o, d):
-    r = np.zeros((len(o), 8), np.float32)
-    r[:, 0:3], r[:, 3:6] = o, d
-    r[:, 6] = 1.0
-    return r
-
-
 def _ray_set(cam, p):
     """the frame's records (whatever their weight), the refusal families, the non-finite rays, random lines and the edge rows"""
     fwd = cam.create_rays(synthetic_samples(N, W, H, SPP), rng_states=ray_rng_states(N))
@@ -55,10 +48,6 @@ def _ray_set(cam, p):
         live = np.flatnonzero(fwd["weight"] > 0)[::16]
         sets += [_records(o, d) for o, d in tc.rejection_families(info, rec[live, 0:3], rec[live, 3:6]).values()]
     return np.ascontiguousarray(np.concatenate(sets), dtype=np.float32), int((fwd["weight"] > 0).sum())
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _check_against_host(cam, p, rays, lam, n_live, tiled):
@@ -146,11 +135,6 @@ def test_in_place_outputs_and_counters(gpu, oracle_lib):
     s3, f3, j3 = cam.trace_back_jacobian(np.ascontiguousarray(rec).view(_capi.RAY_DTYPE).reshape(-1))
     assert np.array_equal(s3, scr.cpu().numpy()) and np.array_equal(f3, fl.cpu().numpy()) and np.array_equal(_bits(j3), _bits(hj))
     cam.close()
-
-
-def _residual(J, T):
-    """|J T - I|_max per ray: J (m,2,6), T (m,6,2)"""
-    return np.abs(np.einsum("nij,njk->nik", J, T) - np.eye(2)[None]).max((1, 2))
 
 
 @pytest.mark.gpu

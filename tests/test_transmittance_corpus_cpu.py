@@ -5,7 +5,7 @@ trace_lens_spectral_strict for where a path passes at all.
 
 Starts: differentials_ref.kolb_start on the oracle's d-line records of the frame traceback_cases.frame_samples(), all of reference_rows
 of the live ones (at most 4096: the restatement is one vectorised pass, so it runs on every row), at the wavelengths of
-test_differentials_spectral_corpus_cpu.frame().  The records pass at the d-line; at its own wavelength a start may not.  Only starts
+differentials_spectral_corpus.frame().  The records pass at the d-line; at its own wavelength a start may not.  Only starts
 that pass in f64 are compared: the f64 path meets every sphere, is nowhere totally reflected (transmittance_ref) and stays within the
 housings (ghost_ref.ghost's plain path).  Their share is asserted on the reference alone, before the host build is read.  Beyond a
 relative margin of PASS_MARGIN on every decision of the f64 path the host build must pass the same starts; the few nearer ones that it
@@ -41,8 +41,9 @@ import ghost_ref as gref
 import lens_losses_corpus as lc
 import machine_lens_corpus as mc
 import transmittance_ref as tref
-from test_ghost_cpu import build_driver as build_ghost_driver
-from test_transmittance_cpu import _bits, build_driver, run_driver
+import host_drivers
+from device_cases import bits_f32 as _bits
+from host_drivers import run_transmittance as run_driver
 
 F32 = np.float32
 PASS_MARGIN = 5e-3       # test_ghost_cpu._plain's: the STRICT trace's rounding at the stop's sphere decides nothing beyond it
@@ -60,13 +61,13 @@ def _measured(name):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("transcorpus"))
+def driver():
+    return host_drivers.transmittance()
 
 
 @pytest.fixture(scope="module")
-def gdriver(tmp_path_factory):
-    return build_ghost_driver(tmp_path_factory.mktemp("transcorpus_strict"))
+def gdriver():
+    return host_drivers.ghost()
 
 
 def test_the_corpus_is_the_pinned_one():

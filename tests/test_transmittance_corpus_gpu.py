@@ -4,7 +4,7 @@ csrc/transmittance.hpp to the f64 restatement on the same lenses:
 
   A  the kernel gives the host build bit for bit, bare and with a film wherever the media differ, STRICT, on reference_rows of the
      live records of the frame: k = 1 on the spectral records, k = 4 on hero records whose hero wavelength is the frame's and whose
-     three companions rotate through test_spectral_gpu.WAVES (their start is the hero's accepted try);
+     three companions rotate through spectral_ref.WAVES (their start is the hero's accepted try);
   B  the identities of the call on the whole frame (41 472 rows), bit for bit: column 0 of the k = 4 call against the k = 1 call (the
      store through the LDS transpose against the direct store), the d-line form, two runs, prefixes, split launches, STRICT against
      FAST, and on the lenses of the most and the fewest interfaces and on plates-32 the frame tiled to 2048 x 256 + 65 rows at k = 1;
@@ -41,12 +41,14 @@ from zoic_amd.workloads import ray_rng_states
 import backward_spectral_ref as bs
 import lens_losses_corpus as lc
 import machine_lens_corpus as mc
-from test_backward_corpus_gpu import PREFIXES
-from test_differentials_spectral_corpus_cpu import frame
-from test_differentials_spectral_corpus_gpu import _wave_with
-from test_ghost_corpus_gpu import BIG, LAMBDA_D32, SPLIT, _camera, _inputs, _launch, _same, _starts, _take
-from test_spectral_gpu import BAD, WAVES
-from test_transmittance_cpu import build_driver, run_driver
+import host_drivers
+from device_cases import bits_f32 as _bits
+from differentials_spectral_corpus import frame, wave_with as _wave_with
+from host_drivers import run_transmittance as run_driver
+from lens_losses_corpus import (BIG, SPLIT, device_camera as _camera, device_inputs as _inputs, device_launch as _launch, device_starts as _starts,
+                                same_words as _same, take as _take)
+from machine_lens_corpus import PREFIXES
+from spectral_ref import BAD, LAMBDA_D32, WAVES
 
 pytestmark = pytest.mark.gpu
 
@@ -54,13 +56,9 @@ F32 = np.float32
 K = 4
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("transcorpus_gpu"))
+def driver():
+    return host_drivers.transmittance()
 
 
 def _hero_wavelengths(rows):

@@ -3,12 +3,11 @@ as the header says, the arithmetic of csrc/transmittance.hpp (compiled for the h
 (transmittance_ref.py) from the same starts, the film's cosine polynomial holds against f64, the physics is what a lens designer
 expects (the on-axis closed form, Brewster's angle, the ideal quarter-wave film), and the gfx950 kernels keep their budget.
 
-Rays: test_differentials_spectral_cpu._rays (~10 k passing rays per lens, C2 - C5) with _wavelengths; no ray is left out.  The measured
+Rays: differentials_spectral_ref.lens_rays (~10 k passing rays per lens, C2 - C5) with ray_wavelengths; no ray is left out.  The measured
 figures are in test_host_build_against_f64."""
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -16,18 +15,20 @@ import pytest
 from zoic_amd import _capi
 from zoic_amd.camera import LENS_DIR, ZoicCamera, ZoicError
 
+import host_drivers
 import transmittance_ref as tref
-from test_differentials_cpu import _clangxx
-from test_differentials_spectral_cpu import _rays, _wavelengths, tables
+from device_cases import bits_f32 as _bits
+from differentials_spectral_ref import lens_rays as _rays, ray_wavelengths as _wavelengths, tables
+from host_drivers import run_transmittance as run_driver
+from library_facts import header_text, kernel_resources
+from transmittance_ref import FILM_INDEX, FILM_LAMBDA0, LENSES, films_where_media_differ, housings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zoic_amd", "csrc")
 NAMES = ("zoic_ray_transmittance_device", "zoic_camera_set_coatings", "zoic_camera_get_coatings")
 F32 = np.float32
 LAMBDA_D32 = F32(587.5618)
 INVALID = _capi.STATUS_NAMES.index("ZOIC_ERR_INVALID_ARGUMENT")
 NO_DEVICE = _capi.STATUS_NAMES.index("ZOIC_ERR_NO_DEVICE")
-FILM_INDEX, FILM_LAMBDA0 = F32(1.38), F32(550.0)     # MgF2, a quarter wave thick in the green
 
 # Largest |host build - f64 restatement| of T over the eight runs of test_host_build_against_f64 (clang++ 22, x86-64) and the bound
 # asserted there and wherever "the bound" is said below: 4 x it, the margin for other compilers' host builds
@@ -40,7 +41,7 @@ COSPI_BOUND = 2e-7
 
 
 def test_abi_declares_and_exports_the_calls():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zoic_amd.h")).read(), flags=re.S)
+    text = header_text()
     raw = ctypes.CDLL(_capi.LIB_PATH)
     for name in NAMES:
         assert re.search(r"\b%s\s*\(" % name, text), name
@@ -50,93 +51,9 @@ def test_abi_declares_and_exports_the_calls():
     assert _capi.load().zoic_abi_version() == 5 and _capi.ABI_VERSION == 5
 
 
-# ---- the host driver ------------------------------------------------------------------------------------------------------------
-DRIVER = r"""
-#include "transmittance.hpp"
-// surf: count x (center, radius2, sign, housing2); disp: count x (iorD, cauchyB); film: count x (index, lambda0); lambda: one per ray
-extern "C" int ztr_trace(int count, const float *surf, const float *disp, const float *film, int n, const float *lambda, const float *o,
-                         const float *d, float *T)
-{
-    using namespace zoic;
-    Surface S[kMaxSurfaces] = {};
-    SpectralTable W = {};
-    FilmTable F = {};
-    W.count = F.count = count;
-    for (int i = 0; i < count; ++i) {
-        S[i].center = surf[4 * i]; S[i].radius2 = surf[4 * i + 1]; S[i].sign = surf[4 * i + 2]; S[i].housing2 = surf[4 * i + 3];
-        W.iorD[i] = disp[2 * i]; W.cauchyB[i] = disp[2 * i + 1];
-        F.index[i] = film[2 * i]; F.lambda0[i] = film[2 * i + 1];
-    }
-    const Surface *SP = S;
-    const SpectralTable *WP = &W;
-    const FilmTable *FP = &F;
-    for (int r = 0; r < n; ++r)
-        T[r] = path_transmittance(SP, WP, FP, count, lambda[r], V3{o[3 * r], o[3 * r + 1], o[3 * r + 2]}, V3{d[3 * r], d[3 * r + 1], d[3 * r + 2]});
-    return 0;
-}
-extern "C" void ztr_cospi(int n, const float *x, float *y) { for (int i = 0; i < n; ++i) y[i] = zoic::film_cospi(x[i]); }
-extern "C" float ztr_interface(float n1, float n2, float ci, float ct, float nc, float lambda0, float lambda)
-{
-    return zoic::interface_transmittance(n1, n2, ci, ct, nc, lambda0, lambda);
-}
-"""
-
-
-def build_driver(directory):
-    """the host build of csrc/transmittance.hpp (shared with tests/test_transmittance_gpu.py)"""
-    import subprocess
-    src, so = os.path.join(str(directory), "driver.cpp"), os.path.join(str(directory), "driver.so")
-    with open(src, "w") as f:
-        f.write(DRIVER)
-    subprocess.check_call([_clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
-                           "-I" + os.path.join(ROOT, "include"), src, "-o", so])
-    drv = ctypes.CDLL(so)
-    drv.ztr_interface.restype = ctypes.c_float
-    drv.ztr_interface.argtypes = [ctypes.c_float] * 7
-    return drv
-
-
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("transdriver"))
-
-
-def housings(info):
-    """Surface::housing2 of every interface (csrc/lens_system.cpp fill_surfaces): the largest f32 <= (aperture / 2)^2 in f64; the
-    stop's is the smaller of that and userApertureRadius^2 in f32"""
-    a = info["elements"][:int(info["lensCount"]), 3].astype(np.float64)
-    want = (a * 0.5) ** 2
-    h = want.astype(F32)
-    over = h.astype(np.float64) > want
-    h[over] = np.nextafter(h[over], F32(-np.inf))
-    stop = int(info["apertureElement"])
-    h[stop] = min(h[stop], F32(info["userApertureRadius"]) * F32(info["userApertureRadius"]))
-    return h
-
-
-def run_driver(drv, surf, disp, lam, o, d, film=None, housing2=None):
-    """(n,) float32 T of the host driver; surf = dref.surfaces(info); film = (index, lambda0) in trace order; housing2 None: no clip"""
-    n, count = len(o), len(surf)
-    h2 = np.full(count, np.inf, F32) if housing2 is None else np.asarray(housing2, F32)
-    s4 = np.stack([surf[:, 0], surf[:, 1], surf[:, 2], h2], 1)
-    fl = np.zeros((count, 2), F32) if film is None else np.stack([film[0], film[1]], 1)
-    keep = [np.ascontiguousarray(a, F32) for a in (s4, np.stack([disp["ior_d"], disp["cauchy_b"]], 1), fl, lam, o, d)]
-    fp = ctypes.POINTER(ctypes.c_float)
-    c = [a.ctypes.data_as(fp) for a in keep]
-    T = np.full(n, -1.0, F32)
-    assert drv.ztr_trace(count, c[0], c[1], c[2], n, c[3], c[4], c[5], T.ctypes.data_as(fp)) == 0
-    return T
-
-
-def films_where_media_differ(disp):
-    """(index, lambda0) in trace order: FILM_INDEX / FILM_LAMBDA0 on every interface whose two media differ at the d-line"""
-    n1 = disp["ior_d"]
-    differ = n1 != np.append(n1[1:], F32(1.0))
-    return np.where(differ, FILM_INDEX, F32(0)).astype(F32), np.where(differ, FILM_LAMBDA0, F32(0)).astype(F32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
+def driver():
+    return host_drivers.transmittance()
 
 
 # ---- the interface on a tables-only camera --------------------------------------------------------------------------------------
@@ -280,19 +197,6 @@ def test_film_cosine(driver):
 
 
 # ---- physics --------------------------------------------------------------------------------------------------------------------
-def _loads(lens):
-    try:
-        tables("C2", lensDataPath=os.path.join(LENS_DIR, lens))
-        return True
-    except ZoicError as e:      # two of the shipped files list no stop: ZOIC_ERR_NO_APERTURE, no camera to trace through
-        assert e.status_name == "ZOIC_ERR_NO_APERTURE", (lens, e)
-        return False
-
-
-LENSES = [f for f in sorted(os.listdir(LENS_DIR)) if f.endswith(".dat") and _loads(f)]
-assert len(LENSES) >= 6 and {"tessar_f2.8.dat", "double_gauss_f2.0.dat", "petzval_f1.25.dat"} <= set(LENSES)
-
-
 @pytest.mark.parametrize("lens", LENSES)
 def test_on_axis_ray_is_the_closed_form(lens, driver):
     """a ray along the axis of every shipped prescription, bare, at lambda_d: prod 1 - ((n1 - n2) / (n1 + n2))^2 on the camera's own
@@ -411,12 +315,7 @@ def test_d_line_is_any_wavelength_on_a_lens_without_v_numbers(driver, oracle_lib
 def test_transmittance_kernels_budget():
     """0 scratch, 0 VGPR spills and at most 128 VGPRs for the transmittance kernels of the built library (its code object's metadata);
     the kernel arguments fit their 4 KB"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import code_object_regs
-    finally:
-        sys.path.pop(0)
-    res = {k: v for k, v in code_object_regs.kernel_resources(_capi.LIB_PATH).items() if "transmittance" in k}
+    res = {k: v for k, v in kernel_resources().items() if "transmittance" in k}
     assert len(res) == 2, sorted(res)
     for k, v in res.items():
         assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)

@@ -17,32 +17,23 @@ from zoic_amd.workloads import ray_rng_states
 
 import differentials_ref as dref
 import hero_cases as hr
-from test_differentials_gpu import _oracle, _params, _samples
-from test_spectral_gpu import BAD, WAVES, _camera
-from test_transmittance_cpu import FILM_INDEX, FILM_LAMBDA0, build_driver, films_where_media_differ, housings, run_driver
+import host_drivers
+from device_cases import BIG, bits_f32 as _bits, camera as _camera, oracle as _oracle, params as _params, samples as _samples
+from hero_cases import LOSS_CAMERAS as CAMERAS, cycled as _cycled, loss_reference as _reference
+from host_drivers import run_transmittance as run_driver
+from spectral_ref import BAD, LAMBDA_D32, WAVES
+from transmittance_ref import FILM_INDEX, FILM_LAMBDA0, films_where_media_differ, housings
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-LAMBDA_D32 = F32(587.5618)
 N = 4096
-BIG = 2048 * 256 + 65
 SIZES = [1, 63, 65, N]
-CAMERAS = {"C2": "C2", "C3": "C3-bokeh-V50"}     # C3 ships no V-numbers: V = 50 on every glass, so that the wavelength matters
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("transdriver_gpu"))
-
-
-def _cycled(n, k):
-    """(n, k) wavelengths cycled from WAVES, every row starting one further on: rows and columns both differ"""
-    return WAVES[(np.arange(n)[:, None] * (k + 1) + np.arange(k)[None, :]) % len(WAVES)].astype(F32)
+def driver():
+    return host_drivers.transmittance()
 
 
 _TABLES = {}
@@ -63,23 +54,6 @@ def _coat(cam, name, coated):
         nc, l0 = _tables(name)[3]
         cam.set_coatings(nc[::-1], l0[::-1])      # file order
     return cam
-
-
-_REFERENCE = {}
-
-
-def _reference(oracle_lib, name, k, lam=None, key=None):
-    """samples, wavelengths, states and the hero reference (words, starts) of N rows: computed once, never written to"""
-    key = (name, k, key)
-    if key not in _REFERENCE:
-        sp = hr.spec(name)
-        s, _, st = hr.inputs(N, k, 11, name)
-        lam = _cycled(N, k) if lam is None else lam
-        words, _, det = hr.hero_reference(oracle_lib, sp.params, sp.dispersion(), s, lam, st, lens_text=sp.text, details=True)
-        for a in (s, lam, st, words, det["starts"]):
-            a.setflags(write=False)
-        _REFERENCE[key] = s, lam, st, words, det["starts"]
-    return _REFERENCE[key]
 
 
 def _expected(driver, name, coated, starts, here, weights):

@@ -106,20 +106,46 @@ def dyadic_lines(info, m, seed=5):
     return o, d
 
 
-def lib_trace(cam, o, d):
-    """zoic_trace_back_ray on every ray: (ps (m,2) float32, flags (m,) uint32)"""
+def lib_trace(cam, o, d, lam=None):
+    """zoic_trace_back_ray (lam None) or zoic_trace_back_ray_spectral on every ray: (ps (m,2) float32, flags (m,) uint32)"""
     lib, h = _capi.load(), cam._h
     ps = np.zeros((len(o), 2), np.float32)
     fl = np.zeros(len(o), np.uint32)
     o = np.ascontiguousarray(o, np.float32)
     d = np.ascontiguousarray(d, np.float32)
-    V = ctypes.POINTER(_capi.Vec3)
+    V, FP, UP = ctypes.POINTER(_capi.Vec3), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
     po, pd = o.ctypes.data, d.ctypes.data
     pp, pf = ps.ctypes.data, fl.ctypes.data
-    fn = lib.zoic_trace_back_ray
+    if lam is None:
+        fn = lib.zoic_trace_back_ray
+        for i in range(len(o)):
+            rc = fn(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pd + 12 * i, V), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
+            assert rc == 0, rc
+        return ps, fl
+    lam = np.broadcast_to(np.asarray(lam, np.float32), (len(o),))
+    fn = lib.zoic_trace_back_ray_spectral
     for i in range(len(o)):
-        rc = fn(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pd + 12 * i, V), ctypes.cast(pp + 8 * i, ctypes.POINTER(ctypes.c_float)),
-                ctypes.cast(pf + 4 * i, ctypes.POINTER(ctypes.c_uint32)))
+        rc = fn(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pd + 12 * i, V), float(lam[i]), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
+        assert rc == 0, rc
+    return ps, fl
+
+
+def lib_project(cam, pts, lam=None):
+    """zoic_project_point (lam None) or zoic_project_point_spectral on every point: (ps (m,2) float32, flags (m,) uint32)"""
+    lib, h = _capi.load(), cam._h
+    m = len(pts)
+    ps, fl = np.zeros((m, 2), np.float32), np.zeros(m, np.uint32)
+    pts = np.ascontiguousarray(pts, np.float32)
+    V, FP, UP = ctypes.POINTER(_capi.Vec3), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+    po, pp, pf = pts.ctypes.data, ps.ctypes.data, fl.ctypes.data
+    if lam is None:
+        for i in range(m):
+            rc = lib.zoic_project_point(h, ctypes.cast(po + 12 * i, V), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
+            assert rc == 0, rc
+        return ps, fl
+    lam = np.broadcast_to(np.asarray(lam, np.float32), (m,))
+    for i in range(m):
+        rc = lib.zoic_project_point_spectral(h, ctypes.cast(po + 12 * i, V), float(lam[i]), ctypes.cast(pp + 8 * i, FP), ctypes.cast(pf + 4 * i, UP))
         assert rc == 0, rc
     return ps, fl
 

@@ -27,6 +27,11 @@ from traceback_ref import RAYTRACED
 
 F32 = np.float32
 REF_STEP = 1e-6
+LEFT_OUT_CAP = 0.03      # the largest share of the live rays picked that a yardstick step may leave out
+MIN_RAYS = 1024          # ... and the fewest rays it must keep
+LAMBDA_D = np.float32(587.5618)
+W, H, SPP = 64, 36, 2    # the frame of the device round trips (tests/test_traceback_jacobian_gpu.py): 4 608 rays
+N = W * H * SPP
 YARDSTICK_STEPS = tuple(2.0 ** -k for k in range(6, 15))   # h: the yardstick's steps are h s_i
 
 
@@ -221,3 +226,31 @@ def measure(cam, trace, edge, o, d, lam, s, ref_steps=(REF_STEP, 1e-5), steps=YA
               % (tag, round(np.log2(r["h"])), r["kept"].sum(), len(o), 100 * r["left_out"], 100 * r["left_out64"], r["j_med"],
                  r["j_p99"], r["y_med"], r["y_p99"]))
     return dict(cam=cam, s=s, o=o, d=d, lam=lam, ref=ref, ps=ps, fl=fl, J=J, Jref=Jref, Jref5=Jref5, eJ=eJ, rows=rows, n=len(o))
+
+
+def best(A):
+    """the yardstick's step of measure()'s result A: the lowest median among the steps that leave out at most LEFT_OUT_CAP"""
+    eligible = [r for r in A["rows"] if r["left_out"] <= LEFT_OUT_CAP]
+    assert eligible, [(r["h"], r["left_out"]) for r in A["rows"]]
+    return min(eligible, key=lambda r: r["y_med"])
+
+
+def check_accuracy(A, tag):
+    """the requirement: J's median <= the yardstick's / 4, J's p99 <= the yardstick's, at the yardstick's step and at its best one"""
+    b = best(A)
+    overall = min((r for r in A["rows"] if r["kept"].sum() >= MIN_RAYS), key=lambda r: r["y_med"])
+    print("%s: stride %d, %d rays kept at h = 2^%d (left out %.2f %%): J median %.3g p99 %.3g; yardstick median %.3g p99 %.3g; "
+          "best yardstick median of any step %.3g (h = 2^%d, J there %.3g)"
+          % (tag, A["stride"], b["kept"].sum(), round(np.log2(b["h"])), 100 * b["left_out"], b["j_med"], b["j_p99"],
+             b["y_med"], b["y_p99"], overall["y_med"], round(np.log2(overall["h"])), overall["j_med"]))
+    assert b["kept"].sum() >= MIN_RAYS, b["kept"].sum()
+    assert b["left_out"] <= LEFT_OUT_CAP and b["left_out64"] <= LEFT_OUT_CAP
+    assert b["j_med"] <= b["y_med"] / 4.0, (b["j_med"], b["y_med"])
+    assert b["j_p99"] <= b["y_p99"], (b["j_p99"], b["y_p99"])
+    # and against the best the yardstick does at ANY of its steps, on that step's own rays
+    assert overall["j_med"] <= overall["y_med"] / 4.0 and overall["j_p99"] <= overall["y_p99"], overall
+
+
+def residual(J, T):
+    """|J T - I|_max per ray: J (m,2,6), T (m,6,2)"""
+    return np.abs(np.einsum("nij,njk->nik", J, T) - np.eye(2)[None]).max((1, 2))
