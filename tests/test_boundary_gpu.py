@@ -350,6 +350,36 @@ def test_host_path_pieces_pinned_and_pageable_equal_the_device_path(gpu, n):
     pin_s.free(); pin_r.free()
 
 
+def test_arnold_rows_across_four_pieces_equal_the_device_path(gpu):
+    """zoic_create_rays_arnold[_differentials] on pageable arrays of 3 * 262144 + 257 rows: four pieces of 262144 rows at most, so
+    both buffer sets are used twice (piece k waits for piece k-2 on the copy-in and on the kernel side) and the last piece is a
+    ragged 257 rows.  Origin, dir and the three weights of every row must be zoic_create_rays_device's records, the twelve derivative
+    fields zoic_ray_differentials_device's for the rows' own dsx, dsy, bit for bit."""
+    import torch
+    n = 3 * 262144 + 257
+    cam = _c2_camera()
+    c = CONFIGS["C2"]
+    base = c["width"] * 300 * c["spp"] + 12_345
+    s = synthetic_samples(n, c["width"], c["height"], c["spp"], seed=1, ray_index_base=base)
+    dsx, dsy = 1.25e-3, -7.5e-4
+    inputs = np.zeros((n, 7), np.float32)                             # AtCameraInput: sx, sy, dsx, dsy, lensx, lensy, relative_time
+    inputs[:, 0], inputs[:, 1], inputs[:, 4], inputs[:, 5] = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+    inputs[:, 2], inputs[:, 3] = dsx, dsy
+    dev_s = torch.from_numpy(s).cuda()
+    dev_rays = cam.create_rays(dev_s, ray_index_base=base)["rays"]
+    diffs = cam.ray_differentials(dev_s, dev_rays, dsx=dsx, dsy=dsy, ray_index_base=base).cpu().numpy()
+    rays = dev_rays.cpu().numpy()
+    assert (rays[:, 6] != 0).any() and (rays[:, 6] == 0).any() and diffs.any()
+    for differentials in (False, True):
+        rows = cam.create_rays_arnold(inputs, ray_index_base=base, differentials=differentials)
+        assert rows.shape == (n, 21)
+        assert np.array_equal(bits(rows[:, 0:6]), bits(rays[:, 0:6])), "differentials=%s: origin / dir" % differentials
+        assert np.array_equal(bits(rows[:, 18:21]), bits(np.repeat(rays[:, 6:7], 3, axis=1))), "differentials=%s: weights" % differentials
+        if differentials:
+            assert np.array_equal(bits(rows[:, 6:18]), bits(diffs))
+    cam.close()
+
+
 def test_failed_bokeh_load_is_not_forgotten(gpu):
     """after a failed bokeh load a second update with the same parameters must not report success with the
     image silently off; new pixels under an unchanged bokehPath must rebuild the CDFs."""

@@ -1,5 +1,5 @@
 // capi.cpp -- the C-ABI of libzoic_amd.so (include/zoic_amd.h): zoic's Arnold node methods restated over plain
-// pointers.  Host logic only; every ray is produced by the HIP kernels (kernels.hip / kolb_fast.hip).
+// pointers.  Host logic only; every ray is produced by the HIP kernels (kernels.hip / kolb_pool*.hip).
 //
 //   zoic_camera_create   <- node_initialize  zoic.cpp:1565-1572
 //   zoic_camera_update   <- node_update      zoic.cpp:1575-1720
@@ -225,17 +225,20 @@ struct Mailbox {
         return e;
     }
     // the resident kernel retires (adding its ray counters to the camera's) and nothing of it is left in flight; a tile it was
-    // working on is finished first (mailbox.hip: no wave leaves with a batch in hand)
-    hipError_t stop()
+    // working on is finished first (mailbox.hip: no wave leaves with a batch in hand).  launchM is held and the mailbox exists.
+    hipError_t retire_locked()
     {
-        std::lock_guard<std::mutex> lk(launchM);
-        if (!mem.host || !stream) return hipSuccess;
         request(0)->stop = 1u;
         std::atomic_thread_fence(std::memory_order_seq_cst);
         const hipError_t e = hipStreamSynchronize(stream);
         request(0)->stop = 0u;
         header()->alive = 0u;
         return e;
+    }
+    hipError_t stop()
+    {
+        std::lock_guard<std::mutex> lk(launchM);
+        return mem.host && stream ? retire_locked() : hipSuccess;
     }
     void release();
 };
@@ -626,6 +629,14 @@ zoic_status check_ray_call(const zoic_camera *cam)
     return ZOIC_OK;
 }
 
+// the camera's lens model is one that produces rays
+zoic_status check_produces_rays(const zoic_camera *cam)
+{
+    const int model = cam->params.p.lensModel;
+    if (model == ZOIC_RAYTRACED || model == ZOIC_THINLENS) return ZOIC_OK;
+    return fail(ZOIC_ERR_INVALID_ARGUMENT, "lensModel NONE produces no rays (zoic.cpp:1966-1968)");
+}
+
 // the result of a call that ends with a kernel launch: rc is what the launcher returned (hipGetLastError)
 zoic_status launch_status(int rc)
 {
@@ -648,9 +659,8 @@ zoic_status launch_rays(zoic_camera *cam, uint64_t n, const float *d_samples, co
                         hipStream_t stream, int modeOverride = -1, bool counted = true)
 {
     static_assert(sizeof(zoic_ray) == sizeof(RayRecord), "zoic_ray layout");
+    if (zoic_status s = check_produces_rays(cam)) return s;
     const int model = cam->params.p.lensModel;
-    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS)
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "lensModel NONE produces no rays (zoic.cpp:1966-1968)");
     const int mode = modeOverride >= 0 ? modeOverride : cam->kernel_mode();
     DeviceCounters *const dCounters = counted ? cam->dCounters : nullptr;
     // the Kolb launch's scratch (kernels.hpp): decision-safe FAST's work list, the finish kernel's byte map
@@ -712,6 +722,62 @@ uint64_t host_piece(uint64_t n)
     if (p < (256ull << 10)) p = 256ull << 10;
     if (p > (4ull << 20)) p = 4ull << 20;
     return p;
+}
+
+// The host-buffer calls (zoic_create_rays_host, zoic_create_rays_arnold[_differentials]): n samples in pieces through a leased
+// context's three streams (copy-in, kernels, copy-out), chained by events, on two buffer sets: while piece k is copied out, piece
+// k+1 is traced and piece k+2 is copied in.  With page-locked caller buffers (zoic_host_alloc / zoic_host_register) every copy is
+// truly asynchronous; with pageable ones hipMemcpyAsync stages internally and the pipeline degrades gracefully.
+// `missing`: the text of the call's NULL-argument error, or nullptr (looked at only behind n == 0).  The call supplies, per piece of
+// m samples at `off` on buffer set b of the context:
+//   reserve(C, b, cap)      room for a piece of cap samples in set b; reports its own failure     -> zoic_status
+//   copyIn(C, b, off, m)    the piece's inputs, enqueued on C.sIn                                 -> hipError_t
+//   run(C, b, off, m)       its kernels, enqueued on C.sRun; reports its own failure (fail())     -> zoic_status
+//   copyOut(C, b, off, m)   its results, enqueued on C.sOut                                       -> hipError_t
+// Everything comes from the context: nothing camera-wide is touched, and only the call's own streams are synchronised.
+template <class Reserve, class CopyIn, class Run, class CopyOut>
+zoic_status host_pipeline(zoic_camera *cam, uint64_t n, const char *missing, Reserve reserve, CopyIn copyIn, Run run, CopyOut copyOut)
+{
+    if (zoic_status s = check_ray_call(cam)) return s;
+    if (n == 0) return ZOIC_OK;
+    if (missing) return fail(ZOIC_ERR_INVALID_ARGUMENT, missing);
+    DeviceGuard guard(cam->device);
+    ZOIC_HIP(guard.error());
+    ContextLease lease(cam);
+    if (!lease) return fail(ZOIC_ERR_HIP, std::string("call context: ") + hipGetErrorString(lease.error()));
+    CallContext &C = *lease;
+    const uint64_t piece = host_piece(n);
+    const size_t cap = static_cast<size_t>(std::min<uint64_t>(n, piece));
+    for (int b = 0; b < 2 && (b == 0 || n > piece); ++b)
+        if (zoic_status s = reserve(C, b, cap)) return s;
+    zoic_status status = ZOIC_OK;
+    uint64_t k = 0;
+    for (uint64_t off = 0; off < n && status == ZOIC_OK; off += piece, ++k) {
+        const int b = static_cast<int>(k & 1u);
+        const uint64_t m = std::min<uint64_t>(piece, n - off);
+        hipError_t e = hipSuccess;
+        // copy-in: set b's inputs are free once the kernels of piece k-2 are done
+        if (k >= 2) e = hipStreamWaitEvent(C.sIn, C.runDone[b], 0);
+        if (e == hipSuccess) e = copyIn(C, b, off, m);
+        if (e == hipSuccess) e = hipEventRecord(C.inDone[b], C.sIn);
+        // kernels: need the inputs, and set b's results back from the copy-out of piece k-2
+        if (e == hipSuccess) e = hipStreamWaitEvent(C.sRun, C.inDone[b], 0);
+        if (e == hipSuccess && k >= 2) e = hipStreamWaitEvent(C.sRun, C.outDone[b], 0);
+        if (e != hipSuccess) { status = fail(ZOIC_ERR_HIP, std::string("copy-in: ") + hipGetErrorString(e)); break; }
+        status = run(C, b, off, m);
+        if (status != ZOIC_OK) break;
+        e = hipEventRecord(C.runDone[b], C.sRun);
+        // copy-out
+        if (e == hipSuccess) e = hipStreamWaitEvent(C.sOut, C.runDone[b], 0);
+        if (e == hipSuccess) e = copyOut(C, b, off, m);
+        if (e == hipSuccess) e = hipEventRecord(C.outDone[b], C.sOut);
+        if (e != hipSuccess) status = fail(ZOIC_ERR_HIP, std::string("copy-out: ") + hipGetErrorString(e));
+    }
+    {   // own streams only: other threads' calls are not waited for
+        const hipError_t e = C.sync_all();
+        if (e != hipSuccess && status == ZOIC_OK) status = fail(ZOIC_ERR_HIP, std::string("stream sync: ") + hipGetErrorString(e));
+    }
+    return status;
 }
 
 // one 32-byte record -> the AtCameraOutput fields zoic writes (zoic.cpp:1960-1961, 1974-1977, 1952, 1981-1987)
@@ -781,22 +847,33 @@ zoic_status fast_self_check(zoic_camera *cam, bool &keep)
     return ZOIC_OK;
 }
 
-// the dispersion table of the camera's lens (spectral.hpp), trace order: the prescription's V-numbers or the override (file order,
-// front first: reversed here)
+// the V-number of trace-order surface i of the camera's lens: the prescription's or the override (file order, front first: reversed here)
+float abbe_number(const zoic_camera *cam, size_t i)
+{
+    const std::vector<LensRow> &rows = cam->lens.rows;
+    return cam->abbeOverride.size() == rows.size() ? cam->abbeOverride[rows.size() - 1 - i] : rows[i].abbe;
+}
+
+// the dispersion table of the camera's lens (spectral.hpp), trace order
 void fill_spectral(const zoic_camera *cam, SpectralTable &W)
 {
     W = SpectralTable{};
     const std::vector<LensRow> &rows = cam->lens.rows;
     const size_t n = std::min<size_t>(rows.size(), kMaxSurfaces);
     W.count = static_cast<int32_t>(n);
-    const bool override = cam->abbeOverride.size() == rows.size() && !rows.empty();
     for (size_t i = 0; i < n; ++i) {
-        const float abbe = override ? cam->abbeOverride[rows.size() - 1 - i] : rows[i].abbe;
         W.iorD[i] = rows[i].ior;
-        W.cauchyB[i] = cauchy_b(rows[i].ior, abbe);
+        W.cauchyB[i] = cauchy_b(rows[i].ior, abbe_number(cam, i));
         const double R = static_cast<double>(rows[i].radius);
         W.invAbsRR[i] = static_cast<float>(1.0 / (std::fabs(R) * R));
     }
+}
+
+// a per-surface override that does not fit the lens: "zoic_camera_set_coatings: 5 coatings for a lens of 7 surfaces"
+zoic_status surface_count_mismatch(const char *setter, size_t given, const char *what, size_t surfaces)
+{
+    return fail(ZOIC_ERR_INVALID_ARGUMENT,
+                std::string(setter) + ": " + std::to_string(given) + " " + what + " for a lens of " + std::to_string(surfaces) + " surfaces");
 }
 
 // the film table of the camera's lens (transmittance.hpp), trace order: the override (file order, front first: reversed here) or all
@@ -814,61 +891,39 @@ void fill_film(const zoic_camera *cam, FilmTable &F)
     }
 }
 
-// the lens rows (trace order) as the arrays the backward tables' fillers take
-struct FlatRows {
-    int n;
-    float radius[kMaxSurfaces], thickness[kMaxSurfaces], ior[kMaxSurfaces], aperture[kMaxSurfaces];
-    explicit FlatRows(const LensSystem &L) : n(static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces)))
-    {
-        for (int i = 0; i < n; ++i) {
-            radius[i] = L.rows[i].radius; thickness[i] = L.rows[i].thickness; ior[i] = L.rows[i].ior; aperture[i] = L.rows[i].aperture;
+// what the backward tables' fillers read of the camera's current tables (backward_tables.hpp)
+LensView lens_view(const zoic_camera *cam)
+{
+    const zoic_params &p = cam->params.p;
+    LensView V;
+    V.tanFov = cam->tanFov;
+    if (p.lensModel == ZOIC_THINLENS) {
+        V.model = 0;
+        V.apertureRadius = cam->apertureRadius; V.focalDistance = p.focalDistance; V.useDof = p.useDof != 0;
+        V.ovDistance = p.opticalVignettingDistance; V.ovRadius = p.opticalVignettingRadius;
+    } else if (p.lensModel == ZOIC_RAYTRACED) {
+        const LensSystem &L = cam->lens;
+        V.model = 1;
+        V.count = static_cast<int>(std::min<size_t>(L.rows.size(), kMaxSurfaces));
+        for (int i = 0; i < V.count; ++i) {
+            V.radius[i] = L.rows[i].radius; V.thickness[i] = L.rows[i].thickness; V.ior[i] = L.rows[i].ior; V.aperture[i] = L.rows[i].aperture;
         }
+        V.apertureElement = L.apertureElement; V.userApertureRadius = L.userApertureRadius; V.originShift = L.originShift;
+        V.sensorWidth = p.sensorWidth;
+        V.useLUT = p.kolbSamplingLUT != 0 && L.hasLUT; V.lutSize = L.hasLUT ? kLutEntries : 0;
+        V.domain = cam->fastDomain;
     }
-};
-
-// the reverse projection's table (reverse.hpp) of the camera's current tables
-void fill_reverse(zoic_camera *cam)
-{
-    const zoic_params &p = cam->params.p;
-    const LensSystem &L = cam->lens;
-    if (p.lensModel != ZOIC_RAYTRACED) {
-        fill_reverse_table(cam->reverse, p.lensModel == ZOIC_THINLENS ? 0 : 2, cam->tanFov, 0, nullptr, nullptr, nullptr, nullptr, -1, 0.0f,
-                           0.0f, 0.0f, false, 0, false);
-        return;
-    }
-    const FlatRows R(L);
-    fill_reverse_table(cam->reverse, 1, cam->tanFov, R.n, R.radius, R.thickness, R.ior, R.aperture, L.apertureElement, L.userApertureRadius,
-                       L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0, cam->fastDomain);
+    return V;
 }
 
-// the trace-back's table (traceback.hpp) of the camera's current tables
-void fill_traceback(zoic_camera *cam)
+// the reverse projection's, the trace-back's and the ghost tracer's tables (reverse.hpp, traceback.hpp, ghost.hpp) of the camera's
+// current tables, and the ghost table's copy on the device
+zoic_status fill_backward_tables(zoic_camera *cam)
 {
-    const zoic_params &p = cam->params.p;
-    const LensSystem &L = cam->lens;
-    if (p.lensModel != ZOIC_RAYTRACED) {
-        fill_traceback_table(cam->traceBack, p.lensModel == ZOIC_THINLENS ? 0 : 2, cam->tanFov, 0, nullptr, nullptr, nullptr, nullptr, -1, 0.0f,
-                             0.0f, 0.0f, false, 0, false, cam->apertureRadius, p.focalDistance, p.useDof != 0, p.opticalVignettingDistance,
-                             p.opticalVignettingRadius);
-        return;
-    }
-    const FlatRows R(L);
-    fill_traceback_table(cam->traceBack, 1, cam->tanFov, R.n, R.radius, R.thickness, R.ior, R.aperture, L.apertureElement,
-                         L.userApertureRadius, L.originShift, p.sensorWidth, p.kolbSamplingLUT != 0 && L.hasLUT, L.hasLUT ? kLutEntries : 0,
-                         cam->fastDomain, 0.0f, 0.0f, false, 0.0f, 0.0f);
-}
-
-// the ghost tracer's geometry (ghost.hpp) of the camera's current tables, and its copy on the device
-zoic_status fill_ghost(zoic_camera *cam)
-{
-    const zoic_params &p = cam->params.p;
-    const LensSystem &L = cam->lens;
-    if (p.lensModel != ZOIC_RAYTRACED) {
-        fill_ghost_table(cam->ghost, p.lensModel == ZOIC_THINLENS ? 0 : 2, 0, nullptr, nullptr, nullptr, -1, 0.0f);
-    } else {
-        const FlatRows R(L);
-        fill_ghost_table(cam->ghost, 1, R.n, R.radius, R.thickness, R.aperture, L.apertureElement, L.userApertureRadius);
-    }
+    const LensView V = lens_view(cam);
+    fill_reverse_table(cam->reverse, V);
+    fill_traceback_table(cam->traceBack, V);
+    fill_ghost_table(cam->ghost, V);
     if (cam->device != ZOIC_DEVICE_NONE) ZOIC_HIP(hipMemcpy(cam->dGhost, &cam->ghost, sizeof(GhostTable), hipMemcpyHostToDevice));
     return ZOIC_OK;
 }
@@ -1263,11 +1318,9 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
     default: break;
     }
     if (p->lensModel == ZOIC_RAYTRACED && !cam->abbeOverride.empty() && cam->abbeOverride.size() != cam->lens.rows.size())
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_abbe_numbers: " + std::to_string(cam->abbeOverride.size()) +
-                                                   " V-numbers for a lens of " + std::to_string(cam->lens.rows.size()) + " surfaces");
+        return surface_count_mismatch("zoic_camera_set_abbe_numbers", cam->abbeOverride.size(), "V-numbers", cam->lens.rows.size());
     if (p->lensModel == ZOIC_RAYTRACED && !cam->coatingIndex.empty() && cam->coatingIndex.size() != cam->lens.rows.size())
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coatings: " + std::to_string(cam->coatingIndex.size()) +
-                                                   " coatings for a lens of " + std::to_string(cam->lens.rows.size()) + " surfaces");
+        return surface_count_mismatch("zoic_camera_set_coatings", cam->coatingIndex.size(), "coatings", cam->lens.rows.size());
 
     // camera->params = parms, zoic.cpp:1719
     cam->params.p = *p;
@@ -1298,9 +1351,8 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
         exposure_terms(p->exposureControl, t.exposureMul, t.exposureOn);
         t.seed = cam->seed;
     }
-    fill_reverse(cam);   // (RAYTRACED: fastDomain is still the geometric test here; the self-check below may narrow it)
-    fill_traceback(cam);
-    if (zoic_status s = fill_ghost(cam)) { cam->updated = false; cam->params.valid = false; return s; }
+    // (RAYTRACED: fastDomain is still the geometric test here; the self-check below may narrow it)
+    if (zoic_status s = fill_backward_tables(cam)) { cam->updated = false; cam->params.valid = false; return s; }
     cam->updated = true;
     // the FAST modes are kept only for a camera they are good for (fast_self_check above; the geometric test comes first).
     // The verdict depends on the lens tables, the LUT and the bokeh tables only: an update that rebuilt none of them (exposure,
@@ -1331,118 +1383,63 @@ zoic_status zoic_create_rays_device(zoic_camera *cam, uint64_t n, const float *d
 zoic_status zoic_create_rays_host(zoic_camera *cam, uint64_t n, const float *h_samples, const uint32_t *h_rng_states,
                                   uint64_t ray_index_base, zoic_ray *h_rays)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!h_samples) return fail(ZOIC_ERR_INVALID_ARGUMENT, "h_samples is NULL");
-    if (!h_rays) return fail(ZOIC_ERR_INVALID_ARGUMENT, "h_rays is NULL");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    ContextLease lease(cam);
-    if (!lease) return fail(ZOIC_ERR_HIP, std::string("call context: ") + hipGetErrorString(lease.error()));
-    CallContext &C = *lease;
-    // Pieces run through the context's three streams (copy-in, kernels, copy-out), chained by events, on two buffer sets:
-    // while piece k is copied out, piece k+1 is traced and piece k+2 is copied in.  With page-locked caller buffers
-    // (zoic_host_alloc / zoic_host_register) every copy is truly asynchronous; with pageable ones hipMemcpyAsync stages
-    // internally and the pipeline degrades gracefully.
-    const uint64_t piece = host_piece(n);
-    const size_t cap = static_cast<size_t>(std::min<uint64_t>(n, piece));
-    for (int b = 0; b < 2 && (b == 0 || n > piece); ++b) {
-        ZOIC_HIP(C.dSamples[b].reserve(cap * 4));
-        ZOIC_HIP(C.dRays[b].reserve(cap));
-        if (h_rng_states) ZOIC_HIP(C.dRng[b].reserve(cap * 4));
-    }
-    zoic_status status = ZOIC_OK;
-    uint64_t k = 0;
-    for (uint64_t off = 0; off < n && status == ZOIC_OK; off += piece, ++k) {
-        const int b = static_cast<int>(k & 1u);
-        const uint64_t m = std::min<uint64_t>(piece, n - off);
-        hipError_t e = hipSuccess;
-        // copy-in: dSamples[b] is free once the kernels of piece k-2 are done
-        if (k >= 2) e = hipStreamWaitEvent(C.sIn, C.runDone[b], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(C.dSamples[b].ptr, h_samples + off * 4, m * 16, hipMemcpyHostToDevice, C.sIn);
-        const uint32_t *dRng = nullptr;
-        if (e == hipSuccess && h_rng_states) {
-            e = hipMemcpyAsync(C.dRng[b].ptr, h_rng_states + off * 4, m * 16, hipMemcpyHostToDevice, C.sIn);
-            dRng = C.dRng[b].ptr;
-        }
-        if (e == hipSuccess) e = hipEventRecord(C.inDone[b], C.sIn);
-        // kernels: need the samples, and dRays[b] back from the copy-out of piece k-2
-        if (e == hipSuccess) e = hipStreamWaitEvent(C.sRun, C.inDone[b], 0);
-        if (e == hipSuccess && k >= 2) e = hipStreamWaitEvent(C.sRun, C.outDone[b], 0);
-        if (e != hipSuccess) { status = fail(ZOIC_ERR_HIP, std::string("H2D: ") + hipGetErrorString(e)); break; }
-        status = launch_rays(cam, m, C.dSamples[b].ptr, dRng, ray_index_base + off, C.dRays[b].ptr, C.sRun);
-        if (status != ZOIC_OK) break;
-        e = hipEventRecord(C.runDone[b], C.sRun);
-        // copy-out
-        if (e == hipSuccess) e = hipStreamWaitEvent(C.sOut, C.runDone[b], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_rays + off, C.dRays[b].ptr, m * sizeof(zoic_ray), hipMemcpyDeviceToHost, C.sOut);
-        if (e == hipSuccess) e = hipEventRecord(C.outDone[b], C.sOut);
-        if (e != hipSuccess) status = fail(ZOIC_ERR_HIP, std::string("D2H: ") + hipGetErrorString(e));
-    }
-    {   // own streams only: other threads' calls are not waited for
-        const hipError_t e = C.sync_all();
-        if (e != hipSuccess && status == ZOIC_OK) status = fail(ZOIC_ERR_HIP, std::string("stream sync: ") + hipGetErrorString(e));
-    }
-    return status;
+    return host_pipeline(
+        cam, n, !h_samples ? "h_samples is NULL" : !h_rays ? "h_rays is NULL" : nullptr,
+        [&](CallContext &C, int b, size_t cap) -> zoic_status {
+            ZOIC_HIP(C.dSamples[b].reserve(cap * 4));
+            ZOIC_HIP(C.dRays[b].reserve(cap));
+            if (h_rng_states) ZOIC_HIP(C.dRng[b].reserve(cap * 4));
+            return ZOIC_OK;
+        },
+        [&](CallContext &C, int b, uint64_t off, uint64_t m) {
+            hipError_t e = hipMemcpyAsync(C.dSamples[b].ptr, h_samples + off * 4, m * 16, hipMemcpyHostToDevice, C.sIn);
+            if (e == hipSuccess && h_rng_states) e = hipMemcpyAsync(C.dRng[b].ptr, h_rng_states + off * 4, m * 16, hipMemcpyHostToDevice, C.sIn);
+            return e;
+        },
+        [&](CallContext &C, int b, uint64_t off, uint64_t m) {
+            return launch_rays(cam, m, C.dSamples[b].ptr, h_rng_states ? C.dRng[b].ptr : nullptr, ray_index_base + off, C.dRays[b].ptr, C.sRun);
+        },
+        [&](CallContext &C, int b, uint64_t off, uint64_t m) {
+            return hipMemcpyAsync(h_rays + off, C.dRays[b].ptr, m * sizeof(zoic_ray), hipMemcpyDeviceToHost, C.sOut);
+        });
 }
 
 // zoic_create_rays_arnold and zoic_create_rays_arnold_differentials: one pipeline, the expansion of the records to rows differs
-// (differentials: the rows' derivative fields are traced from the inputs still on the device, differentials.hip)
+// (differentials: the rows' derivative fields are traced from the inputs still on the device, differentials.hip).
+// The 32-byte records are expanded to AtCameraOutput rows ON THE GPU (kernels.hip expand_outputs_kernel) and leave as whole 84-byte
+// rows straight into the caller's array: the host touches nothing (round 2 expanded on the calling thread: 84 Mrays/s per thread
+// against PCIe's ~0.45 Grays/s).
 static zoic_status create_rays_arnold_rows(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs, zoic_camera_output *outputs,
                                            uint64_t ray_index_base, bool differentials)
 {
-    if (zoic_status s = check_ray_call(cam)) return s;
-    if (n == 0) return ZOIC_OK;
-    if (!inputs || !outputs) return fail(ZOIC_ERR_INVALID_ARGUMENT, "NULL argument");
     static_assert(sizeof(zoic_camera_input) == 28 && sizeof(zoic_camera_output) == 84, "Arnold POD layout");
-    DeviceGuard guard(cam->device);
-    ZOIC_HIP(guard.error());
-    ContextLease lease(cam);
-    if (!lease) return fail(ZOIC_ERR_HIP, std::string("call context: ") + hipGetErrorString(lease.error()));
-    CallContext &C = *lease;
-    // Same three-stream pipeline as zoic_create_rays_host.  The 32-byte records are expanded to AtCameraOutput rows ON THE
-    // GPU (kernels.hip expand_outputs_kernel) and leave as whole 84-byte rows straight into the caller's array: the host
-    // touches nothing (round 2 expanded on the calling thread: 84 Mrays/s per thread against PCIe's ~0.45 Grays/s).
-    const uint64_t piece = host_piece(n);
-    const size_t cap = static_cast<size_t>(std::min<uint64_t>(n, piece));
-    for (int b = 0; b < 2 && (b == 0 || n > piece); ++b) {
-        ZOIC_HIP(C.dInputs7[b].reserve(cap * 7));
-        ZOIC_HIP(C.dSamples[b].reserve(cap * 4));
-        ZOIC_HIP(C.dRays[b].reserve(cap));
-        ZOIC_HIP(C.dOut21[b].reserve(cap * 21));
-    }
-    zoic_status status = ZOIC_OK;
-    uint64_t k = 0;
-    for (uint64_t off = 0; off < n && status == ZOIC_OK; off += piece, ++k) {
-        const int b = static_cast<int>(k & 1u);
-        const uint64_t m = std::min<uint64_t>(piece, n - off);
-        hipError_t e = hipSuccess;
-        if (k >= 2) e = hipStreamWaitEvent(C.sIn, C.runDone[b], 0);   // dInputs7[b] is free once piece k-2's kernels are done
-        if (e == hipSuccess) e = hipMemcpyAsync(C.dInputs7[b].ptr, inputs + off, m * sizeof(zoic_camera_input), hipMemcpyHostToDevice, C.sIn);
-        if (e == hipSuccess) e = hipEventRecord(C.inDone[b], C.sIn);
-        if (e == hipSuccess) e = hipStreamWaitEvent(C.sRun, C.inDone[b], 0);
-        if (e == hipSuccess && k >= 2) e = hipStreamWaitEvent(C.sRun, C.outDone[b], 0);   // dOut21[b] back from piece k-2's copy-out
-        if (e == hipSuccess) e = static_cast<hipError_t>(launch_pack_inputs(C.dInputs7[b].ptr, C.dSamples[b].ptr, m, C.sRun));
-        if (e != hipSuccess) { status = fail(ZOIC_ERR_HIP, std::string("H2D + pack: ") + hipGetErrorString(e)); break; }
-        status = launch_rays(cam, m, C.dSamples[b].ptr, nullptr, ray_index_base + off, C.dRays[b].ptr, C.sRun);
-        if (status != ZOIC_OK) break;
-        if (differentials)
-            e = static_cast<hipError_t>(launch_expand_outputs_differentials(cam->params.p.lensModel, cam->kolb, cam->thin, cam->bokehDev,
-                                                                            C.dInputs7[b].ptr, ray_index_base + off, m, C.dRays[b].ptr,
-                                                                            C.dOut21[b].ptr, C.sRun));
-        else
-            e = static_cast<hipError_t>(launch_expand_outputs(C.dRays[b].ptr, C.dOut21[b].ptr, m, C.sRun));
-        if (e == hipSuccess) e = hipEventRecord(C.runDone[b], C.sRun);
-        if (e == hipSuccess) e = hipStreamWaitEvent(C.sOut, C.runDone[b], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(outputs + off, C.dOut21[b].ptr, m * sizeof(zoic_camera_output), hipMemcpyDeviceToHost, C.sOut);
-        if (e == hipSuccess) e = hipEventRecord(C.outDone[b], C.sOut);
-        if (e != hipSuccess) status = fail(ZOIC_ERR_HIP, std::string("expand + D2H: ") + hipGetErrorString(e));
-    }
-    {   // own streams only: other threads' calls are not waited for
-        const hipError_t e = C.sync_all();
-        if (e != hipSuccess && status == ZOIC_OK) status = fail(ZOIC_ERR_HIP, std::string("stream sync: ") + hipGetErrorString(e));
-    }
-    return status;
+    const auto kernel_failed = [](const char *stage, int rc) {
+        return fail(ZOIC_ERR_HIP, std::string(stage) + ": " + hipGetErrorString(static_cast<hipError_t>(rc)));
+    };
+    return host_pipeline(
+        cam, n, !inputs || !outputs ? "NULL argument" : nullptr,
+        [&](CallContext &C, int b, size_t cap) -> zoic_status {
+            ZOIC_HIP(C.dInputs7[b].reserve(cap * 7));
+            ZOIC_HIP(C.dSamples[b].reserve(cap * 4));
+            ZOIC_HIP(C.dRays[b].reserve(cap));
+            ZOIC_HIP(C.dOut21[b].reserve(cap * 21));
+            return ZOIC_OK;
+        },
+        [&](CallContext &C, int b, uint64_t off, uint64_t m) {
+            return hipMemcpyAsync(C.dInputs7[b].ptr, inputs + off, m * sizeof(zoic_camera_input), hipMemcpyHostToDevice, C.sIn);
+        },
+        [&](CallContext &C, int b, uint64_t off, uint64_t m) -> zoic_status {
+            if (const int rc = launch_pack_inputs(C.dInputs7[b].ptr, C.dSamples[b].ptr, m, C.sRun)) return kernel_failed("pack inputs", rc);
+            if (zoic_status s = launch_rays(cam, m, C.dSamples[b].ptr, nullptr, ray_index_base + off, C.dRays[b].ptr, C.sRun)) return s;
+            const int rc = differentials ? launch_expand_outputs_differentials(cam->params.p.lensModel, cam->kolb, cam->thin, cam->bokehDev,
+                                                                               C.dInputs7[b].ptr, ray_index_base + off, m, C.dRays[b].ptr,
+                                                                               C.dOut21[b].ptr, C.sRun)
+                                         : launch_expand_outputs(C.dRays[b].ptr, C.dOut21[b].ptr, m, C.sRun);
+            return rc ? kernel_failed("expand outputs", rc) : ZOIC_OK;
+        },
+        [&](CallContext &C, int b, uint64_t off, uint64_t m) {
+            return hipMemcpyAsync(outputs + off, C.dOut21[b].ptr, m * sizeof(zoic_camera_output), hipMemcpyDeviceToHost, C.sOut);
+        });
 }
 
 zoic_status zoic_create_rays_arnold(zoic_camera *cam, uint64_t n, const zoic_camera_input *inputs, zoic_camera_output *outputs,
@@ -1570,11 +1567,9 @@ int zoic_camera_get_dispersion(const zoic_camera *cam, int capacity, float *ior_
     if (capacity < 0) { fail(ZOIC_ERR_INVALID_ARGUMENT, "capacity is negative"); return -1; }
     SpectralTable W;
     fill_spectral(cam, W);
-    const std::vector<LensRow> &rows = cam->lens.rows;
-    const bool override = cam->abbeOverride.size() == rows.size() && !rows.empty();
     for (int i = 0; i < W.count && i < capacity; ++i) {
         if (ior_d) ior_d[i] = W.iorD[i];
-        if (abbe) abbe[i] = override ? cam->abbeOverride[rows.size() - 1 - i] : rows[i].abbe;
+        if (abbe) abbe[i] = abbe_number(cam, static_cast<size_t>(i));
         if (cauchy_b_out) cauchy_b_out[i] = W.cauchyB[i];
     }
     return W.count;
@@ -1588,8 +1583,7 @@ zoic_status zoic_camera_set_abbe_numbers(zoic_camera *cam, int count, const floa
     if (!V) return fail(ZOIC_ERR_INVALID_ARGUMENT, "V is NULL");
     const bool loaded = cam->updated && cam->params.p.lensModel == ZOIC_RAYTRACED && !cam->lens.rows.empty();
     if (loaded && static_cast<size_t>(count) != cam->lens.rows.size())
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_abbe_numbers: " + std::to_string(count) + " V-numbers for a lens of " +
-                                                   std::to_string(cam->lens.rows.size()) + " surfaces");
+        return surface_count_mismatch("zoic_camera_set_abbe_numbers", static_cast<size_t>(count), "V-numbers", cam->lens.rows.size());
     cam->abbeOverride.assign(V, V + count);
     return ZOIC_OK;
 }
@@ -1640,8 +1634,7 @@ zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *f
     if (!film_index || !film_lambda0_nm) return fail(ZOIC_ERR_INVALID_ARGUMENT, "film_index and film_lambda0_nm must be non-NULL");
     const bool loaded = cam->updated && cam->params.p.lensModel == ZOIC_RAYTRACED && !cam->lens.rows.empty();
     if (loaded && static_cast<size_t>(count) != cam->lens.rows.size())
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coatings: " + std::to_string(count) + " coatings for a lens of " +
-                                                   std::to_string(cam->lens.rows.size()) + " surfaces");
+        return surface_count_mismatch("zoic_camera_set_coatings", static_cast<size_t>(count), "coatings", cam->lens.rows.size());
     for (int i = 0; i < count; ++i) {
         if (film_index[i] == 0.0f) continue;   // uncoated: its lambda0 is not looked at
         if (!std::isfinite(film_index[i]) || !(film_index[i] >= 1.0f) || !std::isfinite(film_lambda0_nm[i]) || !(film_lambda0_nm[i] > 0.0f))
@@ -1711,12 +1704,7 @@ static zoic_status mailbox_ensure_running(zoic_camera *cam, unsigned slot, bool 
     if (moreSlots || moreWorkers) {
         // a tid beyond the slots the resident launch watches, or the camera's first tile: it retires (stop flag; tiles in flight are
         // finished first) and starts again watching more / with the worker waves
-        if (h->alive != 0u) {
-            M.request(0)->stop = 1u;
-            std::atomic_thread_fence(std::memory_order_seq_cst);
-            ZOIC_HIP(hipStreamSynchronize(M.stream));
-            M.request(0)->stop = 0u; h->alive = 0u;
-        }
+        if (h->alive != 0u) ZOIC_HIP(M.retire_locked());
         if (moreSlots) { h->slotsInUse = slot + 1; M.slotsInUse.store(slot + 1, std::memory_order_release); }
         if (moreWorkers) {
             uint32_t groups = kTileWorkerGroups;
@@ -1826,9 +1814,7 @@ zoic_status zoic_camera_create_ray(zoic_camera *cam, const zoic_camera_input *in
     // No launch per call: the sample goes to the resident mailbox kernel (mailbox.hip) through mapped pinned memory.
     if (zoic_status s = check_ray_call(cam)) return s;
     if (!input || !output) return fail(ZOIC_ERR_INVALID_ARGUMENT, "NULL argument");
-    const int model = cam->params.p.lensModel;
-    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS)
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "lensModel NONE produces no rays (zoic.cpp:1966-1968)");
+    if (zoic_status s = check_produces_rays(cam)) return s;
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     TidState *T = cam->tid_state(tid);
@@ -1896,13 +1882,25 @@ static zoic_status tile_post_locked(zoic_camera *cam, unsigned slot, uint32_t n,
     return ZOIC_OK;
 }
 
+// n rows at (dIn -> dOut) through `slot` in posts of kTileMaxSamples at most, each settled before the next; slotM[slot] is held and no
+// tile is in flight on it.  inStride / outStride: the bytes of an input / output row; rows: the request's rows / inputs word
+static zoic_status tile_run_locked(zoic_camera *cam, unsigned slot, uint32_t n, uint64_t dIn, uint64_t dOut, uint32_t inStride, uint32_t outStride,
+                                   uint64_t base, int rows)
+{
+    uint32_t seq = 0;
+    for (uint32_t off = 0; off < n; off += kTileMaxSamples) {
+        const uint32_t m = std::min<uint32_t>(kTileMaxSamples, n - off);
+        if (zoic_status s = tile_post_locked(cam, slot, m, dIn + static_cast<uint64_t>(off) * inStride, dOut + static_cast<uint64_t>(off) * outStride,
+                                             base + off, &seq, rows)) return s;
+        if (zoic_status s = tile_settle_locked(cam, slot)) return s;
+    }
+    return ZOIC_OK;
+}
+
 static zoic_status check_tile_call(const zoic_camera *cam)
 {
     if (zoic_status s = check_ray_call(cam)) return s;
-    const int model = cam->params.p.lensModel;
-    if (model != ZOIC_RAYTRACED && model != ZOIC_THINLENS)
-        return fail(ZOIC_ERR_INVALID_ARGUMENT, "lensModel NONE produces no rays (zoic.cpp:1966-1968)");
-    return ZOIC_OK;
+    return check_produces_rays(cam);
 }
 
 zoic_status zoic_tile_create(zoic_camera *cam, uint32_t capacity, uint16_t tid, zoic_tile **out)
@@ -1976,26 +1974,28 @@ zoic_status zoic_tile_wait(zoic_tile *tile)
     return ZOIC_OK;
 }
 
-zoic_status zoic_tile_set_rows(zoic_tile *tile, int rows)
+// zoic_tile_set_rows / zoic_tile_set_inputs: the tile's `what` layout (its `field`) becomes `value`, which must be `arnold` or `other`, the
+// two that `values` names
+static zoic_status tile_set_layout(zoic_tile *tile, int zoic_tile::*field, int value, int arnold, int other, const char *what, const char *values)
 {
     if (!tile) return fail(ZOIC_ERR_INVALID_ARGUMENT, "tile is NULL");
     if (!tile->cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "the tile's camera has been destroyed");
-    if (rows != ZOIC_TILE_ROWS_ARNOLD && rows != ZOIC_TILE_ROWS_RAYS) return fail(ZOIC_ERR_INVALID_ARGUMENT, "rows: ZOIC_TILE_ROWS_ARNOLD or ZOIC_TILE_ROWS_RAYS");
-    if (tile->seq != 0u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_tile_set_rows between a submit and its wait");
-    tile->rows = rows;
+    if (value != arnold && value != other) return fail(ZOIC_ERR_INVALID_ARGUMENT, std::string(what) + ": " + values);
+    if (tile->seq != 0u) return fail(ZOIC_ERR_INVALID_ARGUMENT, std::string("zoic_tile_set_") + what + " between a submit and its wait");
+    tile->*field = value;
     return ZOIC_OK;
+}
+
+zoic_status zoic_tile_set_rows(zoic_tile *tile, int rows)
+{
+    return tile_set_layout(tile, &zoic_tile::rows, rows, ZOIC_TILE_ROWS_ARNOLD, ZOIC_TILE_ROWS_RAYS, "rows","ZOIC_TILE_ROWS_ARNOLD or ZOIC_TILE_ROWS_RAYS");
 }
 
 const zoic_ray *zoic_tile_rays(const zoic_tile *tile) { return tile ? reinterpret_cast<const zoic_ray *>(tile->outputs) : nullptr; }
 
 zoic_status zoic_tile_set_inputs(zoic_tile *tile, int inputs)
 {
-    if (!tile) return fail(ZOIC_ERR_INVALID_ARGUMENT, "tile is NULL");
-    if (!tile->cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "the tile's camera has been destroyed");
-    if (inputs != ZOIC_TILE_INPUTS_ARNOLD && inputs != ZOIC_TILE_INPUTS_SAMPLES) return fail(ZOIC_ERR_INVALID_ARGUMENT, "inputs: ZOIC_TILE_INPUTS_ARNOLD or ZOIC_TILE_INPUTS_SAMPLES");
-    if (tile->seq != 0u) return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_tile_set_inputs between a submit and its wait");
-    tile->ins = inputs;
-    return ZOIC_OK;
+    return tile_set_layout(tile, &zoic_tile::ins, inputs, ZOIC_TILE_INPUTS_ARNOLD, ZOIC_TILE_INPUTS_SAMPLES, "inputs","ZOIC_TILE_INPUTS_ARNOLD or ZOIC_TILE_INPUTS_SAMPLES");
 }
 
 float *zoic_tile_samples(zoic_tile *tile) { return tile ? reinterpret_cast<float *>(tile->inputs) : nullptr; }
@@ -2041,16 +2041,9 @@ zoic_status zoic_camera_create_rays_tile(zoic_camera *cam, uint32_t n, const zoi
     }
     std::lock_guard<std::mutex> slotLock(M.slotM[slot]);
     if (zoic_status s = tile_settle_locked(cam, slot)) return s;
+    if (dIn != 0 && dOut != 0)
+        return tile_run_locked(cam, slot, n, dIn, dOut, sizeof(zoic_camera_input), sizeof(zoic_camera_output), ray_index_base, ZOIC_TILE_ROWS_ARNOLD);
     uint32_t seq = 0;
-    if (dIn != 0 && dOut != 0) {
-        for (uint32_t off = 0; off < n; off += kTileMaxSamples) {
-            const uint32_t m = std::min<uint32_t>(kTileMaxSamples, n - off);
-            if (zoic_status s = tile_post_locked(cam, slot, m, dIn + static_cast<uint64_t>(off) * sizeof(zoic_camera_input),
-                                                 dOut + static_cast<uint64_t>(off) * sizeof(zoic_camera_output), ray_index_base + off, &seq)) return s;
-            if (zoic_status s = tile_settle_locked(cam, slot)) return s;
-        }
-        return ZOIC_OK;
-    }
     constexpr uint32_t kPiece = 16384;
     const uint32_t piece = std::min<uint32_t>(n, kPiece);
     const unsigned buffers = n > kPiece ? 2u : 1u;
@@ -2082,9 +2075,9 @@ zoic_status zoic_create_rays_device_resident(zoic_camera *cam, uint32_t n, const
     // consumer's batch is a tile request with 16-byte samples in and 32-byte records out -- the layouts of zoic_create_rays_device.
     if (zoic_status s = check_tile_call(cam)) return s;
     if (n == 0u) return ZOIC_OK;
-    if (!d_samples || !d_rays) return fail(ZOIC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (zoic_status s = check_pointer("d_samples", d_samples, 16)) return s;
+    if (zoic_status s = check_pointer("d_rays", d_rays, 16)) return s;
     if (n > ZOIC_RESIDENT_MAX_SAMPLES) return fail(ZOIC_ERR_INVALID_ARGUMENT, "n exceeds ZOIC_RESIDENT_MAX_SAMPLES: zoic_create_rays_device is the call for large batches");
-    if ((reinterpret_cast<uintptr_t>(d_samples) & 15u) || (reinterpret_cast<uintptr_t>(d_rays) & 15u)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "d_samples and d_rays must be 16-byte aligned");
     DeviceGuard guard(cam->device);
     ZOIC_HIP(guard.error());
     {
@@ -2100,15 +2093,8 @@ zoic_status zoic_create_rays_device_resident(zoic_camera *cam, uint32_t n, const
     const unsigned slot = tid % kMailSlots;
     std::lock_guard<std::mutex> slotLock(M.slotM[slot]);
     if (zoic_status s = tile_settle_locked(cam, slot)) return s;
-    const uint64_t dIn = reinterpret_cast<uint64_t>(d_samples), dOut = reinterpret_cast<uint64_t>(d_rays);
-    uint32_t seq = 0;
-    for (uint32_t off = 0; off < n; off += kTileMaxSamples) {
-        const uint32_t m = std::min<uint32_t>(kTileMaxSamples, n - off);
-        if (zoic_status s = tile_post_locked(cam, slot, m, dIn + static_cast<uint64_t>(off) * 16u, dOut + static_cast<uint64_t>(off) * sizeof(zoic_ray), ray_index_base + off, &seq,
-                                             ZOIC_TILE_ROWS_RAYS | (ZOIC_TILE_INPUTS_SAMPLES << 1))) return s;
-        if (zoic_status s = tile_settle_locked(cam, slot)) return s;
-    }
-    return ZOIC_OK;
+    return tile_run_locked(cam, slot, n, reinterpret_cast<uint64_t>(d_samples), reinterpret_cast<uint64_t>(d_rays), 16u, sizeof(zoic_ray), ray_index_base,
+                           ZOIC_TILE_ROWS_RAYS | (ZOIC_TILE_INPUTS_SAMPLES << 1));
 }
 
 int zoic_camera_reverse_ray(const zoic_camera *cam, const zoic_vec3 *Po, float fov, float *Ps, float *relative_time)

@@ -211,26 +211,33 @@ ZOIC_HD GhostRay ghost_record(GP G, MP M, uint32_t pair, bool haveStart, float l
     return ghost_trace(G, M, a, b, lambda, o, d);
 }
 
-// Host: the table of a camera from its lens rows (trace order, after LensSystem::prepare), the rows and the validity conditions of
-// fill_traceback_table.  model: 0 THINLENS, 1 RAYTRACED, 2 NONE.
-inline void fill_ghost_table(GhostTable &G, int model, int count, const float *radius, const float *thickness, const float *aperture,
-                             int apertureElement, float userApertureRadius)
+// Host: the table of a camera from its LensView (backward_tables.hpp), the rows and the validity conditions of
+// fill_traceback_table.
+inline void fill_ghost_table(GhostTable &G, const LensView &L)
 {
     G = GhostTable{};
-    G.model = model;
-    if (model != 1) return;
-    if (count < 1 || count > kMaxSurfaces || apertureElement < 0 || apertureElement >= count) { G.model = 2; return; }
+    G.model = L.model;
+    if (L.model != 1) return;
+    if (!L.rows_valid()) { G.model = 2; return; }
+    const int count = L.count;
     G.count = count;
     float vtx[kMaxSurfaces];
-    backward_vertices(count, thickness, vtx);
+    backward_vertices(count, L.thickness, vtx);
     G.vtxRear = vtx[0];
     G.vtxFront = vtx[count - 1];
     for (int i = 0; i < count; ++i) {
         GhostSurface &S = G.surf[i];
         S.step = (i == 0) ? 0.0f : static_cast<float>(static_cast<double>(vtx[i]) - static_cast<double>(vtx[i - 1]));
-        S.curv = static_cast<float>(1.0 / static_cast<double>(radius[i]));
-        S.housing2 = backward_housing2(aperture[i], i == apertureElement, userApertureRadius);
+        S.curv = static_cast<float>(1.0 / static_cast<double>(L.radius[i]));
+        S.housing2 = backward_housing2(L, i);
     }
+}
+
+// the same from flat arguments (backward_tables.hpp lens_view_of_rows)
+inline void fill_ghost_table(GhostTable &G, int model, int count, const float *radius, const float *thickness, const float *aperture,
+                             int apertureElement, float userApertureRadius)
+{
+    fill_ghost_table(G, lens_view_of_rows(model, 0.0f, count, radius, thickness, nullptr, aperture, apertureElement, userApertureRadius));
 }
 
 // ---- launcher (ghost.hip) ------------------------------------------------------------------------------------------------

@@ -298,27 +298,27 @@ ZOIC_HD uint32_t project_point(const ReverseTable &T, float px, float py, float 
     return flags;
 }
 
-// Host: the table of a camera from its lens rows (trace order, rear first, after LensSystem::prepare: radius, thickness, ior,
-// aperture in cm), or a thin lens / NONE table.  The paraxial entrance pupil is traced in f64: the image of the stop's centre
+// Host: the table of a camera from its LensView (backward_tables.hpp: the lens rows in trace order, rear first, after
+// LensSystem::prepare), or a thin lens / NONE table.  The paraxial entrance pupil is traced in f64: the image of the stop's centre
 // through the front group, n' u' = n u + y (n' - n) / R (the centre of curvature lies at vertex - R).
-inline void fill_reverse_table(ReverseTable &T, int model, float tanFov, int count, const float *radius, const float *thickness,
-                               const float *ior, const float *aperture, int apertureElement, float userApertureRadius, float originShift,
-                               float sensorWidth, bool useLUT, int lutSize, bool domain)
+inline void fill_reverse_table(ReverseTable &T, const LensView &L)
 {
     T = ReverseTable{};
-    T.model = model;
-    T.tanFov = tanFov;
-    if (model != 1) return;
-    if (count < 1 || count > kMaxSurfaces || apertureElement < 0 || apertureElement >= count) { T.model = 2; return; }
-    T.domain = domain ? 1 : 0;
+    T.model = L.model;
+    T.tanFov = L.tanFov;
+    if (L.model != 1) return;
+    if (!L.rows_valid()) { T.model = 2; return; }
+    const int count = L.count, apertureElement = L.apertureElement;
+    const float *radius = L.radius, *ior = L.ior;
+    T.domain = L.domain ? 1 : 0;
     T.count = count;
     T.stop = count - 1 - apertureElement;
-    T.useLUT = useLUT ? 1 : 0;
-    T.lutSize = lutSize;
-    T.halfSensor = sensorWidth * 0.5f;
+    T.useLUT = L.useLUT ? 1 : 0;
+    T.lutSize = L.lutSize;
+    T.halfSensor = L.sensorWidth * 0.5f;
     T.invHalfSensor = 1.0f / T.halfSensor;
     float vtx[kMaxSurfaces];
-    backward_vertices(count, thickness, vtx);
+    backward_vertices(count, L.thickness, vtx);
     // paraxial entrance pupil: a ray from the stop's centre towards the front
     const double u0 = 0.1;
     double y = 0.0, u = u0, z = vtx[apertureElement];
@@ -334,7 +334,7 @@ inline void fill_reverse_table(ReverseTable &T, int model, float tanFov, int cou
     T.zFront = vtx[count - 1];
     T.zPupil = static_cast<float>(zp);
     T.pupilSlope = static_cast<float>(k);
-    T.sensorZ = static_cast<float>(static_cast<double>(originShift) - static_cast<double>(vtx[0]));
+    T.sensorZ = static_cast<float>(static_cast<double>(L.originShift) - static_cast<double>(vtx[0]));
     for (int j = 0; j < count; ++j) {
         const int i = count - 1 - j;
         RevSurface &S = T.surf[j];
@@ -343,9 +343,19 @@ inline void fill_reverse_table(ReverseTable &T, int model, float tanFov, int cou
         const float front = (i + 1 < count) ? ior[i + 1] : 1.0f;
         S.etaF = ior[i] / front;
         S.etaR = front / ior[i];
-        S.housing2 = backward_housing2(aperture[i], i == apertureElement, userApertureRadius);
+        S.housing2 = backward_housing2(L, i);
     }
     T.frontRadius = std::sqrt(T.surf[0].housing2);
+}
+
+// the same from flat arguments (backward_tables.hpp lens_view_of_rows)
+inline void fill_reverse_table(ReverseTable &T, int model, float tanFov, int count, const float *radius, const float *thickness,
+                               const float *ior, const float *aperture, int apertureElement, float userApertureRadius, float originShift,
+                               float sensorWidth, bool useLUT, int lutSize, bool domain)
+{
+    LensView L = lens_view_of_rows(model, tanFov, count, radius, thickness, ior, aperture, apertureElement, userApertureRadius);
+    L.originShift = originShift; L.sensorWidth = sensorWidth; L.useLUT = useLUT; L.lutSize = lutSize; L.domain = domain;
+    fill_reverse_table(T, L);
 }
 
 // ---- launcher (reverse.hip) --------------------------------------------------------------------------------------------

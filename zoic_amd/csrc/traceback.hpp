@@ -255,47 +255,57 @@ ZOIC_HD uint32_t trace_back_ray(const TraceBackTable &T, float ox, float oy, flo
     return tb_trace(T, ox, oy, oz, dx, dy, dz, sx, sy, M, G);
 }
 
-// Host: the table of a camera from its lens rows (trace order, rear first, after LensSystem::prepare: radius, thickness, ior,
-// aperture in cm; the stop's row carries the reference's |R| ~ 1e4 sphere), or a thin lens / NONE table.
+// Host: the table of a camera from its LensView (backward_tables.hpp: the lens rows in trace order, rear first, after
+// LensSystem::prepare; the stop's row carries the reference's |R| ~ 1e4 sphere), or a thin lens / NONE table.
+inline void fill_traceback_table(TraceBackTable &T, const LensView &L)
+{
+    T = TraceBackTable{};
+    T.model = L.model;
+    if (L.model == 0) {
+        T.useDof = L.useDof ? 1 : 0;
+        T.ovOn = L.ovDistance > 0.0f ? 1 : 0;
+        T.aperture2 = L.apertureRadius * L.apertureRadius;
+        T.ovDistance = L.ovDistance;
+        T.ovLimit = L.apertureRadius * L.ovRadius;
+        T.focalDistance = std::fabs(L.focalDistance);
+        T.invFocalTan = 1.0f / (T.focalDistance * L.tanFov);
+        return;
+    }
+    if (L.model != 1) return;
+    if (!L.rows_valid()) { T.model = 2; return; }
+    const int count = L.count;
+    T.domain = L.domain ? 1 : 0;
+    T.count = count;
+    T.useLUT = L.useLUT ? 1 : 0;
+    T.lutSize = L.lutSize;
+    T.halfSensor = L.sensorWidth * 0.5f;
+    T.invHalfSensor = 1.0f / T.halfSensor;
+    float vtx[kMaxSurfaces];
+    backward_vertices(count, L.thickness, vtx);
+    T.zFront = vtx[count - 1];
+    T.sensorZ = static_cast<float>(static_cast<double>(L.originShift) - static_cast<double>(vtx[0]));
+    for (int j = 0; j < count; ++j) {
+        const int i = count - 1 - j;
+        TbSurface &S = T.surf[j];
+        S.dz = (j == 0) ? 0.0f : static_cast<float>(static_cast<double>(vtx[i + 1]) - static_cast<double>(vtx[i]));
+        S.curv = static_cast<float>(1.0 / static_cast<double>(L.radius[i]));
+        const float front = (i + 1 < count) ? L.ior[i + 1] : 1.0f;
+        S.eta = front / L.ior[i];
+        S.housing2 = backward_housing2(L, i);
+    }
+    T.capSlack = kTbCapSlack * std::sqrt(T.surf[0].housing2);
+}
+
+// the same from flat arguments (backward_tables.hpp lens_view_of_rows)
 inline void fill_traceback_table(TraceBackTable &T, int model, float tanFov, int count, const float *radius, const float *thickness,
                                  const float *ior, const float *aperture, int apertureElement, float userApertureRadius, float originShift,
                                  float sensorWidth, bool useLUT, int lutSize, bool domain, float apertureRadius, float focalDistance,
                                  bool useDof, float ovDistance, float ovRadius)
 {
-    T = TraceBackTable{};
-    T.model = model;
-    if (model == 0) {
-        T.useDof = useDof ? 1 : 0;
-        T.ovOn = ovDistance > 0.0f ? 1 : 0;
-        T.aperture2 = apertureRadius * apertureRadius;
-        T.ovDistance = ovDistance;
-        T.ovLimit = apertureRadius * ovRadius;
-        T.focalDistance = std::fabs(focalDistance);
-        T.invFocalTan = 1.0f / (T.focalDistance * tanFov);
-        return;
-    }
-    if (model != 1) return;
-    if (count < 1 || count > kMaxSurfaces || apertureElement < 0 || apertureElement >= count) { T.model = 2; return; }
-    T.domain = domain ? 1 : 0;
-    T.count = count;
-    T.useLUT = useLUT ? 1 : 0;
-    T.lutSize = lutSize;
-    T.halfSensor = sensorWidth * 0.5f;
-    T.invHalfSensor = 1.0f / T.halfSensor;
-    float vtx[kMaxSurfaces];
-    backward_vertices(count, thickness, vtx);
-    T.zFront = vtx[count - 1];
-    T.sensorZ = static_cast<float>(static_cast<double>(originShift) - static_cast<double>(vtx[0]));
-    for (int j = 0; j < count; ++j) {
-        const int i = count - 1 - j;
-        TbSurface &S = T.surf[j];
-        S.dz = (j == 0) ? 0.0f : static_cast<float>(static_cast<double>(vtx[i + 1]) - static_cast<double>(vtx[i]));
-        S.curv = static_cast<float>(1.0 / static_cast<double>(radius[i]));
-        const float front = (i + 1 < count) ? ior[i + 1] : 1.0f;
-        S.eta = front / ior[i];
-        S.housing2 = backward_housing2(aperture[i], i == apertureElement, userApertureRadius);
-    }
-    T.capSlack = kTbCapSlack * std::sqrt(T.surf[0].housing2);
+    LensView L = lens_view_of_rows(model, tanFov, count, radius, thickness, ior, aperture, apertureElement, userApertureRadius);
+    L.originShift = originShift; L.sensorWidth = sensorWidth; L.useLUT = useLUT; L.lutSize = lutSize; L.domain = domain;
+    L.apertureRadius = apertureRadius; L.focalDistance = focalDistance; L.useDof = useDof; L.ovDistance = ovDistance; L.ovRadius = ovRadius;
+    fill_traceback_table(T, L);
 }
 
 // ---- launcher (traceback.hip) ------------------------------------------------------------------------------------------
