@@ -22,7 +22,8 @@ from device_cases import BIG, bits_f32 as _bits, camera as _camera, oracle as _o
 from hero_cases import LOSS_CAMERAS as CAMERAS, cycled as _cycled, loss_reference as _reference
 from host_drivers import run_transmittance as run_driver
 from spectral_ref import BAD, LAMBDA_D32, WAVES
-from transmittance_ref import FILM_INDEX, FILM_LAMBDA0, films_where_media_differ, housings
+from transmittance_cases import coat as _coat, expected as _expected, tables as _tables
+from transmittance_ref import FILM_INDEX, FILM_LAMBDA0
 
 pytestmark = pytest.mark.gpu
 
@@ -34,40 +35,6 @@ SIZES = [1, 63, 65, N]
 @pytest.fixture(scope="module")
 def driver():
     return host_drivers.transmittance()
-
-
-_TABLES = {}
-
-
-def _tables(name):
-    """(dispersion, surfaces, housing2, film in trace order) of the camera's lens, from a tables-only camera"""
-    if name not in _TABLES:
-        cam = hr.spec(name).camera(device=-1)
-        info, disp = cam.info(), cam.dispersion()
-        cam.close()
-        _TABLES[name] = disp, dref.surfaces(info), housings(info), films_where_media_differ(disp)
-    return _TABLES[name]
-
-
-def _coat(cam, name, coated):
-    if coated:
-        nc, l0 = _tables(name)[3]
-        cam.set_coatings(nc[::-1], l0[::-1])      # file order
-    return cam
-
-
-def _expected(driver, name, coated, starts, here, weights):
-    """(n, k) float32: the host build's T from the row's start at the column's wavelength where the record has weight and the
-    wavelength is valid, else +0.0"""
-    disp, surf, h2, film = _tables(name)
-    n, k = here.shape
-    want = np.zeros((n, k), F32)
-    for j in range(k):
-        live = (weights[:, j] != 0) & hr.valid(here[:, j])
-        rows = np.nonzero(live)[0]
-        if len(rows):
-            want[rows, j] = run_driver(driver, surf, disp, here[rows, j], starts[rows, 0:3], starts[rows, 3:6], film if coated else None, h2)
-    return want
 
 
 def _forward(cam, s, lam, st, base=0):
