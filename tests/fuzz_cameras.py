@@ -176,16 +176,19 @@ def update_both(cam, oc, p, oracle_lib):
     return perr, oerr
 
 
-def _oracle_spectral(oracle_lib, p, dispersion, s, lam, states, lens_text=None, image=None):
+def _oracle_spectral(oracle_lib, p, dispersion, s, lam, states, lens_text=None, image=None, oc=None):
     """the oracle camera, group by group: each wavelength's n_i written into its lens table (zo_lenses) after update, restored after.
     lens_text / image: the prescription text and bokeh image of a camera that was given them (default: p's lens file, the
-    hexagon when p asks for an image)"""
-    oc = oracle_lib.OracleCamera()
-    if lens_text is not None:
-        oc.set_lens_text(lens_text)
-    if p.get("useImage"):
-        oc.set_bokeh_image(hexagon_bokeh() if image is None else image)
-    oc.update(**p)
+    hexagon when p asks for an image).  oc: an updated oracle camera the caller owns instead (tests/update_sequences.py: only a camera
+    with the same history has the same exit-pupil LUT); it is not closed, and its d-line indices are back on return"""
+    own = oc is None
+    if own:
+        oc = oracle_lib.OracleCamera()
+        if lens_text is not None:
+            oc.set_lens_text(lens_text)
+        if p.get("useImage"):
+            oc.set_bokeh_image(hexagon_bokeh() if image is None else image)
+        oc.update(**p)
     L = oc._L
     count = L.zo_lens_count(oc._h)
     le = L.zo_lenses(oc._h)
@@ -206,7 +209,8 @@ def _oracle_spectral(oracle_lib, p, dispersion, s, lam, states, lens_text=None, 
         planes[:, rows] = r["planes"]
         flags[rows] = r["flags"]
     after = oc.counters()
-    oc.close()
+    if own:
+        oc.close()
     return dict(planes=planes, flags=flags), {k: after[k] - before[k] for k in after}
 
 

@@ -67,17 +67,21 @@ class Indices:
             self.le[i].ior = float(self.nd[i])
 
 
-def hero_reference(oracle_lib, params, dispersion, samples, lam, states, lens_text=None, image=None, details=False):
+def hero_reference(oracle_lib, params, dispersion, samples, lam, states, lens_text=None, image=None, details=False, oc=None):
     """(words, counters): words (n, k, 8) uint32, all 8 words of every record of the call; counters: the deltas of succesRays,
     vignettedRays and totalInternalReflection.  details=True adds a dict: starts (n, 6) float32 and hero (planes (7, n), flags (n,)),
-    rows of an invalid hero zero."""
+    rows of an invalid hero zero.
+    oc: an updated oracle camera the caller owns (its history is the camera's: tests/update_sequences.py) instead of a fresh one behind
+    params, lens_text and image; it is not closed, and its lens table holds the d-line indices again on return."""
     s = np.ascontiguousarray(samples, np.float32)
     lam = np.ascontiguousarray(lam, np.float32)
     st = np.ascontiguousarray(states, np.uint32)
     n, k = lam.shape
     assert s.shape == (n, 4) and st.shape == (n, 4)
     ok_lam = valid(lam)
-    oc = oracle_camera(oracle_lib, params, lens_text, image)
+    own = oc is None
+    if own:
+        oc = oracle_camera(oracle_lib, params, lens_text, image)
     thin = params.get("lensModel", RAYTRACED) != RAYTRACED
     idx = Indices(oc, None if thin else dispersion)
     planes = np.zeros((7, n), np.float32)
@@ -126,7 +130,8 @@ def hero_reference(oracle_lib, params, dispersion, samples, lam, states, lens_te
             words[through, j, :6] = _bits(ends[ok] * np.float32(-1.0))        # zoic.cpp:1960-1961
             words[through, j, 6] = _bits(planes[6, through])
             words[through, j, 7] = flags[through]
-    oc.close()
+    if own:
+        oc.close()
     if details:
         return words, counters, dict(starts=starts, planes=planes, flags=flags)
     return words, counters
