@@ -17,7 +17,7 @@
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
  *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_create_rays_hero_device, zoic_create_ghost_rays_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
- *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian (and their _spectral forms), zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
+ *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian, zoic_pupil_bounds_device, zoic_pupil_bounds_point (and their _spectral forms), zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
  *   - No entry point changes the calling thread's current HIP device.
@@ -65,7 +65,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_ray_transmittance_device, zoic_camera_set_coatings and
  *      zoic_camera_get_coatings (the Fresnel transmittance of traced rays, with single-layer coatings).
  *      Added later without a new number (additive): zoic_create_ghost_rays_device and zoic_camera_get_ghost_pairs (ghost rays: the
- *      two-reflection paths through the lens with their Fresnel weights), ZOIC_GHOST_MAX_PAIRS and the ZOIC_GHOST_* flag macros. */
+ *      two-reflection paths through the lens with their Fresnel weights), ZOIC_GHOST_MAX_PAIRS and the ZOIC_GHOST_* flag macros.
+ *      Added later without a new number (additive): zoic_pupil_bounds_device, zoic_pupil_bounds_point and their _spectral forms
+ *      (pupil bounds: the lens area a scene point sees and the box of its blur spot), zoic_pupil_bounds and the ZOIC_PUPIL_* macros. */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -684,6 +686,57 @@ zoic_status zoic_trace_back_jacobian_spectral_device(zoic_camera *cam, uint64_t 
                                                      float *d_jacobian /* n x 12 */, void *stream);
 zoic_status zoic_trace_back_ray_jacobian_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm,
                                                   float *Ps /* [2] */, uint32_t *flags /* may be NULL */, float *J /* [12] */);
+
+/* ---- pupil bounds: the lens area and the blur spot of a scene point (opt-in; csrc/pupil_bounds.hpp has the full definition) ------
+ * The trace-back calls above leave the step before them to the caller: how lens points are drawn.  Drawn from the whole front element,
+ * almost every ray of a stopped-down or vignetted camera is refused at the stop.  These four calls answer, for a scene point P (the
+ * frame of the records, as zoic_project_point takes it): which part of the lens does P see, and how big is its blur spot on the sensor
+ * -- the circle of confusion with its cat's eye, and the vignetting.  Deterministic: no random number, no weight.
+ *   Aims     lattice x lattice points A, the cell centres of the square [-R, R]^2 across the axis: RAYTRACED on the front vertex plane
+ *            with R the front element's housing radius, THINLENS with useDof on the lens plane z = 0 with R = apertureRadius.
+ *            ax = (2 ix + 1 - lattice) R / lattice, ay likewise.  lattice is 8, 16 or 32.
+ *   Ray      origin = P, dir = P - A, taken back by zoic_trace_back_ray, spectral: by zoic_trace_back_ray_spectral at the point's wavelength.
+ *   Passing  an aim passes if its ray is traced back (ZOIC_TRACED_BACK) and, where a window (sx0, sy0, sx1, sy1) is given,
+ *            sx0 <= sx <= sx1 and sy0 <= sy <= sy1.  A NaN window bound passes nothing.  window = NULL: no window.
+ *   Record   aim: min ax, min ay, max ax, max ay over the passing aims, each side grown by one pitch 2 R / lattice and clamped to +-R.
+ *            screen: min sx, min sy, max sx, max sy over the passing aims, not grown: the box of the blur spot.
+ *            count: the passing aims; lattice: lattice^2, so that count / lattice x 4 R^2 is the pupil's area as seen from P.
+ *            flags: bit 0 (ZOIC_PUPIL_SOME) at least one aim passes; bits 16-31 the OR over the refused aims of
+ *            ZOIC_PUPIL_REFUSED(reason), reason a ZOIC_TRACE_BACK_* code, and 0 for an aim that traced back but landed outside the window.
+ *            With no aim passing, aim and screen are all +0.
+ *   Refused wholesale: lensModel NONE, THINLENS without useDof, a camera outside the geometric domain, a non-finite P, a P behind the front
+ *            element's cap, an invalid wavelength.  Not an error: count = 0 and the bit of that reason.
+ * The bounds are statements about the lattice, not a guarantee: every passing lattice aim lies in `aim`, but a sliver of pupil thinner
+ * than a pitch can lie outside the grown box (DESIGN 4.17 has the measured share).  Draw lens points in `aim`, trace each ray back as before
+ * (zoic_trace_back_jacobian_device gives the change of measure); how they are weighted stays the caller's.
+ * Every output is a minimum, a maximum, a count or an OR over the trace-back's own bits: the device calls and the host calls give the same
+ * record for the same point in every precision mode.
+ * d_points: n x 3 floats, device memory, 4-byte aligned; d_wavelengths: n f32 (nm), device memory; window: 4 floats of HOST memory, read
+ * during the call, or NULL; d_bounds: n records, device memory, 16-byte aligned.  Asynchronous on `stream`, with the threading contract of
+ * zoic_trace_back_rays_device; no record, no counter and no retry stream is touched.  ZOIC_ERR_NOT_UPDATED before an update;
+ * ZOIC_ERR_INVALID_ARGUMENT for a NULL, misaligned or non-device pointer or a lattice that is not 8, 16 or 32, before any launch;
+ * ZOIC_ERR_NO_DEVICE on a tables-only camera; n = 0 returns ZOIC_OK. */
+typedef struct zoic_pupil_bounds {
+    float aim[4];    /* min ax, min ay, max ax, max ay (cm), grown by a pitch and clamped */
+    float screen[4]; /* min sx, min sy, max sx, max sy */
+    uint32_t count;
+    uint32_t lattice;
+    uint32_t flags;
+    uint32_t reserved; /* 0 */
+} zoic_pupil_bounds; /* 48 bytes */
+#define ZOIC_PUPIL_SOME 0x1u
+#define ZOIC_PUPIL_OUTSIDE_WINDOW 0 /* the reason of an aim that traced back but landed outside the window */
+#define ZOIC_PUPIL_REFUSED(reason) (1u << (16 + (reason)))
+zoic_status zoic_pupil_bounds_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */, int lattice,
+                                     const float *window /* [4], host, may be NULL */, zoic_pupil_bounds *d_bounds /* n */, void *stream);
+zoic_status zoic_pupil_bounds_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */,
+                                              const float *d_wavelengths /* n */, int lattice, const float *window /* [4], host, may be NULL */,
+                                              zoic_pupil_bounds *d_bounds /* n */, void *stream);
+/* The host build of the same code for one point (works on a ZOIC_DEVICE_NONE camera). */
+zoic_status zoic_pupil_bounds_point(const zoic_camera *cam, const zoic_vec3 *Po, int lattice, const float *window /* [4] or NULL */,
+                                    zoic_pupil_bounds *bounds);
+zoic_status zoic_pupil_bounds_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, int lattice,
+                                             const float *window /* [4] or NULL */, zoic_pupil_bounds *bounds);
 
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins

@@ -62,6 +62,17 @@ RAY_DTYPE = [("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("dx", "<f4"), ("dy", 
              ("flags", "<u4")]
 
 
+class PupilBounds(C.Structure):   # zoic_pupil_bounds: one 48-byte record per scene point
+    _fields_ = [("aim", C.c_float * 4), ("screen", C.c_float * 4), ("count", C.c_uint32), ("lattice", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+PUPIL_BOUNDS_DTYPE = [("aim", "<f4", (4,)), ("screen", "<f4", (4,)), ("count", "<u4"), ("lattice", "<u4"), ("flags", "<u4"), ("reserved", "<u4")]
+# zoic_pupil_bounds.flags: bit 0, and the bit of an aim refused for `reason` (a TRACE_BACK reason; 0: outside the window)
+PUPIL_SOME = 0x1
+PUPIL_REASON_SHIFT = 16
+
+
 class FrameLaneInfo(C.Structure):
     _fields_ = [("device", C.c_int32), ("peer_access_to_root", C.c_int32), ("peer_access_from_root", C.c_int32), ("chunks", C.c_uint32),
                 ("rays", C.c_uint64), ("bytes_to_root", C.c_uint64)]
@@ -142,6 +153,10 @@ SYMBOLS = {
     "zoic_trace_back_ray_jacobian": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(C.c_float)]),
     "zoic_trace_back_jacobian_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zoic_trace_back_ray_jacobian_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(C.c_float)]),
+    "zoic_pupil_bounds_device": (C.c_int, [_vp, _u64, _vp, C.c_int, C.POINTER(C.c_float), _vp, _vp]),
+    "zoic_pupil_bounds_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, C.c_int, C.POINTER(C.c_float), _vp, _vp]),
+    "zoic_pupil_bounds_point": (C.c_int, [_vp, C.POINTER(Vec3), C.c_int, C.POINTER(C.c_float), C.POINTER(PupilBounds)]),
+    "zoic_pupil_bounds_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.c_int, C.POINTER(C.c_float), C.POINTER(PupilBounds)]),
     "zoic_project_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zoic_project_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),

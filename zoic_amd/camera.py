@@ -105,6 +105,45 @@ def solid_angle_measure(jac, dirs, basis=None):
     return (A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]) * (d * d).sum(1)
 
 
+def pupil_bounds_records(bounds):
+    """the (n,) structured array (_capi.PUPIL_BOUNDS_DTYPE) of the (n,12) float32 records ZoicCamera.pupil_bounds returns for device
+    points (a tensor is copied to the host; the caller has waited for its stream)"""
+    if _is_torch(bounds):
+        bounds = bounds.cpu().numpy()
+    a = np.ascontiguousarray(bounds)
+    if a.dtype == np.dtype(_capi.PUPIL_BOUNDS_DTYPE):
+        return a.reshape(-1)
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 12).view(_capi.PUPIL_BOUNDS_DTYPE).reshape(-1)
+
+
+def pupil_rays(points, bounds, u, aim_z=0.0):
+    """Rays from scene points towards their pupil boxes: (origins (n,3), dirs (n,3), pdf_area (n,)) float32, the rays to hand to
+    ZoicCamera.trace_back_jacobian.
+
+    points: (n,3) scene points; bounds: their pupil-bounds records (the structured array, or the (n,12) float32 records);
+    u: (n,2) numbers in [0,1)^2, the caller's own (this function draws nothing); aim_z: the z of the aims' plane
+    (ZoicCamera.pupil_square()[0]).  Aim i = (aim.min + u_i (aim.max - aim.min), aim_z): uniform in the point's `aim` box;
+    origins = points, dirs = points - aims (into the scene, as the trace-back wants), pdf_area = 1 / the box's area (per cm^2 on
+    the aims' plane), and 0 for a point with count = 0 (its dir aims at the axis and is refused as every other ray from there).
+
+    Pure host code, numpy only.  The box holds the lattice's passing aims, not exactly the pupil: a ray drawn in it is still traced
+    back and may be refused, and how the traced ones are weighted -- by pdf_area, the Jacobian, a filter -- is the caller's."""
+    b = pupil_bounds_records(bounds)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+    if not (len(b) == len(p) == len(u)):
+        raise ValueError("points, bounds and u must have one row per point")
+    lo, hi = b["aim"][:, 0:2], b["aim"][:, 2:4]
+    aims = np.empty_like(p)
+    aims[:, 0:2] = np.clip(lo + u * (hi - lo), lo, hi)
+    aims[:, 2] = np.float32(aim_z)
+    area = (hi[:, 0] - lo[:, 0]).astype(np.float64) * (hi[:, 1] - lo[:, 1]).astype(np.float64)
+    some = (b["count"] > 0) & (area > 0)
+    pdf = np.zeros(len(p), np.float32)
+    pdf[some] = (1.0 / area[some]).astype(np.float32)
+    return p, p - aims, pdf
+
+
 class PinnedArray:
     """A numpy array over page-locked host memory (zoic_host_alloc): buffers of this kind let create_rays' host path
     run as an asynchronous two-stream pipeline.  Keep the object alive as long as the array is used."""
@@ -656,6 +695,101 @@ class ZoicCamera:
             rays = rays["rays"]
         return self._backward_batch("rays", 8, self._lib.zoic_trace_back_jacobian_device, self._lib.zoic_trace_back_jacobian_spectral_device,
                                     rays, wavelengths, out, flags, stream, jacobian, True)
+
+    @staticmethod
+    def _pupil_window(window):
+        """the window argument of the pupil-bounds calls: None, or four floats (sx0, sy0, sx1, sy1) of host memory"""
+        if window is None:
+            return None
+        w = [float(v) for v in window]
+        if len(w) != 4:
+            raise ValueError("window must be (sx0, sy0, sx1, sy1)")
+        return (C.c_float * 4)(*w)
+
+    def pupil_square(self):
+        """(z, R) of the square [-R, R]^2 the pupil-bounds aims lie in, in the frame of the records: RAYTRACED the front vertex plane
+        and the front element's housing radius, THINLENS the lens plane z = 0 and apertureRadius (csrc/pupil_bounds.hpp, in the
+        table's own f32 operations).  4 R^2 count / lattice of a pupil-bounds record is the pupil's area as seen from its point;
+        z is the aim_z of pupil_rays."""
+        info, f32 = self.info(), np.float32
+        if int(self.params["lensModel"]) != RAYTRACED:
+            a = f32(info["apertureRadius"])
+            return 0.0, float(np.sqrt(f32(a * a)))
+        n = int(info["lensCount"])
+        th = info["elements"][:n, 1].astype(f32)
+        front = th[0]
+        for t in th[1:]:
+            front = f32(front + t)
+        lim = (float(info["elements"][n - 1, 3]) * 0.5) ** 2
+        h2 = f32(lim)
+        if float(h2) > lim:
+            h2 = np.nextafter(h2, f32(-np.inf))
+        ua = f32(info["userApertureRadius"])
+        if info["apertureElement"] == n - 1 and f32(ua * ua) < h2:
+            h2 = f32(ua * ua)
+        return -float(front), float(np.sqrt(h2))
+
+    def pupil_bounds_point(self, Po, lattice=16, window=None, wavelength=None):
+        """Pupil bounds of one scene point on the host (zoic_pupil_bounds_point): a dict with aim (4,) float32 = (min ax, min ay, max ax,
+        max ay), the box of the lattice aims whose rays from Po are traced back, grown by a pitch; screen (4,) float32 = (min sx, min sy,
+        max sx, max sy), the box of the blur spot; count, lattice (= lattice^2) and flags (csrc/pupil_bounds.hpp).  Po in the frame of
+        the records; lattice 8, 16 or 32; window: None or (sx0, sy0, sx1, sy1), the film window an aim's sample must land in.  Works
+        on a tables-only camera (device=-1).
+        wavelength (nm): the trace at that wavelength (zoic_pupil_bounds_point_spectral)."""
+        po = _capi.Vec3(*[float(v) for v in Po])
+        b = _capi.PupilBounds()
+        w = self._pupil_window(window)
+        if wavelength is not None:
+            self._check(self._lib.zoic_pupil_bounds_point_spectral(self._h, C.byref(po), float(wavelength), int(lattice), w, C.byref(b)))
+        else:
+            self._check(self._lib.zoic_pupil_bounds_point(self._h, C.byref(po), int(lattice), w, C.byref(b)))
+        return dict(aim=np.array(b.aim[:], np.float32), screen=np.array(b.screen[:], np.float32), count=int(b.count), lattice=int(b.lattice),
+                    flags=int(b.flags))
+
+    def pupil_bounds(self, points, lattice=16, window=None, wavelengths=None, out=None, stream=None):
+        """Pupil bounds of (n,3) float32 scene points (zoic_pupil_bounds_device): for each point the box of the lens it sees and the box
+        of its blur spot, from a lattice x lattice grid of aims on the front element traced back from the point (csrc/pupil_bounds.hpp).
+
+        numpy in  -> the points are copied to the camera's device through torch, the call waits and returns an (n,) structured array
+                     (_capi.PUPIL_BOUNDS_DTYPE: aim (4,), screen (4,), count, lattice, flags, reserved); out must be None there.
+        torch device tensor in -> asynchronous on `stream` (default: torch's current stream); returns the records as an (n,12) float32
+                     device tensor (columns 0-3 aim, 4-7 screen, 8-11 the bits of count, lattice, flags, reserved: view them as int32);
+                     out: an optional tensor of that kind to write into.  pupil_bounds_records(t) turns it into the structured array.
+        lattice: 8, 16 or 32.  window: None or (sx0, sy0, sx1, sy1).
+        wavelengths: (n,) float32 (nm), numpy with numpy points, a device tensor with device points (zoic_pupil_bounds_spectral_device)."""
+        import torch
+        w = self._pupil_window(window)
+        if not _is_torch(points):
+            if out is not None:
+                raise ValueError("out is for torch points")
+            if wavelengths is not None and _is_torch(wavelengths):
+                raise TypeError("numpy points need numpy wavelengths")
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("points must be (n, 3)")
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                self._check(self._lib.zoic_pupil_bounds_device(self._h, a.shape[0], None, int(lattice), w, None, None))
+            dev = torch.device("cuda", self.device)
+            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            res = self.pupil_bounds(torch.from_numpy(a).to(dev), lattice, window, tw)
+            torch.cuda.synchronize(dev)
+            return pupil_bounds_records(res)
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
+            raise ValueError("points must be a contiguous (n,3) float32 device tensor")
+        if points.device.index != self.device:
+            raise ValueError("points live on cuda:%s but this camera is bound to device %d" % (points.device.index, self.device))
+        n = points.shape[0]
+        if out is None:
+            out = torch.empty((n, 12), dtype=torch.float32, device=points.device)
+        if tuple(out.shape) != (n, 12) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
+            raise ValueError("out must be a contiguous (n,12) float32 tensor on the points' device")
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream)
+        if wavelengths is not None:
+            lam = self._wavelength_tensor(wavelengths, n, points)
+            self._check(self._lib.zoic_pupil_bounds_spectral_device(self._h, n, points.data_ptr(), lam.data_ptr(), int(lattice), w, out.data_ptr(), st))
+        else:
+            self._check(self._lib.zoic_pupil_bounds_device(self._h, n, points.data_ptr(), int(lattice), w, out.data_ptr(), st))
+        return out
 
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
         """inputs: (n,7) float32 AtCameraInput rows -> (n,21) float32 AtCameraOutput rows (weight initialised to 1).

@@ -42,6 +42,7 @@
 #include "backward_spectral.hpp"
 #include "traceback.hpp"
 #include "traceback_jacobian.hpp"
+#include "pupil_bounds.hpp"
 #include "ghost.hpp"
 #include "transmittance.hpp"
 #include "lens_system.hpp"
@@ -2204,6 +2205,60 @@ zoic_status zoic_trace_back_jacobian_spectral_device(zoic_camera *cam, uint64_t 
                               return launch_trace_back_jacobian_spectral(cam->traceBack, backward_dispersion(cam), d_rays, d_wavelengths, n,
                                                                          d_screen, d_flags, d_jacobian, stream);
                           });
+}
+
+// the lattice and the window of the four pupil-bounds calls (window NULL: none)
+static zoic_status pupil_arguments(int lattice, const float *window, PupilWindow &W)
+{
+    if (!pupil_lattice_valid(lattice)) return fail(ZOIC_ERR_INVALID_ARGUMENT, "lattice must be 8, 16 or 32");
+    W = window ? PupilWindow{window[0], window[1], window[2], window[3]} : PupilWindow{};
+    return ZOIC_OK;
+}
+
+static void put_pupil_bounds(zoic_pupil_bounds *out, const PupilBounds &B)
+{
+    static_assert(sizeof(zoic_pupil_bounds) == 48 && sizeof(PupilBounds) == 48, "the pupil-bounds record is 48 bytes");
+    std::memcpy(out, &B, sizeof B);
+}
+
+zoic_status zoic_pupil_bounds_point(const zoic_camera *cam, const zoic_vec3 *Po, int lattice, const float *window, zoic_pupil_bounds *bounds)
+{
+    PupilWindow W;
+    if (zoic_status s = pupil_arguments(lattice, window, W)) return s;
+    return backward_item(cam, Po && bounds, "Po and bounds", nullptr, [&] {
+        put_pupil_bounds(bounds, pupil_bounds_point(cam->traceBack, lattice, Po->x, Po->y, Po->z, W));
+        return 0u;
+    });
+}
+
+zoic_status zoic_pupil_bounds_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, int lattice, const float *window,
+                                             zoic_pupil_bounds *bounds)
+{
+    PupilWindow W;
+    if (zoic_status s = pupil_arguments(lattice, window, W)) return s;
+    return backward_item(cam, Po && bounds, "Po and bounds", nullptr, [&] {
+        put_pupil_bounds(bounds, pupil_bounds_point_spectral(cam->traceBack, backward_dispersion(cam), wavelength_nm, lattice, Po->x, Po->y, Po->z, W));
+        return 0u;
+    });
+}
+
+zoic_status zoic_pupil_bounds_device(zoic_camera *cam, uint64_t n, const float *d_points, int lattice, const float *window,
+                                     zoic_pupil_bounds *d_bounds, void *stream)
+{
+    PupilWindow W;
+    if (zoic_status s = pupil_arguments(lattice, window, W)) return s;
+    return backward_batch(cam, n, {{"d_points", d_points, 4}, {"d_bounds", d_bounds, 16}},
+                          [&] { return launch_pupil_bounds(cam->traceBack, d_points, n, lattice, W, d_bounds, stream); });
+}
+
+zoic_status zoic_pupil_bounds_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points, const float *d_wavelengths, int lattice,
+                                              const float *window, zoic_pupil_bounds *d_bounds, void *stream)
+{
+    PupilWindow W;
+    if (zoic_status s = pupil_arguments(lattice, window, W)) return s;
+    return backward_batch(cam, n, {{"d_points", d_points, 4}, {"d_wavelengths", d_wavelengths, 4}, {"d_bounds", d_bounds, 16}}, [&] {
+        return launch_pupil_bounds_spectral(cam->traceBack, backward_dispersion(cam), d_points, d_wavelengths, n, lattice, W, d_bounds, stream);
+    });
 }
 
 zoic_status zoic_host_alloc(size_t bytes, void **out)
