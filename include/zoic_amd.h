@@ -17,7 +17,7 @@
  *   - zoic_camera_create / _update / _destroy / _set_* / _reset_counters: one thread at a time per camera, and no
  *     ray call of that camera running on another thread.  (_update and _destroy wait for launches still queued.)
  *   - zoic_create_rays_device / _host / _arnold / _arnold_differentials / _device_resident, zoic_ray_differentials_device, zoic_ray_differentials_spectral_device, zoic_create_rays_hero_device, zoic_create_ghost_rays_device, zoic_camera_create_ray, zoic_camera_create_rays_tile, zoic_tile_submit / _wait /
- *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian, zoic_pupil_bounds_device, zoic_pupil_bounds_point (and their _spectral forms), zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
+ *     _done (one tile per thread), zoic_camera_reverse_ray, zoic_project_points_device, zoic_project_point, zoic_trace_back_rays_device, zoic_trace_back_ray, zoic_trace_back_jacobian_device, zoic_trace_back_ray_jacobian, zoic_pupil_bounds_device, zoic_pupil_bounds_point, zoic_splat_points_device, zoic_splat_point (and their _spectral forms), zoic_camera_get_counters, zoic_camera_set_wait_mode: any number of host threads on one camera at once.  Each call works on private
  *     scratch and private HIP streams and waits only for its own work; results do not depend on the interleaving
  *     (batched calls key every ray's retry stream by its global ray index, the per-sample call by its tid).
  *   - No entry point changes the calling thread's current HIP device.
@@ -67,7 +67,9 @@ extern "C" {
  *      Added later without a new number (additive): zoic_create_ghost_rays_device and zoic_camera_get_ghost_pairs (ghost rays: the
  *      two-reflection paths through the lens with their Fresnel weights), ZOIC_GHOST_MAX_PAIRS and the ZOIC_GHOST_* flag macros.
  *      Added later without a new number (additive): zoic_pupil_bounds_device, zoic_pupil_bounds_point and their _spectral forms
- *      (pupil bounds: the lens area a scene point sees and the box of its blur spot), zoic_pupil_bounds and the ZOIC_PUPIL_* macros. */
+ *      (pupil bounds: the lens area a scene point sees and the box of its blur spot), zoic_pupil_bounds and the ZOIC_PUPIL_* macros.
+ *      Added later without a new number (additive): zoic_splat_points_device, zoic_splat_point and their _spectral forms (lens splats:
+ *      scene points through drawn aims in their pupil boxes to the screen, with two measures), zoic_splat and ZOIC_SPLAT_NO_BOX. */
 #define ZOIC_AMD_ABI_VERSION 5
 
 typedef enum zoic_status {
@@ -737,6 +739,53 @@ zoic_status zoic_pupil_bounds_point(const zoic_camera *cam, const zoic_vec3 *Po,
                                     zoic_pupil_bounds *bounds);
 zoic_status zoic_pupil_bounds_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, float wavelength_nm, int lattice,
                                              const float *window /* [4] or NULL */, zoic_pupil_bounds *bounds);
+
+/* ---- lens splats: a scene point through drawn aims in its pupil box to the screen (opt-in; csrc/splat.hpp has the full definition) --
+ * The device call that puts the backward calls together for a point splatter or a light tracer: from each scene point P and its
+ * pupil-bounds record B (as zoic_pupil_bounds_device wrote it, read in place), m rays towards m aims in B's `aim` box, each traced back
+ * with its Jacobian, of which the four numbers a splatter keeps are written.  Deterministic: the caller brings the numbers u, nothing
+ * is drawn, weighted or accumulated here.
+ *   Empty box  B.count == 0 or ZOIC_PUPIL_SOME clear: nothing is traced; the record is all +0 but flags = ZOIC_SPLAT_NO_BOX (bit 12, a
+ *              bit the trace-back's flag word leaves free).
+ *   Aim        ax = aim[0] + u0 (aim[2] - aim[0]), then clamped to [aim[0], aim[2]] by two selects; ay likewise with aim[1], aim[3], u1:
+ *              uniform in the box for u uniform in [0, 1)^2, on the box's edge for u outside.  A NaN u gives a NaN aim, which the trace
+ *              refuses (ZOIC_TRACE_BACK_NON_FINITE).  The aims' plane is that of the pupil bounds.
+ *   Ray        origin = P, dir = P - A, taken back by zoic_trace_back_ray_jacobian (spectral: zoic_trace_back_ray_jacobian_spectral at the
+ *              point's wavelength): sx, sy and flags are that call's bits.
+ *   Measures   for a traced ray (ZOIC_TRACED_BACK), +0 otherwise, with J that call's Jacobian:
+ *              area  = J[3] J[10] - J[4] J[9] = det d(sx, sy) / d(ax, ay) at fixed P: screen area per cm^2 of the aims' plane.  With u
+ *                      uniform, the density of the aims is 1 / |box| per cm^2.
+ *              angle = area |dir|^3 / dir.z = dPs / d(omega), the value of solid_angle_measure(J, dir) (dir.z < 0: the sign is -area's).
+ *              An entry that is not a number is the one quiet NaN 0x7fc00000.
+ *   Record     ax, ay are written for every ray that was traced or refused by the trace, and are +0 with ZOIC_SPLAT_NO_BOX.
+ *   m          m >= 1 aims per point, point-major: splat i = p m + j reads point p, bounds p, u[2 i], u[2 i + 1] and writes record i.
+ * Every operation is a single correctly rounded f32 operation in a fixed order: the device calls and the host calls give the same
+ * record for the same item in every precision mode.
+ * d_points: n x 3 floats, device memory, 4-byte aligned; d_bounds: n records, device memory, 16-byte aligned; d_u: n x m x 2 floats,
+ * device memory, 8-byte aligned; d_wavelengths: n f32 (nm), device memory; d_splats: n x m records, device memory, 16-byte aligned.
+ * Asynchronous on `stream`, with the threading contract of zoic_pupil_bounds_device; no counter and no retry stream is touched.
+ * ZOIC_ERR_NOT_UPDATED before an update; ZOIC_ERR_INVALID_ARGUMENT for m = 0 with n > 0, for n m >= 2^58 and for a NULL, misaligned or
+ * non-device pointer, before any launch: d_splats is not written; ZOIC_ERR_NO_DEVICE on a tables-only camera; n = 0 returns ZOIC_OK. */
+typedef struct zoic_splat {
+    float sx, sy;      /* the screen sample */
+    float ax, ay;      /* the aim (cm) on the pupil bounds' plane */
+    float area;        /* det d(sx, sy) / d(ax, ay) */
+    float angle;       /* dPs / d(omega) */
+    uint32_t flags;    /* the trace-back's flag word, or ZOIC_SPLAT_NO_BOX */
+    uint32_t reserved; /* 0 */
+} zoic_splat; /* 32 bytes */
+#define ZOIC_SPLAT_NO_BOX 0x1000u
+zoic_status zoic_splat_points_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */, const zoic_pupil_bounds *d_bounds /* n */,
+                                     uint32_t m, const float *d_u /* n x m x 2 */, zoic_splat *d_splats /* n x m */, void *stream);
+zoic_status zoic_splat_points_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */,
+                                              const zoic_pupil_bounds *d_bounds /* n */, const float *d_wavelengths /* n */, uint32_t m,
+                                              const float *d_u /* n x m x 2 */, zoic_splat *d_splats /* n x m */, void *stream);
+/* The host build of the same code for one point and its m aims (works on a ZOIC_DEVICE_NONE camera).  u and splats: host
+ * memory, 4-byte aligned.  m = 0, a NULL pointer and a misaligned u or splats are ZOIC_ERR_INVALID_ARGUMENT: splats is not written. */
+zoic_status zoic_splat_point(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, uint32_t m,
+                             const float *u /* m x 2 */, zoic_splat *splats /* m */);
+zoic_status zoic_splat_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, float wavelength_nm,
+                                      uint32_t m, const float *u /* m x 2 */, zoic_splat *splats /* m */);
 
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins

