@@ -60,6 +60,48 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _records(rays):
+    """the record buffer of a `rays` argument: the dict of a create_rays call stands for its "rays" entry"""
+    return rays["rays"] if isinstance(rays, dict) else rays
+
+
+def _ray_views(rays):
+    """the strided views a forward call on device tensors returns beside its (n,8) or (n,k,8) float32 record tensor"""
+    import torch
+    planes = rays[..., 0:7].movedim(-1, 0)
+    return dict(origin=planes[0:3], dir=planes[3:6], weight=planes[6], planes=planes, flags=rays[..., 7].view(torch.int32))
+
+
+def _host_records(rays):
+    """the structured zoic_ray records, shape (n,) or (n,k), of a record tensor whose stream has been waited for"""
+    a = np.ascontiguousarray(rays.cpu().numpy())
+    return a.view(_capi.RAY_DTYPE).reshape(a.shape[:-1])
+
+
+# what the numpy half of a batch call makes of its further arrays before they go to the device (n: the number of items)
+def _f32(a, n):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _f32_flat(a, n):
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+
+
+def _hero_wavelengths(a, n):
+    w = np.ascontiguousarray(a, dtype=np.float32)
+    if w.ndim != 2 or w.shape[0] != n:
+        raise ValueError("wavelengths must be (n, k)")
+    return w
+
+
+def _rng_words(a, n):
+    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
+
+
+def _bounds_floats(a, n):
+    return np.ascontiguousarray(pupil_bounds_records(a)).view(np.float32).reshape(-1, 12)
+
+
 def rays_to_dict(rays):
     """(n,) zoic_ray records -> convenience views (planes are copies: ox oy oz dx dy dz weight)."""
     planes = np.stack([rays[k] for k in ("ox", "oy", "oz", "dx", "dy", "dz", "weight")]).astype(np.float32, copy=False)
@@ -282,6 +324,82 @@ class ZoicCamera:
     def __exit__(self, *a):
         self.close()
 
+    # ------------------------------------------------------------------ arguments of the batch calls
+    def _device_tensor(self, name, t, shape, ints=False, missing=ValueError):
+        """t, if it is what every tensor argument of a batch call must be: a torch tensor (else `missing` is raised: TypeError for
+        wavelengths), float32 (ints: int32 or uint32), of exactly `shape` (None: a free dimension), contiguous, on the camera's
+        device.  Anything else is a ValueError: the kernels read and write through the bare pointer."""
+        import torch
+        if not _is_torch(t):
+            raise missing("%s must be a torch tensor on cuda:%d, as the items are (numpy arrays go with numpy items)" % (name, self.device))
+        s = t.shape
+        if (t.dtype not in ((torch.int32, torch.uint32) if ints else (torch.float32,)) or not t.is_contiguous() or not t.is_cuda
+                or t.device.index != self.device
+                or (s != shape and (len(s) != len(shape) or any(w is not None and w != g for w, g in zip(shape, s))))):
+            raise ValueError("%s must be a contiguous (%s) %s tensor on cuda:%d, this camera's device; it is a %s(%s) %s tensor on %s"
+                             % (name, ",".join("*" if w is None else str(w) for w in shape), "int32/uint32" if ints else "float32", self.device,
+                                "" if t.is_contiguous() else "strided ", ",".join(str(g) for g in s), str(t.dtype).replace("torch.", ""), t.device))
+        return t
+
+    def _result(self, name, t, shape, like, ints=False):
+        """the tensor a batch call writes into: a new one on like's device, or the caller's, checked"""
+        if t is None:
+            import torch
+            return torch.empty(shape, dtype=torch.int32 if ints else torch.float32, device=like.device)
+        return self._device_tensor(name, t, shape, ints)
+
+    def _rng_pointer(self, rng_states, n):
+        return None if rng_states is None else self._device_tensor("rng_states", rng_states, (n, 4), ints=True).data_ptr()
+
+    def _traced(self, n, rays, rng_states, lead=None):
+        """(the record tensor, the rng_states pointer) of a call that follows a forward call on n samples: rays -- its records, or
+        its dict, of shape lead + (8,) (None: (n,)) -- and rng_states as that call was given them"""
+        return self._device_tensor("rays", _records(rays), ((n,) if lead is None else lead) + (8,)), self._rng_pointer(rng_states, n)
+
+    def _wavelength_pointer(self, wavelengths, n):
+        return None if wavelengths is None else self._device_tensor("wavelengths", wavelengths, (n,), missing=TypeError).data_ptr()
+
+    def _stream(self, stream):
+        """the stream argument of a device call: the caller's handle, or torch's current stream on the camera's device"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        return C.c_void_p(stream)
+
+    def _spectral_or(self, dline, spectral, wavelength, head, tail):
+        """dline(h, *head, *tail), or with a wavelength (a float, or the pointer of one per item) spectral(h, *head, wavelength, *tail):
+        how every d-line entry point of the C-ABI and its spectral twin take their arguments"""
+        if wavelength is None:
+            self._check(dline(self._h, *head, *tail))
+        else:
+            self._check(spectral(self._h, *head, wavelength, *tail))
+
+    def _through_device(self, what, width, items, others, results, probe, half):
+        """The numpy half of a batch call: what the torch half `half` returns for the arrays copied to the camera's device, complete
+        (the device has been waited for); the caller turns it into numpy.
+
+        items: the (n, width) float32 `what` (width 8: (n,) zoic_ray records too); others: (name, array or None, normaliser) of the
+        further arrays; results: name -> the caller's result buffer, which must be None here; probe(*host arrays): the library call
+        with no pointers that reports a tables-only camera (ZOIC_ERR_NO_DEVICE); half(*device tensors)."""
+        if any(r is not None for r in results.values()):
+            raise ValueError("%s are for torch %s" % (", ".join(results), what))
+        if any(_is_torch(a) for _, a, _ in others):
+            raise TypeError("numpy %s need numpy %s" % (what, ", ".join(name for name, _, _ in others)))
+        a = np.asarray(items)
+        if width == 8 and a.dtype == np.dtype(_capi.RAY_DTYPE):
+            a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError("%s must be (n, %d)%s" % (what, width, " float32 or (n,) zoic_ray records" if width == 8 else ""))
+        host = [a] + [None if v is None else norm(v, a.shape[0]) for _, v, norm in others]
+        if self.device < 0:
+            self._check(probe(*host))
+        import torch
+        dev = torch.device("cuda", self.device)
+        res = half(*[None if v is None else torch.from_numpy(v).to(dev) for v in host])
+        torch.cuda.synchronize(dev)
+        return res
+
     # ------------------------------------------------------------------ node_update
     def set_bokeh_image(self, pixels):
         """pixels: (H, W, C>=3) float32 -- what AiTextureLoad would return for bokehPath (zoic.cpp:176-186)."""
@@ -346,10 +464,14 @@ class ZoicCamera:
                      with numpy samples a numpy array: samples, wavelengths and rng_states are copied to the camera's device through
                      torch, the call waits for the records and returns the numpy dict (out must be None there).
         """
-        if wavelengths is not None:
-            return self._create_rays_spectral(samples, wavelengths, rng_states, ray_index_base, out, stream)
         if _is_torch(samples):
-            return self._create_rays_torch(samples, rng_states, ray_index_base, out, stream)
+            return self._create_rays_torch(samples, wavelengths, False, rng_states, ray_index_base, out, stream)
+        if wavelengths is not None:
+            res = self._through_device(
+                "samples", 4, samples, [("wavelengths", wavelengths, _f32_flat), ("rng_states", rng_states, _rng_words)], dict(out=out),
+                lambda s, w, r: self._lib.zoic_create_rays_spectral_device(self._h, len(s), None, None, None, int(ray_index_base), None, None),
+                lambda s, w, r: self._create_rays_torch(s, w, False, r, ray_index_base, None, None))
+            return rays_to_dict(_host_records(res["rays"]))
         s = np.ascontiguousarray(samples, dtype=np.float32)
         if s.ndim != 2 or s.shape[1] != 4:
             raise ValueError("samples must be (n, 4)")
@@ -357,7 +479,7 @@ class ZoicCamera:
         if out is not None:   # caller-owned (e.g. pinned) record array
             rays = out
             if rays.dtype != np.dtype(_capi.RAY_DTYPE) or rays.shape != (n,) or not rays.flags.c_contiguous:
-                raise ValueError("out must be a contiguous (n,) array of zoic_ray records")
+                raise ValueError("out must be an (n,) C-contiguous array of zoic_ray records")
         else:
             rays = np.empty(n, dtype=_capi.RAY_DTYPE)
         rs_ptr = None
@@ -369,76 +491,22 @@ class ZoicCamera:
         self._check(self._lib.zoic_create_rays_host(self._h, n, s.ctypes.data, rs_ptr, int(ray_index_base), rays.ctypes.data))
         return rays_to_dict(rays)
 
-    def _create_rays_torch(self, samples, rng_states, ray_index_base, out, stream):
-        import torch
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous():
-            raise ValueError("samples must be a contiguous (n,4) float32 tensor")
-        if not samples.is_cuda:
-            raise ValueError("torch samples must live on the GPU (use numpy for host buffers)")
-        if samples.device.index != self.device:
-            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
-        n = samples.shape[0]
-        if out is None:
-            out = dict(rays=torch.empty((n, 8), dtype=torch.float32, device=samples.device))
-        rays = out["rays"]
-        if rays.device != samples.device:
-            raise ValueError("out['rays'] must live on the samples' device")
-        rs_ptr = None
-        if rng_states is not None:
-            if rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4):
-                raise ValueError("rng_states must be (n,4) int32/uint32 on the device")
-            rs_ptr = rng_states.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
-        self._check(self._lib.zoic_create_rays_device(self._h, n, samples.data_ptr(), rs_ptr, int(ray_index_base),
-                                                      rays.data_ptr(), C.c_void_p(st)))
-        out.update(origin=rays[:, 0:3].t(), dir=rays[:, 3:6].t(), weight=rays[:, 6], planes=rays[:, 0:7].t(),
-                   flags=rays[:, 7].view(torch.int32))
-        return out
-
-    def _create_rays_spectral(self, samples, wavelengths, rng_states, ray_index_base, out, stream):
-        import torch
-        if not _is_torch(samples):
-            if _is_torch(wavelengths) or (rng_states is not None and _is_torch(rng_states)):
-                raise TypeError("numpy samples need numpy wavelengths and rng_states")
-            if out is not None:
-                raise ValueError("out is for torch samples")
-            s = np.ascontiguousarray(samples, dtype=np.float32)
-            if s.ndim != 2 or s.shape[1] != 4:
-                raise ValueError("samples must be (n, 4)")
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                self._check(self._lib.zoic_create_rays_spectral_device(self._h, s.shape[0], None, None, None, int(ray_index_base), None, None))
-            dev = torch.device("cuda", self.device)
-            ts = torch.from_numpy(s).to(dev)
-            tw = torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            tr = None if rng_states is None else torch.from_numpy(np.ascontiguousarray(rng_states, dtype=np.uint32).view(np.int32)).to(dev)
-            res = self._create_rays_spectral(ts, tw, tr, ray_index_base, None, None)
-            torch.cuda.synchronize(dev)
-            rays = np.ascontiguousarray(res["rays"].cpu().numpy()).view(_capi.RAY_DTYPE).reshape(-1)
-            return rays_to_dict(rays)
-        if not _is_torch(wavelengths):
-            raise TypeError("torch samples need a torch wavelength tensor")
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
-            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
-        if samples.device.index != self.device:
-            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
-        n = samples.shape[0]
-        if wavelengths.dtype != torch.float32 or tuple(wavelengths.shape) != (n,) or not wavelengths.is_contiguous() or wavelengths.device != samples.device:
-            raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the samples' device")
-        if out is None:
-            out = dict(rays=torch.empty((n, 8), dtype=torch.float32, device=samples.device))
-        rays = out["rays"]
-        if rays.device != samples.device:
-            raise ValueError("out['rays'] must live on the samples' device")
-        rs_ptr = None
-        if rng_states is not None:
-            if rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4):
-                raise ValueError("rng_states must be (n,4) int32/uint32 on the device")
-            rs_ptr = rng_states.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
-        self._check(self._lib.zoic_create_rays_spectral_device(self._h, n, samples.data_ptr(), wavelengths.data_ptr(), rs_ptr,
-                                                               int(ray_index_base), rays.data_ptr(), C.c_void_p(st)))
-        out.update(origin=rays[:, 0:3].t(), dir=rays[:, 3:6].t(), weight=rays[:, 6], planes=rays[:, 0:7].t(),
-                   flags=rays[:, 7].view(torch.int32))
+    def _create_rays_torch(self, samples, wavelengths, hero, rng_states, ray_index_base, out, stream):
+        """the torch half of create_rays (wavelengths None or (n,)) and of create_rays_hero (hero: wavelengths (n,k))"""
+        n = self._device_tensor("samples", samples, (None, 4)).shape[0]
+        lead = (n,)
+        if hero or wavelengths is not None:
+            lead = tuple(self._device_tensor("wavelengths", wavelengths, (n, None) if hero else (n,), missing=TypeError).shape)
+        out = dict(rays=None) if out is None else out
+        rays = out["rays"] = self._result("out['rays']", out["rays"], lead + (8,), samples)
+        tail = (self._rng_pointer(rng_states, n), int(ray_index_base), rays.data_ptr(), self._stream(stream))
+        if wavelengths is None:
+            self._check(self._lib.zoic_create_rays_device(self._h, n, samples.data_ptr(), *tail))
+        elif hero:
+            self._check(self._lib.zoic_create_rays_hero_device(self._h, n, lead[1], samples.data_ptr(), wavelengths.data_ptr(), *tail))
+        else:
+            self._check(self._lib.zoic_create_rays_spectral_device(self._h, n, samples.data_ptr(), wavelengths.data_ptr(), *tail))
+        out.update(_ray_views(rays))
         return out
 
     def create_rays_hero(self, samples, wavelengths, rng_states=None, ray_index_base=0, out=None, stream=None):
@@ -453,63 +521,26 @@ class ZoicCamera:
         numpy in  -> samples, wavelengths and rng_states are copied to the camera's device through torch, the call waits and returns
                      numpy arrays of those shapes with a structured (n, k) rays (out must be None there).
         """
-        import torch
-        if not _is_torch(samples):
-            if _is_torch(wavelengths) or (rng_states is not None and _is_torch(rng_states)):
-                raise TypeError("numpy samples need numpy wavelengths and rng_states")
-            if out is not None:
-                raise ValueError("out is for torch samples")
-            s = np.ascontiguousarray(samples, dtype=np.float32)
-            if s.ndim != 2 or s.shape[1] != 4:
-                raise ValueError("samples must be (n, 4)")
-            w = np.ascontiguousarray(wavelengths, dtype=np.float32)
-            if w.ndim != 2 or w.shape[0] != s.shape[0]:
-                raise ValueError("wavelengths must be (n, k)")
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                self._check(self._lib.zoic_create_rays_hero_device(self._h, s.shape[0], w.shape[1], None, None, None, int(ray_index_base), None, None))
-            dev = torch.device("cuda", self.device)
-            tr = None if rng_states is None else torch.from_numpy(np.ascontiguousarray(rng_states, dtype=np.uint32).view(np.int32)).to(dev)
-            res = self.create_rays_hero(torch.from_numpy(s).to(dev), torch.from_numpy(w).to(dev), tr, ray_index_base, None, None)
-            torch.cuda.synchronize(dev)
-            rays = np.ascontiguousarray(res["rays"].cpu().numpy()).view(_capi.RAY_DTYPE).reshape(w.shape)
-            return hero_rays_to_dict(rays)
-        if not _is_torch(wavelengths):
-            raise TypeError("torch samples need a torch wavelength tensor")
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
-            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
-        if samples.device.index != self.device:
-            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
-        n = samples.shape[0]
-        if (wavelengths.dtype != torch.float32 or wavelengths.dim() != 2 or wavelengths.shape[0] != n or not wavelengths.is_contiguous()
-                or wavelengths.device != samples.device):
-            raise ValueError("wavelengths must be a contiguous (n,k) float32 tensor on the samples' device")
-        k = wavelengths.shape[1]
-        if out is None:
-            out = dict(rays=torch.empty((n, k, 8), dtype=torch.float32, device=samples.device))
-        rays = out["rays"]
-        if tuple(rays.shape) != (n, k, 8) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
-            raise ValueError("out['rays'] must be a contiguous (n,k,8) float32 tensor on the samples' device")
-        rs_ptr = None
-        if rng_states is not None:
-            if (not _is_torch(rng_states) or rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4)
-                    or not rng_states.is_contiguous() or rng_states.device != samples.device):
-                raise ValueError("rng_states must be a contiguous (n,4) int32/uint32 tensor on the samples' device")
-            rs_ptr = rng_states.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
-        self._check(self._lib.zoic_create_rays_hero_device(self._h, n, k, samples.data_ptr(), wavelengths.data_ptr(), rs_ptr,
-                                                           int(ray_index_base), rays.data_ptr(), C.c_void_p(st)))
-        out.update(origin=rays[:, :, 0:3].permute(2, 0, 1), dir=rays[:, :, 3:6].permute(2, 0, 1), weight=rays[:, :, 6],
-                   planes=rays[:, :, 0:7].permute(2, 0, 1), flags=rays[:, :, 7].view(torch.int32))
-        return out
+        if _is_torch(samples):
+            return self._create_rays_torch(samples, wavelengths, True, rng_states, ray_index_base, out, stream)
+        res = self._through_device(
+            "samples", 4, samples, [("wavelengths", wavelengths, _hero_wavelengths), ("rng_states", rng_states, _rng_words)], dict(out=out),
+            lambda s, w, r: self._lib.zoic_create_rays_hero_device(self._h, len(s), w.shape[1], None, None, None, int(ray_index_base), None, None),
+            lambda s, w, r: self._create_rays_torch(s, w, True, r, ray_index_base, None, None))
+        return hero_rays_to_dict(_host_records(res["rays"]))
 
     def dispersion(self):
         """The lens's dispersion table (zoic_camera_get_dispersion), trace order (rear first): dict of float32 arrays ior_d, abbe and
         cauchy_b (nm^2).  Works on a tables-only camera (device=-1)."""
-        n = self._lib.zoic_camera_get_dispersion(self._h, 0, None, None, None)
+        return self._table(self._lib.zoic_camera_get_dispersion, np.float32, ("ior_d", "abbe", "cauchy_b"))
+
+    def _table(self, getter, dtype, names):
+        """the arrays of a table getter of the C-ABI, by name: ask for the size (no pointers), then have one array per name filled"""
+        n = getter(self._h, 0, *[None] * len(names))
         if n < 0:
             self._check(1)   # ZOIC_ERR_INVALID_ARGUMENT with the library's detail
-        a = {k: np.zeros(n, dtype=np.float32) for k in ("ior_d", "abbe", "cauchy_b")}
-        self._lib.zoic_camera_get_dispersion(self._h, n, a["ior_d"].ctypes.data, a["abbe"].ctypes.data, a["cauchy_b"].ctypes.data)
+        a = {k: np.zeros(n, dtype=dtype) for k in names}
+        getter(self._h, n, *[v.ctypes.data for v in a.values()])
         return a
 
     def set_abbe_numbers(self, V):
@@ -530,13 +561,8 @@ class ZoicCamera:
         (zoic_create_rays_device_resident): no launch, not stream-ordered -- the current stream is synchronised first (the samples must
         be complete), the records are complete on return.  The bits of create_rays(samples, ray_index_base=...)."""
         import torch
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous():
-            raise ValueError("samples must be a contiguous (n, 4) float32 device tensor")
-        n = samples.shape[0]
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=samples.device)
-        if tuple(out.shape) != (n, 8) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != samples.device:
-            raise ValueError("out must be a contiguous (n, 8) float32 tensor on the samples' device")
+        n = self._device_tensor("samples", samples, (None, 4)).shape[0]
+        out = self._result("out", out, (n, 8), samples)
         torch.cuda.current_stream(samples.device).synchronize()
         self._check(self._lib.zoic_create_rays_device_resident(self._h, n, samples.data_ptr(), out.data_ptr(), int(ray_index_base), int(tid) & 0xFFFF))
         return out
@@ -561,78 +587,32 @@ class ZoicCamera:
         """Opt in (True) or out (False, the default) of answering reverse_ray / camera_reverse_ray with the projection."""
         self._check(self._lib.zoic_camera_set_reverse_projection(self._h, 1 if enable else 0))
 
-    def _wavelength_tensor(self, wavelengths, n, like):
-        """the (n,) float32 wavelength tensor of a batch call, validated as create_rays(..., wavelengths=) validates its own"""
-        import torch
-        if not _is_torch(wavelengths):
-            raise TypeError("torch items need a torch wavelength tensor")
-        if wavelengths.dtype != torch.float32 or tuple(wavelengths.shape) != (n,) or not wavelengths.is_contiguous() or wavelengths.device != like.device:
-            raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the items' device")
-        return wavelengths
-
     def _backward_batch(self, what, width, dline, spectral, items, wavelengths, out, flags, stream, jacobian=None, with_jacobian=False):
         """The batch wrapper of project_points, trace_back and trace_back_jacobian.  `what` ("points" / "rays") names the (n, width)
         float32 items; dline / spectral are the library's entry points without and with wavelengths.  Returns (out, flags) and, with
         with_jacobian, the (n,2,6) jacobian: tensors for torch items, numpy arrays (after a round trip and a wait) for numpy items."""
-        import torch
+        more = 1 if with_jacobian else 0
         if not _is_torch(items):
-            if out is not None or flags is not None or jacobian is not None:
-                raise ValueError("%s are for torch %s" % ("out, flags and jacobian" if with_jacobian else "out and flags", what))
-            if wavelengths is not None and _is_torch(wavelengths):
-                raise TypeError("numpy %s need numpy wavelengths" % what)
-            a = np.asarray(items)
-            if width == 8 and a.dtype == np.dtype(_capi.RAY_DTYPE):
-                a = np.ascontiguousarray(a).reshape(-1).view(np.float32).reshape(-1, 8)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != width:
-                raise ValueError("rays must be (n,) zoic_ray records or (n, 8) float32" if width == 8 else "%s must be (n, %d)" % (what, width))
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                if wavelengths is not None:
-                    self._check(spectral(self._h, a.shape[0], *[None] * (6 if with_jacobian else 5)))
-                self._check(dline(self._h, a.shape[0], *[None] * (5 if with_jacobian else 4)))
-            dev = torch.device("cuda", self.device)
-            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            res = self._backward_batch(what, width, dline, spectral, torch.from_numpy(a).to(dev), tw, None, None, None, None, with_jacobian)
-            torch.cuda.synchronize(dev)
+            res = self._through_device(
+                what, width, items, [("wavelengths", wavelengths, _f32_flat)], dict(out=out, flags=flags, **(dict(jacobian=jacobian) if more else {})),
+                lambda a, w: dline(self._h, len(a), *[None] * (4 + more)) if w is None else spectral(self._h, len(a), *[None] * (5 + more)),
+                lambda t, w: self._backward_batch(what, width, dline, spectral, t, w, None, None, None, None, with_jacobian))
             return tuple(t.cpu().numpy() for t in res)
-        if items.dtype != torch.float32 or items.dim() != 2 or items.shape[1] != width or not items.is_contiguous() or not items.is_cuda:
-            raise ValueError("%s must be a contiguous (n,%d) float32 device tensor" % (what, width))
-        if items.device.index != self.device:
-            raise ValueError("%s live on cuda:%s but this camera is bound to device %d" % (what, items.device.index, self.device))
-        n = items.shape[0]
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float32, device=items.device)
-        if tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != items.device:
-            raise ValueError("out must be a contiguous (n,2) float32 tensor on the %s' device" % what)
-        if flags is None:
-            flags = torch.empty((n,), dtype=torch.int32, device=items.device)
-        if tuple(flags.shape) != (n,) or flags.dtype not in (torch.int32, torch.uint32) or not flags.is_contiguous() or flags.device != items.device:
-            raise ValueError("flags must be a contiguous (n,) int32 tensor on the %s' device" % what)
-        res, tail = (out, flags), [out.data_ptr(), flags.data_ptr()]
+        n = self._device_tensor(what, items, (None, width)).shape[0]
+        res = [self._result("out", out, (n, 2), items), self._result("flags", flags, (n,), items, ints=True)]
         if with_jacobian:
-            if jacobian is None:
-                jacobian = torch.empty((n, 2, 6), dtype=torch.float32, device=items.device)
-            if tuple(jacobian.shape) != (n, 2, 6) or jacobian.dtype != torch.float32 or not jacobian.is_contiguous() or jacobian.device != items.device:
-                raise ValueError("jacobian must be a contiguous (n,2,6) float32 tensor on the %s' device" % what)
-            res, tail = (out, flags, jacobian), tail + [jacobian.data_ptr()]
-        tail.append(C.c_void_p(stream if stream is not None else torch.cuda.current_stream(items.device).cuda_stream))
-        if wavelengths is not None:
-            w = self._wavelength_tensor(wavelengths, n, items)
-            self._check(spectral(self._h, n, items.data_ptr(), w.data_ptr(), *tail))
-        else:
-            self._check(dline(self._h, n, items.data_ptr(), *tail))
-        return res
+            res.append(self._result("jacobian", jacobian, (n, 2, 6), items))
+        w = self._wavelength_pointer(wavelengths, n)
+        self._spectral_or(dline, spectral, w, (n, items.data_ptr()), [t.data_ptr() for t in res] + [self._stream(stream)])
+        return tuple(res)
 
-    def _trace_back_one(self, dline, spectral, origin, dir, wavelength, *extra):
-        """the host single-ray wrappers' call: (sx, sy, flags); extra: further output arguments of both entry points"""
-        o = _capi.Vec3(*[float(v) for v in origin])
-        d = _capi.Vec3(*[float(v) for v in dir])
+    def _screen_sample(self, dline, spectral, vectors, wavelength, *extra):
+        """the host single-item wrappers' call: the (sx, sy, flags) both entry points write for `vectors` (a point, or an origin and
+        a dir); extra: further output arguments of both"""
         ps = (C.c_float * 2)(0.0, 0.0)
         f = C.c_uint32(0)
-        if wavelength is not None:
-            self._check(spectral(self._h, C.byref(o), C.byref(d), float(wavelength), ps, C.byref(f), *extra))
-        else:
-            self._check(dline(self._h, C.byref(o), C.byref(d), ps, C.byref(f), *extra))
+        self._spectral_or(dline, spectral, None if wavelength is None else float(wavelength),
+                          [C.byref(_capi.Vec3(*[float(x) for x in v])) for v in vectors], (ps, C.byref(f)) + extra)
         return float(ps[0]), float(ps[1]), int(f.value)
 
     def project_point(self, Po, wavelength=None):
@@ -641,14 +621,7 @@ class ZoicCamera:
         the reason a point is not projected (csrc/reverse.hpp).  Works on a tables-only camera (device=-1).
         wavelength (nm): the projection through the glass at that wavelength (zoic_project_point_spectral, csrc/backward_spectral.hpp);
         outside [360, 830] or NaN: not projected, reason _capi.PROJECT_WAVELENGTH."""
-        po = _capi.Vec3(*[float(v) for v in Po])
-        ps = (C.c_float * 2)(0.0, 0.0)
-        f = C.c_uint32(0)
-        if wavelength is not None:
-            self._check(self._lib.zoic_project_point_spectral(self._h, C.byref(po), float(wavelength), ps, C.byref(f)))
-            return float(ps[0]), float(ps[1]), int(f.value)
-        self._check(self._lib.zoic_project_point(self._h, C.byref(po), ps, C.byref(f)))
-        return float(ps[0]), float(ps[1]), int(f.value)
+        return self._screen_sample(self._lib.zoic_project_point, self._lib.zoic_project_point_spectral, (Po,), wavelength)
 
     def project_points(self, points, out=None, flags=None, stream=None, wavelengths=None):
         """Reverse projection of (n,3) float32 points (zoic_project_points_device): returns (screen (n,2) float32, flags (n,) int32).
@@ -669,7 +642,7 @@ class ZoicCamera:
         tables-only camera (device=-1).
         wavelength (nm): the trace through the glass at that wavelength (zoic_trace_back_ray_spectral, csrc/backward_spectral.hpp);
         outside [360, 830] or NaN: not traced back, reason _capi.TRACE_BACK_WAVELENGTH."""
-        return self._trace_back_one(self._lib.zoic_trace_back_ray, self._lib.zoic_trace_back_ray_spectral, origin, dir, wavelength)
+        return self._screen_sample(self._lib.zoic_trace_back_ray, self._lib.zoic_trace_back_ray_spectral, (origin, dir), wavelength)
 
     def trace_back(self, rays, out=None, flags=None, stream=None, wavelengths=None):
         """Trace-back of n camera rays (zoic_trace_back_rays_device): returns (screen (n,2) float32, flags (n,) int32).
@@ -682,10 +655,8 @@ class ZoicCamera:
         wavelengths: (n,) float32 (nm), numpy with numpy rays, a device tensor with device rays -- for the records of
                      create_rays(samples, wavelengths=w), the same w: every ray traced back at its own wavelength
                      (zoic_trace_back_rays_spectral_device); None: the d-line call."""
-        if isinstance(rays, dict):
-            rays = rays["rays"]
-        return self._backward_batch("rays", 8, self._lib.zoic_trace_back_rays_device, self._lib.zoic_trace_back_rays_spectral_device, rays,
-                                    wavelengths, out, flags, stream)
+        return self._backward_batch("rays", 8, self._lib.zoic_trace_back_rays_device, self._lib.zoic_trace_back_rays_spectral_device,
+                                    _records(rays), wavelengths, out, flags, stream)
 
     def trace_back_ray_jacobian(self, origin, dir, wavelength=None):
         """Trace-back of one camera ray on the host with its Jacobian (zoic_trace_back_ray_jacobian): (sx, sy, flags, J (2,6) float32).
@@ -693,8 +664,8 @@ class ZoicCamera:
         (csrc/traceback_jacobian.hpp); all zero for a ray that is not traced back.  Works on a tables-only camera (device=-1).
         wavelength (nm): the trace at that wavelength, held fixed (zoic_trace_back_ray_jacobian_spectral)."""
         jac = np.zeros((2, 6), np.float32)
-        return self._trace_back_one(self._lib.zoic_trace_back_ray_jacobian, self._lib.zoic_trace_back_ray_jacobian_spectral, origin, dir,
-                                    wavelength, jac.ctypes.data_as(C.POINTER(C.c_float))) + (jac,)
+        return self._screen_sample(self._lib.zoic_trace_back_ray_jacobian, self._lib.zoic_trace_back_ray_jacobian_spectral, (origin, dir),
+                                   wavelength, jac.ctypes.data_as(C.POINTER(C.c_float))) + (jac,)
 
     def trace_back_jacobian(self, rays, wavelengths=None, out=None, flags=None, jacobian=None, stream=None):
         """Trace-back of n camera rays with the Jacobian of each (zoic_trace_back_jacobian_device): returns (screen (n,2) float32,
@@ -705,10 +676,8 @@ class ZoicCamera:
         rays, wavelengths, stream: as trace_back takes them (device tensors, the dict of a create_rays call, or numpy).
         out / flags / jacobian: optional (n,2) float32, (n,) int32 and (n,2,6) float32 tensors on the rays' device to write into
         (torch rays only)."""
-        if isinstance(rays, dict):
-            rays = rays["rays"]
         return self._backward_batch("rays", 8, self._lib.zoic_trace_back_jacobian_device, self._lib.zoic_trace_back_jacobian_spectral_device,
-                                    rays, wavelengths, out, flags, stream, jacobian, True)
+                                    _records(rays), wavelengths, out, flags, stream, jacobian, True)
 
     @staticmethod
     def _pupil_window(window):
@@ -753,10 +722,8 @@ class ZoicCamera:
         po = _capi.Vec3(*[float(v) for v in Po])
         b = _capi.PupilBounds()
         w = self._pupil_window(window)
-        if wavelength is not None:
-            self._check(self._lib.zoic_pupil_bounds_point_spectral(self._h, C.byref(po), float(wavelength), int(lattice), w, C.byref(b)))
-        else:
-            self._check(self._lib.zoic_pupil_bounds_point(self._h, C.byref(po), int(lattice), w, C.byref(b)))
+        self._spectral_or(self._lib.zoic_pupil_bounds_point, self._lib.zoic_pupil_bounds_point_spectral,
+                          None if wavelength is None else float(wavelength), (C.byref(po),), (int(lattice), w, C.byref(b)))
         return dict(aim=np.array(b.aim[:], np.float32), screen=np.array(b.screen[:], np.float32), count=int(b.count), lattice=int(b.lattice),
                     flags=int(b.flags))
 
@@ -771,38 +738,17 @@ class ZoicCamera:
                      out: an optional tensor of that kind to write into.  pupil_bounds_records(t) turns it into the structured array.
         lattice: 8, 16 or 32.  window: None or (sx0, sy0, sx1, sy1).
         wavelengths: (n,) float32 (nm), numpy with numpy points, a device tensor with device points (zoic_pupil_bounds_spectral_device)."""
-        import torch
         w = self._pupil_window(window)
         if not _is_torch(points):
-            if out is not None:
-                raise ValueError("out is for torch points")
-            if wavelengths is not None and _is_torch(wavelengths):
-                raise TypeError("numpy points need numpy wavelengths")
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError("points must be (n, 3)")
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                self._check(self._lib.zoic_pupil_bounds_device(self._h, a.shape[0], None, int(lattice), w, None, None))
-            dev = torch.device("cuda", self.device)
-            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            res = self.pupil_bounds(torch.from_numpy(a).to(dev), lattice, window, tw)
-            torch.cuda.synchronize(dev)
+            res = self._through_device("points", 3, points, [("wavelengths", wavelengths, _f32_flat)], dict(out=out),
+                                       lambda a, lam: self._lib.zoic_pupil_bounds_device(self._h, len(a), None, int(lattice), w, None, None),
+                                       lambda t, lam: self.pupil_bounds(t, lattice, window, lam))
             return pupil_bounds_records(res)
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
-            raise ValueError("points must be a contiguous (n,3) float32 device tensor")
-        if points.device.index != self.device:
-            raise ValueError("points live on cuda:%s but this camera is bound to device %d" % (points.device.index, self.device))
-        n = points.shape[0]
-        if out is None:
-            out = torch.empty((n, 12), dtype=torch.float32, device=points.device)
-        if tuple(out.shape) != (n, 12) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
-            raise ValueError("out must be a contiguous (n,12) float32 tensor on the points' device")
-        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream)
-        if wavelengths is not None:
-            lam = self._wavelength_tensor(wavelengths, n, points)
-            self._check(self._lib.zoic_pupil_bounds_spectral_device(self._h, n, points.data_ptr(), lam.data_ptr(), int(lattice), w, out.data_ptr(), st))
-        else:
-            self._check(self._lib.zoic_pupil_bounds_device(self._h, n, points.data_ptr(), int(lattice), w, out.data_ptr(), st))
+        n = self._device_tensor("points", points, (None, 3)).shape[0]
+        out = self._result("out", out, (n, 12), points)
+        lam = self._wavelength_pointer(wavelengths, n)
+        self._spectral_or(self._lib.zoic_pupil_bounds_device, self._lib.zoic_pupil_bounds_spectral_device, lam, (n, points.data_ptr()),
+                          (int(lattice), w, out.data_ptr(), self._stream(stream)))
         return out
 
     def splat_point(self, Po, bounds, u, wavelength=None):
@@ -827,10 +773,8 @@ class ZoicCamera:
         m = uu.shape[0]
         out = np.zeros(m, _capi.SPLAT_DTYPE)
         up, op = uu.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
-        if wavelength is not None:
-            self._check(self._lib.zoic_splat_point_spectral(self._h, C.byref(po), C.byref(b), float(wavelength), m, up, op))
-        else:
-            self._check(self._lib.zoic_splat_point(self._h, C.byref(po), C.byref(b), m, up, op))
+        self._spectral_or(self._lib.zoic_splat_point, self._lib.zoic_splat_point_spectral, None if wavelength is None else float(wavelength),
+                          (C.byref(po), C.byref(b)), (m, up, op))
         return out
 
     def splat_points(self, points, bounds, u, wavelengths=None, out=None, stream=None):
@@ -847,45 +791,21 @@ class ZoicCamera:
         numpy in  -> points, bounds (the structured records or (n,12) float32) and u are copied to the camera's device through
                      torch, the call waits and returns an (n,m) structured array (_capi.SPLAT_DTYPE); out must be None there.
         wavelengths: (n,) float32 (nm), numpy with numpy points, a device tensor with device points (zoic_splat_points_spectral_device)."""
-        import torch
         if not _is_torch(points):
-            if out is not None:
-                raise ValueError("out is for torch points")
-            if _is_torch(bounds) or _is_torch(u) or (wavelengths is not None and _is_torch(wavelengths)):
-                raise TypeError("numpy points need numpy bounds, u and wavelengths")
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError("points must be (n, 3)")
-            b = np.ascontiguousarray(pupil_bounds_records(bounds)).view(np.float32).reshape(-1, 12)
-            uu = np.ascontiguousarray(u, dtype=np.float32)
-            if self.device < 0:   # a tables-only camera: the library reports it (ZOIC_ERR_NO_DEVICE)
-                self._check(self._lib.zoic_splat_points_device(self._h, a.shape[0], None, None, 1, None, None, None))
-            dev = torch.device("cuda", self.device)
-            tw = None if wavelengths is None else torch.from_numpy(np.ascontiguousarray(wavelengths, dtype=np.float32).reshape(-1)).to(dev)
-            res = self.splat_points(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), torch.from_numpy(uu).to(dev), tw)
-            torch.cuda.synchronize(dev)
+            res = self._through_device(
+                "points", 3, points, [("bounds", bounds, _bounds_floats), ("u", u, _f32), ("wavelengths", wavelengths, _f32_flat)], dict(out=out),
+                lambda a, b, uu, lam: self._lib.zoic_splat_points_device(self._h, len(a), None, None, 1, None, None, None),
+                lambda t, b, uu, lam: self.splat_points(t, b, uu, lam))
             return splat_records(res)
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous() or not points.is_cuda:
-            raise ValueError("points must be a contiguous (n,3) float32 device tensor")
-        if points.device.index != self.device:
-            raise ValueError("points live on cuda:%s but this camera is bound to device %d" % (points.device.index, self.device))
-        n = points.shape[0]
-        if not _is_torch(bounds) or tuple(bounds.shape) != (n, 12) or bounds.dtype != torch.float32 or not bounds.is_contiguous() or bounds.device != points.device:
-            raise ValueError("bounds must be the contiguous (n,12) float32 tensor of pupil_bounds on the points' device")
-        if not _is_torch(u) or u.dim() != 3 or u.shape[0] != n or u.shape[1] < 1 or u.shape[2] != 2 or u.dtype != torch.float32 or not u.is_contiguous() or u.device != points.device:
-            raise ValueError("u must be a contiguous (n,m,2) float32 tensor on the points' device, m >= 1")
-        m = u.shape[1]
-        if out is None:
-            out = torch.empty((n, m, 8), dtype=torch.float32, device=points.device)
-        if tuple(out.shape) != (n, m, 8) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
-            raise ValueError("out must be a contiguous (n,m,8) float32 tensor on the points' device")
-        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream)
-        if wavelengths is not None:
-            lam = self._wavelength_tensor(wavelengths, n, points)
-            self._check(self._lib.zoic_splat_points_spectral_device(self._h, n, points.data_ptr(), bounds.data_ptr(), lam.data_ptr(), m, u.data_ptr(),
-                                                                    out.data_ptr(), st))
-        else:
-            self._check(self._lib.zoic_splat_points_device(self._h, n, points.data_ptr(), bounds.data_ptr(), m, u.data_ptr(), out.data_ptr(), st))
+        n = self._device_tensor("points", points, (None, 3)).shape[0]
+        self._device_tensor("bounds", bounds, (n, 12))
+        m = self._device_tensor("u", u, (n, None, 2)).shape[1]
+        if m < 1:
+            raise ValueError("u must hold at least one aim per point: (n,m,2), m >= 1")
+        out = self._result("out", out, (n, m, 8), points)
+        lam = self._wavelength_pointer(wavelengths, n)
+        self._spectral_or(self._lib.zoic_splat_points_device, self._lib.zoic_splat_points_spectral_device, lam,
+                          (n, points.data_ptr(), bounds.data_ptr()), (m, u.data_ptr(), out.data_ptr(), self._stream(stream)))
         return out
 
     def create_rays_arnold(self, inputs, ray_index_base=0, differentials=False):
@@ -915,40 +835,21 @@ class ZoicCamera:
         outside [360, 830] or NaN get zeros.  chromatic=True (needs wavelengths) returns (diffs, chroma): chroma is an (n,6) float32
         tensor, dO/dlambda and dD/dlambda per nanometre with the sensor point and the lens point held fixed (never scaled by dsx /
         dsy; csrc/differentials_spectral.hpp)."""
-        import torch
         if chromatic and wavelengths is None:
             raise ValueError("chromatic=True needs wavelengths")
-        if isinstance(rays, dict):
-            rays = rays["rays"]
-        if not _is_torch(samples) or not _is_torch(rays):
-            raise ValueError("samples and rays must be device tensors (create_rays with a torch tensor)")
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
-            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
-        if samples.device.index != self.device:
-            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
-        n = samples.shape[0]
-        if tuple(rays.shape) != (n, 8) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
-            raise ValueError("rays must be the contiguous (n,8) float32 record tensor on the samples' device")
-        rs_ptr = None
-        if rng_states is not None:
-            if rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4) or not rng_states.is_contiguous():
-                raise ValueError("rng_states must be (n,4) int32/uint32 on the device")
-            rs_ptr = rng_states.data_ptr()
-        if out is None:
-            out = torch.empty((n, 12), dtype=torch.float32, device=samples.device)
-        if tuple(out.shape) != (n, 12) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != samples.device:
-            raise ValueError("out must be a contiguous (n,12) float32 tensor on the samples' device")
-        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
-        if wavelengths is not None:
-            w = self._wavelength_tensor(wavelengths, n, samples)
-            chroma = torch.empty((n, 6), dtype=torch.float32, device=samples.device) if chromatic else None
-            self._check(self._lib.zoic_ray_differentials_spectral_device(
-                self._h, n, samples.data_ptr(), w.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(), float(dsx), float(dsy),
-                out.data_ptr(), chroma.data_ptr() if chromatic else None, C.c_void_p(st)))
-            return (out, chroma) if chromatic else out
-        self._check(self._lib.zoic_ray_differentials_device(self._h, n, samples.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(),
-                                                            float(dsx), float(dsy), out.data_ptr(), C.c_void_p(st)))
-        return out
+        n = self._device_tensor("samples", samples, (None, 4)).shape[0]
+        rays, rs_ptr = self._traced(n, rays, rng_states)
+        out = self._result("out", out, (n, 12), samples)
+        if wavelengths is None:
+            self._check(self._lib.zoic_ray_differentials_device(self._h, n, samples.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(),
+                                                                float(dsx), float(dsy), out.data_ptr(), self._stream(stream)))
+            return out
+        w = self._device_tensor("wavelengths", wavelengths, (n,), missing=TypeError)
+        chroma = self._result("chroma", None, (n, 6), samples) if chromatic else None
+        self._check(self._lib.zoic_ray_differentials_spectral_device(
+            self._h, n, samples.data_ptr(), w.data_ptr(), rs_ptr, int(ray_index_base), rays.data_ptr(), float(dsx), float(dsy),
+            out.data_ptr(), chroma.data_ptr() if chromatic else None, self._stream(stream)))
+        return (out, chroma) if chromatic else out
 
     def transmittance(self, samples, rays, wavelengths=None, rng_states=None, ray_index_base=0, out=None, stream=None):
         """Fresnel transmittance (zoic_ray_transmittance_device) of rays create_rays / create_rays_hero made from device tensors: the
@@ -959,41 +860,16 @@ class ZoicCamera:
         create_rays(samples, wavelengths=); (n,k): the hero records of create_rays_hero, rays (n,k,8).  Returns a float32 device tensor
         of the wavelengths' shape ((n,) for None); asynchronous on `stream` (default: torch's current stream).  Records of weight 0
         and columns whose wavelength is outside [360, 830] or NaN get +0.0.  Changes no record and no counter."""
-        import torch
-        if isinstance(rays, dict):
-            rays = rays["rays"]
-        if not _is_torch(samples) or not _is_torch(rays):
-            raise ValueError("samples and rays must be device tensors (create_rays with a torch tensor)")
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
-            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
-        if samples.device.index != self.device:
-            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
-        n = samples.shape[0]
-        shape, k, w_ptr = (n,), 1, None
+        n = self._device_tensor("samples", samples, (None, 4)).shape[0]
+        shape, w_ptr = (n,), None
         if wavelengths is not None:
-            if not _is_torch(wavelengths):
-                raise TypeError("torch samples need a torch wavelength tensor")
-            if (wavelengths.dtype != torch.float32 or wavelengths.dim() not in (1, 2) or wavelengths.shape[0] != n
-                    or not wavelengths.is_contiguous() or wavelengths.device != samples.device):
-                raise ValueError("wavelengths must be a contiguous (n,) or (n,k) float32 tensor on the samples' device")
-            shape = tuple(wavelengths.shape)
-            k = shape[1] if len(shape) == 2 else 1
+            hero = getattr(wavelengths, "ndim", 1) == 2
+            shape = tuple(self._device_tensor("wavelengths", wavelengths, (n, None) if hero else (n,), missing=TypeError).shape)
             w_ptr = wavelengths.data_ptr()
-        if tuple(rays.shape) != shape + (8,) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
-            raise ValueError("rays must be the contiguous %s float32 record tensor on the samples' device" % (shape + (8,),))
-        rs_ptr = None
-        if rng_states is not None:
-            if (not _is_torch(rng_states) or rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4)
-                    or not rng_states.is_contiguous() or rng_states.device != samples.device):
-                raise ValueError("rng_states must be a contiguous (n,4) int32/uint32 tensor on the samples' device")
-            rs_ptr = rng_states.data_ptr()
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=samples.device)
-        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != samples.device:
-            raise ValueError("out must be a contiguous %s float32 tensor on the samples' device" % (shape,))
-        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
-        self._check(self._lib.zoic_ray_transmittance_device(self._h, n, k, samples.data_ptr(), w_ptr, rs_ptr, int(ray_index_base),
-                                                            rays.data_ptr(), out.data_ptr(), C.c_void_p(st)))
+        rays, rs_ptr = self._traced(n, rays, rng_states, shape)
+        out = self._result("out", out, shape, samples)
+        self._check(self._lib.zoic_ray_transmittance_device(self._h, n, shape[1] if len(shape) == 2 else 1, samples.data_ptr(), w_ptr, rs_ptr,
+                                                            int(ray_index_base), rays.data_ptr(), out.data_ptr(), self._stream(stream)))
         return out
 
     def set_coatings(self, index, lambda0_nm):
@@ -1010,22 +886,13 @@ class ZoicCamera:
     def coatings(self):
         """The lens's film table (zoic_camera_get_coatings), trace order (rear first): dict of float32 arrays index (0: uncoated) and
         lambda0_nm.  Works on a tables-only camera (device=-1)."""
-        n = self._lib.zoic_camera_get_coatings(self._h, 0, None, None)
-        if n < 0:
-            self._check(1)   # ZOIC_ERR_INVALID_ARGUMENT with the library's detail
-        a = {k: np.zeros(n, dtype=np.float32) for k in ("index", "lambda0_nm")}
-        self._lib.zoic_camera_get_coatings(self._h, n, a["index"].ctypes.data, a["lambda0_nm"].ctypes.data)
-        return a
+        return self._table(self._lib.zoic_camera_get_coatings, np.float32, ("index", "lambda0_nm"))
 
     def ghost_pairs(self):
         """The interface pairs that can make a ghost (zoic_camera_get_ghost_pairs): an (m,2) int32 array of rows (a, b), trace-order
         indices (rear first), a > b, both interfaces between unequal media at the d-line; ordered by a, then b.  Works on a
         tables-only camera (device=-1)."""
-        m = self._lib.zoic_camera_get_ghost_pairs(self._h, 0, None)
-        if m < 0:
-            self._check(1)   # ZOIC_ERR_INVALID_ARGUMENT with the library's detail
-        packed = np.zeros(m, dtype=np.uint32)
-        self._lib.zoic_camera_get_ghost_pairs(self._h, m, packed.ctypes.data)
+        packed = self._table(self._lib.zoic_camera_get_ghost_pairs, np.uint32, ("packed",))["packed"]
         return np.stack([packed & _GHOST_INDEX_MASK, (packed >> _GHOST_INDEX_BITS) & _GHOST_INDEX_MASK], 1).astype(np.int32)
 
     def create_ghost_rays(self, samples, rays, pairs, wavelengths=None, rng_states=None, ray_index_base=0, out=None, stream=None):
@@ -1039,59 +906,30 @@ class ZoicCamera:
         word (bit 0: traced; else the reason in bits 8-11, the interface in bits 16-21, the leg in bits 24-25 and zeros before
         them).  More than 32 pairs are served by successive calls on the same stream.  out: an optional contiguous (n,p,8) float32
         tensor on the samples' device to write into (p <= 32).  Changes no record and no counter."""
-        import torch
-        if isinstance(rays, dict):
-            rays = rays["rays"]
-        if not _is_torch(samples) or not _is_torch(rays):
-            raise ValueError("samples and rays must be device tensors (create_rays with a torch tensor)")
-        if samples.dtype != torch.float32 or samples.dim() != 2 or samples.shape[1] != 4 or not samples.is_contiguous() or not samples.is_cuda:
-            raise ValueError("samples must be a contiguous (n,4) float32 device tensor")
-        if samples.device.index != self.device:
-            raise ValueError("samples live on cuda:%s but this camera is bound to device %d" % (samples.device.index, self.device))
-        n = samples.shape[0]
-        if tuple(rays.shape) != (n, 8) or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != samples.device:
-            raise ValueError("rays must be the contiguous (n,8) float32 record tensor on the samples' device")
+        n = self._device_tensor("samples", samples, (None, 4)).shape[0]
+        rays, rs_ptr = self._traced(n, rays, rng_states)
         pr = np.asarray(pairs)
         if pr.ndim != 2 or pr.shape[1] != 2 or pr.shape[0] == 0 or not np.issubdtype(pr.dtype, np.integer):
             raise ValueError("pairs must be a non-empty (p,2) integer array of (a, b)")
         if (pr < 0).any() or (pr > _GHOST_INDEX_MASK).any():
             raise ValueError("pair indices must lie in 0 ... %d" % _GHOST_INDEX_MASK)
         packed = np.ascontiguousarray(pr[:, 0].astype(np.uint32) | (pr[:, 1].astype(np.uint32) << _GHOST_INDEX_BITS))
-        w_ptr = None
-        if wavelengths is not None:
-            if not _is_torch(wavelengths):
-                raise TypeError("torch samples need a torch wavelength tensor")
-            if (wavelengths.dtype != torch.float32 or tuple(wavelengths.shape) != (n,) or not wavelengths.is_contiguous()
-                    or wavelengths.device != samples.device):
-                raise ValueError("wavelengths must be a contiguous (n,) float32 tensor on the samples' device")
-            w_ptr = wavelengths.data_ptr()
-        rs_ptr = None
-        if rng_states is not None:
-            if (not _is_torch(rng_states) or rng_states.dtype not in (torch.int32, torch.uint32) or tuple(rng_states.shape) != (n, 4)
-                    or not rng_states.is_contiguous() or rng_states.device != samples.device):
-                raise ValueError("rng_states must be a contiguous (n,4) int32/uint32 tensor on the samples' device")
-            rs_ptr = rng_states.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(samples.device).cuda_stream
+        w_ptr = self._wavelength_pointer(wavelengths, n)
         p = len(packed)
         chunk = 32   # ZOIC_GHOST_MAX_PAIRS
-        if out is not None and (p > chunk or tuple(out.shape) != (n, p, 8) or out.dtype != torch.float32 or not out.is_contiguous()
-                                or out.device != samples.device):
-            raise ValueError("out must be a contiguous (n,p,8) float32 tensor on the samples' device, p <= 32")
-        if p <= chunk:
-            if out is None:
-                out = torch.empty((n, p, 8), dtype=torch.float32, device=samples.device)
-            self._check(self._lib.zoic_create_ghost_rays_device(self._h, n, p, packed.ctypes.data, samples.data_ptr(), w_ptr, rs_ptr,
-                                                                int(ray_index_base), rays.data_ptr(), out.data_ptr(), C.c_void_p(st)))
-            return out
-        if stream is not None:
+        if p > chunk and out is not None:
+            raise ValueError("out is for at most 32 pairs: more are gathered into a tensor of the call's own")
+        if p > chunk and stream is not None:
             raise ValueError("more than 32 pairs are gathered with torch on the current stream: leave stream=None")
         parts = []
-        for lo in range(0, p, chunk):
+        for lo in range(0, p, chunk):   # (one chunk: straight into out)
             q = packed[lo:lo + chunk]
-            part = torch.empty((n, len(q), 8), dtype=torch.float32, device=samples.device)
+            parts.append(self._result("out", out, (n, len(q), 8), samples))
             self._check(self._lib.zoic_create_ghost_rays_device(self._h, n, len(q), q.ctypes.data, samples.data_ptr(), w_ptr, rs_ptr,
-                                                                int(ray_index_base), rays.data_ptr(), part.data_ptr(), C.c_void_p(st)))
-            parts.append(part)
+                                                                int(ray_index_base), rays.data_ptr(), parts[-1].data_ptr(), self._stream(stream)))
+        if len(parts) == 1:
+            return parts[0]
+        import torch
         return torch.cat(parts, 1)
 
     def tile(self, capacity, tid=0):
@@ -1114,9 +952,8 @@ class ZoicCamera:
         dev = torch.device("cuda", self.device)
         if out is None:
             out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         self._check(self._lib.zoic_generate_samples_device(self._h, n, int(ray_index_base), width, height, spp, seed,
-                                                           out.data_ptr(), C.c_void_p(st)))
+                                                           out.data_ptr(), self._stream(stream)))
         return out
 
     # ------------------------------------------------------------------ statistics / tables
