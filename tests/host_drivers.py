@@ -28,13 +28,16 @@ _LIBS = {}
 
 
 def _build(key, source):
-    """the loaded host build of `source`, compiled on the first request for `key` (the directory goes once the library is mapped)"""
+    """the loaded host build of `source`, compiled on the first request for `key` (the directory goes once the library is mapped).
+    -Bsymbolic: the library itself is loaded RTLD_GLOBAL (zoic_amd/_capi.py) and exports the headers' inline functions as weak symbols
+    (zoic::splat_point, zoic::trace_back_ray, ...); without it every call of a driver that the compiler did not inline binds to the
+    LIBRARY's copy, and the "host twin" is the library's own object code whatever the header under csrc/ says."""
     if key not in _LIBS:
         with tempfile.TemporaryDirectory(prefix="zoic_%s_driver_" % key) as d:
             src, so = os.path.join(d, "driver.cpp"), os.path.join(d, "driver.so")
             with open(src, "w") as f:
                 f.write(source)
-            subprocess.check_call([clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC,
+            subprocess.check_call([clangxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-I" + CSRC,
                                    "-I" + os.path.join(ROOT, "include"), src, "-o", so])
             _LIBS[key] = ctypes.CDLL(so)
     return _LIBS[key]

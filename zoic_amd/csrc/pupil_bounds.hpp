@@ -35,7 +35,9 @@
 //
 // What the bounds are: statements about the LATTICE, not a guarantee about the pupil.  Every passing lattice aim lies inside `aim`,
 // and growing the box by a pitch covers the pupil's edge wherever the pupil is at least a pitch wide there; a sliver of pupil thinner
-// than a pitch can pass between the aims and lie outside the grown box (DESIGN 4.17 has the measured share).  `screen` is the box of
+// than a pitch can pass between the aims and lie outside the grown box (DESIGN 4.17 has the measured share).  Where the whole pupil
+// is thinner than a pitch -- a front housing much larger than the entrance pupil, as on a fisheye -- no aim may pass at all, and
+// count = 0 then says nothing about whether P sees the lens (the corpus table and the fall-backs).  `screen` is the box of
 // the lattice aims' landing points, nothing more.  The caller draws in `aim` and still traces every ray back: a draw outside the true
 // pupil is refused there, as before.
 //
