@@ -182,7 +182,7 @@ def test_rows_beside_hostile_neighbours(oracle_lib, precision):
 
 
 # ---- 5: past the grid's first pass ---------------------------------------------------------------------------------------------
-# mirrored from zoic_amd/csrc/spectral.hip: kSpecGridCap blocks of kSpecBlock threads; a wave of kolb_spectral_kernel<FAST, HERO> claims
+# mirrored from zoic_amd/csrc/device_pass.hpp and spectral.hip: kPassGridCap blocks of kPassBlock threads; a wave of kolb_spectral_kernel<FAST, HERO> claims
 # kSpecChunk samples at a time, a thread of hero_replicate_kernel one row per stride
 HERO_GRID_CAP, HERO_BLOCK, HERO_CHUNK = 2048, 256, 256
 KOLB_FIRST_PASS = HERO_GRID_CAP * (HERO_BLOCK // 64) * HERO_CHUNK      # 2 097 152 samples

@@ -22,7 +22,7 @@ import traceback_cases as tc
 # 1: a workgroup with three idle waves; 3: one idle wave; 4: a full workgroup; 5: a partial second workgroup; 257: 64 full
 # workgroups and a last one with a single busy wave
 SHAPES = (1, 3, 4, 5, 257)
-GRID_CAP = 2048   # workgroups of four waves (pupil_bounds.hip): a larger batch is walked with a grid stride
+GRID_CAP = 2048   # workgroups of four waves (kPassGridCap, device_pass.hpp; pupil_bounds.hip takes a point per wave): a larger batch is walked with a grid stride
 
 
 def _camera(name):

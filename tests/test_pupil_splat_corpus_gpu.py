@@ -36,7 +36,7 @@ from traceback_ref import OUTSIDE_DOMAIN
 
 F32 = np.float32
 PREFIXES = (1, 3, 4, 5)
-GRID_CAP = 2048                      # workgroups a launch is capped at (pupil_bounds.hip: four points each; splat.hip: 256 splats each)
+GRID_CAP = 2048                      # workgroups a launch is capped at (kPassGridCap, device_pass.hpp; pupil_bounds.hip: four points each; splat.hip: 256 splats each)
 SLAB_PLUS_ONE = 4 * GRID_CAP + 1     # pupil bounds: one slab of the grid-stride walk and one point
 STRIDE_SHAPE = (174763, 3)           # splats: 2^19 + 1 = 3 x 174763
 assert STRIDE_SHAPE[0] * STRIDE_SHAPE[1] == GRID_CAP * 256 + 1

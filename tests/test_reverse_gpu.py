@@ -11,7 +11,7 @@ from zoic_amd.workloads import camera_params, hexagon_bokeh, ray_rng_states
 
 from reverse_ref import kolb_point_set, thin_point_set
 
-SLAB = 2048 * 256   # one grid of the kernel (reverse.hip): larger batches are walked slab by slab
+SLAB = 2048 * 256   # one grid of the kernel (kPassGridCap x kPassBlock, device_pass.hpp): larger batches are walked slab by slab
 
 
 def _camera(cfg, **over):

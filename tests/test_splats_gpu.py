@@ -19,7 +19,7 @@ import splat_driver
 import splat_ref
 import traceback_cases as tc
 
-GRID_CAP = 2048   # workgroups of 256 lanes (splat.hip): more than GRID_CAP x 256 splats are walked with a grid stride
+GRID_CAP = 2048   # workgroups of 256 lanes (kPassGridCap, kPassBlock: device_pass.hpp): more than GRID_CAP x 256 splats are walked with a grid stride
 # (n, m): the smallest call; a wave straddling points, m no power of two; one point per wave; more aims than a workgroup; and one
 # splat more than a full grid (2^19 + 1 = 3 x 174763), so that lane 0 of workgroup 0 takes a second trip (m = 3 does not divide the
 # stride: the walk's remainder step carries over)

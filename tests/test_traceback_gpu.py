@@ -14,7 +14,7 @@ import traceback_cases as tc
 from device_cases import records as _records
 from traceback_ref import TraceBack
 
-SLAB = 2048 * 256   # one grid of the kernel (traceback.hip): larger batches are walked slab by slab
+SLAB = 2048 * 256   # one grid of the kernel (kPassGridCap x kPassBlock, device_pass.hpp): larger batches are walked slab by slab
 W, H, SPP = 256, 144, 2   # 73 728 rays
 
 

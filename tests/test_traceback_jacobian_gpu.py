@@ -20,7 +20,7 @@ from device_cases import bits as _bits, records as _records
 from traceback_jacobian_ref import H, N, SPP, W, residual as _residual
 from traceback_ref import TraceBack
 
-SLAB = 2048 * 256   # one grid of the kernels (traceback.hip): larger batches are walked slab by slab
+SLAB = 2048 * 256   # one grid of the kernels (kPassGridCap x kPassBlock, device_pass.hpp): larger batches are walked slab by slab
 EDGE_ROWS = np.array([[0, 0, -1, 0, 0, -1], [0, 0, -1e30, 0, 0, -1e-30], [1e30, 0, -1, 0, 0, -1], [0, 0, -1, 1e30, 0, -1e-30],
                       [0, 0, 0, 0, 0, -1], [-0.0, -0.0, -0.0, -0.0, -0.0, -1], [0, 0, -1, 1, 0, -1e-38], [1e-30, 1e-30, -1e-30, 1e-30, 0, -1e-30]],
                      np.float32)

@@ -18,7 +18,7 @@
 //   Unchanged  Geometry, housings, the stop limit, the sensor plane (originShift), the focal-length rescale, the LUT flag, the
 //              domain gate, the cap test, the projection's paraxial first guess (it only seeds the search) and every arithmetic step
 //              that does not read an index: the camera is focused at 587.5618 nm, as on the forward side.
-//   At lambda = 587.5618f   spectral_dl is exactly 0, every n_i is n_d,i, every ratio is the host table's own division: Ps and flags
+//   At the d-line (kLambdaD32)   spectral_dl is exactly 0, every n_i is n_d,i, every ratio is the host table's own division: Ps and flags
 //              equal the d-line calls' bit for bit, for every input (the same templates run, traceback.hpp trace_back_ray and
 //              reverse.hpp project_point, with another source of eta).
 //   Rejected   A wavelength outside [360, 830] nm, or NaN, rejects that item alone, before anything else is looked at (as the

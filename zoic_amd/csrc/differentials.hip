@@ -1,23 +1,22 @@
 // differentials.hip -- the traced ray differentials (differentials.hpp): one pass over the records a ray launch wrote.
 //
-// Mapping: one ray per lane, wave64, 256-lane workgroups, a grid of at most 2048 workgroups striding over the batch a wave
-// (64 consecutive rays) at a time.  Tables arrive as by-value kernel arguments, as in the ray kernels: the interfaces are read
-// with scalar loads at a wave-uniform index.  A wave first reads the second half of its 64 records (weight, flags): if every
-// weight is 0 -- 79 % of a wide-open PETZVAL frame's rays -- it writes zeros and never reads a sample; otherwise only the live
-// lanes read theirs, replay their retry stream up to the accepted try (the loop runs to the wave's largest try count), rebuild
-// the lens point and trace one try with two tangents.  Results leave through a per-wave LDS transpose: the 48-byte outputs of a
-// wave are three fully coalesced 16-byte stores per lane (Arnold rows: 21 coalesced dword stores).  The pass itself is
-// differentials_device.hpp differentials_pass; this file holds the d-line ray functions and launchers.
+// Mapping: one ray per lane, the record pass of record_pass.hpp (launch shape: device_pass.hpp).  Tables arrive as by-value kernel
+// arguments, as in the ray kernels: the interfaces are read with scalar loads at a wave-uniform index.  A wave first reads the second
+// half of its 64 records (weight, flags): if every weight is 0 -- 79 % of a wide-open PETZVAL frame's rays -- it writes zeros and never
+// reads a sample; otherwise only the live lanes read theirs, replay their retry stream up to the accepted try (the loop runs to the
+// wave's largest try count), rebuild the lens point and trace one try with two tangents.  The 48-byte outputs of a wave leave as three
+// fully coalesced 16-byte stores per lane (Arnold rows: 21 coalesced dword stores).  The pass itself is record_pass.hpp
+// differentials_pass; this file holds the d-line ray functions and launchers.
 #include <hip/hip_runtime.h>
 
-#include "differentials_device.hpp"
+#include "record_pass.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 
 namespace zoic {
 namespace {
 
-// RAYTRACED: the accepted try's start (differentials_device.hpp), then one traced try with tangents
+// RAYTRACED: the accepted try's start (record_pass.hpp), then one traced try with tangents
 __device__ __forceinline__ RayDifferential kolb_ray(const KolbTable &T, const BokehTables &B, const float2 *lut, float4 s, uint32_t a,
                                                     const uint4 *rngStates, uint64_t rayBase, uint64_t i)
 {
@@ -29,20 +28,19 @@ __device__ __forceinline__ RayDifferential kolb_ray(const KolbTable &T, const Bo
 
 // budget: 0 scratch, 0 spills, <= 128 VGPRs (4 waves per SIMD)
 template <bool ROWS>
-__global__ __launch_bounds__(kDiffBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_differentials_kernel(
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_differentials_kernel(
     const KolbTable T, const BokehTables B, const float4 *__restrict__ samples, const float *__restrict__ inputs7,
     const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays, float dsx, float dsy,
     float *__restrict__ out)
 {
-    __shared__ __align__(16) float2 lut[kLutEntries];   // (maxScale, centroid.x) pairs of the exit-pupil LUT: setup_ray's lookup
-    if (threadIdx.x < kLutEntries) lut[threadIdx.x] = make_float2(T.lutMaxScale[threadIdx.x], T.lutCentroidX[threadIdx.x]);
-    __syncthreads();
+    __shared__ __align__(16) float2 lut[kLutEntries];
+    stage_lut(T, lut);
     differentials_pass<ROWS, false, false>([&](float4 s, uint32_t a, uint64_t i) { return kolb_ray(T, B, lut, s, a, rngStates, rayBase, i); },
                                            samples, inputs7, nullptr, rays, n, dsx, dsy, out, nullptr);
 }
 
 template <bool ROWS>
-__global__ __launch_bounds__(kDiffBlock) __attribute__((amdgpu_waves_per_eu(4))) void thin_differentials_kernel(
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void thin_differentials_kernel(
     const ThinTable T, const BokehTables B, const float4 *__restrict__ samples, const float *__restrict__ inputs7,
     const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays, float dsx, float dsy,
     float *__restrict__ out)
@@ -61,14 +59,9 @@ int launch_differentials(int model, const KolbTable &kolb, const ThinTable &thin
     const float4 *samples = ROWS ? nullptr : reinterpret_cast<const float4 *>(in);
     const float *inputs7 = ROWS ? in : nullptr;
     const uint4 *rng = reinterpret_cast<const uint4 *>(d_rng);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
     if (model == 1)
-        hipLaunchKernelGGL(kolb_differentials_kernel<ROWS>, dim3(diff_grid(n)), dim3(kDiffBlock), 0, s, kolb, bokeh, samples, inputs7, rng,
-                           rayBase, n, rays, dsx, dsy, out);
-    else
-        hipLaunchKernelGGL(thin_differentials_kernel<ROWS>, dim3(diff_grid(n)), dim3(kDiffBlock), 0, s, thin, bokeh, samples, inputs7, rng,
-                           rayBase, n, rays, dsx, dsy, out);
-    return static_cast<int>(hipGetLastError());
+        return launch_pass(kolb_differentials_kernel<ROWS>, pass_grid(n), stream, kolb, bokeh, samples, inputs7, rng, rayBase, n, rays, dsx, dsy, out);
+    return launch_pass(thin_differentials_kernel<ROWS>, pass_grid(n), stream, thin, bokeh, samples, inputs7, rng, rayBase, n, rays, dsx, dsy, out);
 }
 }  // namespace
 

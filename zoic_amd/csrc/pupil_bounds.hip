@@ -1,8 +1,8 @@
 // pupil_bounds.hip -- the batch pupil bounds (pupil_bounds.hpp), d-line and at a wavelength per point: two kernels (an instance per lens
 // model), one scene point per wave.
 //
-// Mapping: wave64, 256-lane workgroups, so four points per workgroup per step; a grid of at most kPbGridCap workgroups, whose waves
-// walk a larger batch with a grid stride.  The TraceBackTable (and, spectral, the BackwardDispersion) arrives by value as a kernel
+// Mapping: the launch shape of device_pass.hpp with a wave's point as the item, so four points per workgroup per step; the waves walk
+// a larger batch with a grid stride.  The TraceBackTable (and, spectral, the BackwardDispersion) arrives by value as a kernel
 // argument, and so do the lattice and the window: everything but the aim is wave-uniform, the interface loop's index included, so
 // every table entry stays one scalar load.  The point (12 bytes) and, spectral, its wavelength are loaded once per wave at a
 // wave-uniform address.  Lane l traces the aims l, l + 64, ...: G^2 / 64 of them, the same trip count in every lane, and keeps ten
@@ -13,6 +13,7 @@
 // whole body by a wave-uniform branch, and nothing is read or written past n.
 #include <hip/hip_runtime.h>
 
+#include "device_pass.hpp"
 #include "pupil_bounds.hpp"
 
 #pragma STDC FP_CONTRACT OFF
@@ -20,15 +21,7 @@
 namespace zoic {
 namespace {
 
-constexpr int kPbBlock = 256;
-constexpr int kPbWaves = kPbBlock / 64;   // points per workgroup per step
-constexpr uint64_t kPbGridCap = 2048;
-
-dim3 pb_grid(uint64_t n)
-{
-    const uint64_t blocks = (n + kPbWaves - 1) / kPbWaves;
-    return dim3(static_cast<uint32_t>(blocks < kPbGridCap ? blocks : kPbGridCap));
-}
+constexpr int kPbWaves = kPassBlock / 64;   // points per workgroup per step
 
 __device__ __forceinline__ float pb_xor(float v, int off) { return __shfl_xor(v, off, 64); }
 __device__ __forceinline__ uint32_t pb_xor(uint32_t v, int off) { return static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), off, 64)); }
@@ -75,35 +68,24 @@ __device__ __forceinline__ void pb_walk(const TraceBackTable &T, const float *__
 
 }  // namespace
 
-// The lens model is a template parameter: the host picks the instance of the camera's model, and the kernel tells the compiler which one
-// it is, so that each instance carries only its own model's trace (the table fields of the other one are not held in scalar registers
-// across the three loops).  kPbNoLens: every model that traces no ray (lensModel NONE).  Same operations, same bits.
-constexpr int kPbThin = 0, kPbKolb = 1, kPbNoLens = 2;
-
-template <int kModel>
-__device__ __forceinline__ void pb_model(const TraceBackTable &T)
-{
-    if (kModel == kPbNoLens) __builtin_assume(T.model != kPbThin && T.model != kPbKolb);
-    else __builtin_assume(T.model == kModel);
-}
-
+// The lens model is a template parameter (traceback.hpp assume_model / model_instance).
 // budget (all six): 0 scratch, 0 spills, 0 LDS
 template <int kModel>
-__global__ __launch_bounds__(kPbBlock) void pupil_bounds_kernel(const TraceBackTable T, const float *__restrict__ points, uint64_t n, int shift,
+__global__ __launch_bounds__(kPassBlock) void pupil_bounds_kernel(const TraceBackTable T, const float *__restrict__ points, uint64_t n, int shift,
                                                                 const PupilWindow W, float4 *__restrict__ bounds)
 {
-    pb_model<kModel>(T);
+    assume_model<kModel>(T);
     pb_walk(T, points, n, shift, W, bounds, [&](uint64_t, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy) {
         return trace_back_ray(T, ox, oy, oz, dx, dy, dz, sx, sy);
     });
 }
 
 template <int kModel>
-__global__ __launch_bounds__(kPbBlock) void pupil_bounds_spectral_kernel(const TraceBackTable T, const BackwardDispersion D,
+__global__ __launch_bounds__(kPassBlock) void pupil_bounds_spectral_kernel(const TraceBackTable T, const BackwardDispersion D,
                                                                          const float *__restrict__ points, const float *__restrict__ lambda,
                                                                          uint64_t n, int shift, const PupilWindow W, float4 *__restrict__ bounds)
 {
-    pb_model<kModel>(T);
+    assume_model<kModel>(T);
     pb_walk(T, points, n, shift, W, bounds, [&](uint64_t p, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy) {
         return trace_back_ray_spectral(T, D, lambda[p], ox, oy, oz, dx, dy, dz, sx, sy);
     });
@@ -113,10 +95,8 @@ int launch_pupil_bounds(const TraceBackTable &T, const float *d_points, uint64_t
 {
     if (n == 0) return 0;
     if (!pupil_lattice_valid(G)) return static_cast<int>(hipErrorInvalidValue);
-    const auto kernel = T.model == kPbThin ? pupil_bounds_kernel<kPbThin> : T.model == kPbKolb ? pupil_bounds_kernel<kPbKolb> : pupil_bounds_kernel<kPbNoLens>;
-    hipLaunchKernelGGL(kernel, pb_grid(n), dim3(kPbBlock), 0, static_cast<hipStream_t>(stream), T, d_points, n, pupil_shift(G), W,
-                       static_cast<float4 *>(d_bounds));
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = model_instance(T, pupil_bounds_kernel<kModelThin>, pupil_bounds_kernel<kModelKolb>, pupil_bounds_kernel<kModelNoLens>);
+    return launch_pass(kernel, pass_grid(n, kPbWaves), stream, T, d_points, n, pupil_shift(G), W, static_cast<float4 *>(d_bounds));
 }
 
 int launch_pupil_bounds_spectral(const TraceBackTable &T, const BackwardDispersion &D, const float *d_points, const float *d_lambda, uint64_t n,
@@ -124,12 +104,9 @@ int launch_pupil_bounds_spectral(const TraceBackTable &T, const BackwardDispersi
 {
     if (n == 0) return 0;
     if (!pupil_lattice_valid(G)) return static_cast<int>(hipErrorInvalidValue);
-    const auto kernel = T.model == kPbThin   ? pupil_bounds_spectral_kernel<kPbThin>
-                        : T.model == kPbKolb ? pupil_bounds_spectral_kernel<kPbKolb>
-                                             : pupil_bounds_spectral_kernel<kPbNoLens>;
-    hipLaunchKernelGGL(kernel, pb_grid(n), dim3(kPbBlock), 0, static_cast<hipStream_t>(stream), T, D, d_points, d_lambda, n, pupil_shift(G), W,
-                       static_cast<float4 *>(d_bounds));
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = model_instance(T, pupil_bounds_spectral_kernel<kModelThin>, pupil_bounds_spectral_kernel<kModelKolb>,
+                                       pupil_bounds_spectral_kernel<kModelNoLens>);
+    return launch_pass(kernel, pass_grid(n, kPbWaves), stream, T, D, d_points, d_lambda, n, pupil_shift(G), W, static_cast<float4 *>(d_bounds));
 }
 
 }  // namespace zoic

@@ -1,7 +1,8 @@
 // spectral.hip -- camera_create_ray (RAYTRACED, zoic.cpp:1850-1964) at a wavelength per ray (spectral.hpp has the model), and with
 // HERO at k wavelengths per sample: the hero's accepted try traced once more at each companion wavelength (hero.hpp has the contract).
 //
-// Mapping.  Persistent lanes: a wave claims CHUNKS of kSpecChunk consecutive samples (grid-stride over the batch) and each lane holds
+// Mapping.  The launch shape of device_pass.hpp with a wave's chunk as the item; the two small passes behind the thin-lens kernel walk
+// one row per lane (for_each_item).  Persistent lanes: a wave claims CHUNKS of kSpecChunk consecutive samples (grid-stride over the batch) and each lane holds
 // one sample until it is finished, then takes the next sample of the chunk (ballot + mbcnt).  A round of the wave's loop is
 //   * refill: free lanes take the chunk's next samples and set them up -- the reference's set-up arithmetic (setup_ray<true>: sensor
 //     point, exit-pupil LUT, parabola rotation), the sample's own lens point, the ray's wavelength;
@@ -26,37 +27,24 @@
 #include <hip/hip_runtime.h>
 
 #include "hero.hpp"
-#include "kolb_pool_body.hpp"
+#include "record_pass.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 
 namespace zoic {
 namespace {
 
-constexpr int kSpecBlock = 256;
 constexpr uint32_t kSpecChunk = 256;           // samples per claim of a wave: 4 per lane
 constexpr uint32_t kSpecMinSearching = 16;     // the search goes on while at least this many lanes are looking
-constexpr uint64_t kSpecGridCap = 2048;        // 8 waves per SIMD on 256 CUs
 
-// The kernels' argument list as a struct (HIP lays kernel arguments out like a C struct, kolb_pool_body.hpp KolbKernelArgs): the
-// traces read the tables through the kernarg segment (spectral.hpp ZOIC_SPEC_PIN).  T first: kernarg_fast_surfaces() (fast_optics.hpp)
-// counts on it.
+// The ray kernels' argument list (device_pass.hpp kernarg_view): the traces read the tables through the kernarg segment (spectral.hpp
+// ZOIC_SPEC_PIN).  T first: kernarg_fast_surfaces() (fast_optics.hpp) counts on it.
 struct SpectralKernelArgs {
     KolbTable T; SpectralTable W; BokehTables B; const float4 *samples; const float *lambdas; const uint4 *rngStates; uint64_t rayBase; uint64_t n;
     RayRecord *out; DeviceCounters *counters; uint32_t k;
 };
-typedef const Surface __attribute__((address_space(4))) *SurfaceTable;
-typedef const SpectralTable __attribute__((address_space(4))) *SpectralTablePtr;
-__device__ __forceinline__ SurfaceTable kernarg_surfaces()
-{
-    typedef const char __attribute__((address_space(4))) *KernargBytes;
-    return (SurfaceTable)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpectralKernelArgs, T) + offsetof(KolbTable, surf));
-}
-__device__ __forceinline__ SpectralTablePtr kernarg_spectral()
-{
-    typedef const char __attribute__((address_space(4))) *KernargBytes;
-    return (SpectralTablePtr)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpectralKernelArgs, W));
-}
+__device__ __forceinline__ auto kernarg_surfaces() { return kernarg_view<SpectralKernelArgs, Surface>(offsetof(SpectralKernelArgs, T) + offsetof(KolbTable, surf)); }
+__device__ __forceinline__ auto kernarg_spectral() { return kernarg_view<SpectralKernelArgs, SpectralTable>(offsetof(SpectralKernelArgs, W)); }
 
 __device__ __forceinline__ bool trace_strict(int count, float dl, V3 &o, V3 &d, uint32_t &tirCount)
 {
@@ -71,7 +59,7 @@ __device__ __forceinline__ bool trace_fast(int n, float dl, V3 &o, V3 &d, uint32
     V3 u{d.x * inv, d.y * inv, d.z * inv};
     float oAxis2 = fast_axis2(o);
     bool ok = true, refracted = false;
-    SpectralTablePtr W = kernarg_spectral();
+    auto W = kernarg_spectral();
     float n1 = ffma(W->cauchyB[0], dl, W->iorD[0]);
     for (int ii = 0; ii < n; ++ii) {
         const int i = __builtin_amdgcn_readfirstlane(ii);
@@ -115,7 +103,7 @@ __device__ __forceinline__ void store_zero_record(RayRecord *out, uint64_t at, u
 // the tail of the passes behind the thin-lens kernel: the counts it gave rejected rows are taken back (`flags`: such a row's record)
 __device__ __forceinline__ void count_taken_back(uint32_t flags, uint32_t &succ, uint32_t &vign)
 {
-    if (((flags >> 1) & 31u) > static_cast<uint32_t>(kMaxTries)) ++vign; else ++succ;
+    if (record_tries(flags) > static_cast<uint32_t>(kMaxTries)) ++vign; else ++succ;
 }
 __device__ __forceinline__ void take_back(DeviceCounters *counters, uint32_t succ, uint32_t vign)
 {
@@ -132,18 +120,17 @@ __device__ __forceinline__ void take_back(DeviceCounters *counters, uint32_t suc
 // budget: 0 scratch, 0 spills.  HERO: k = kRows wavelengths per sample, record (idx, col) at out[idx k + col]; otherwise k is 1 and every
 // hero-only statement below (col, hflags, hw, the saved start, the advance stage, the lost companions) is compiled away.
 template <bool FAST, bool HERO>
-__global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTable T, const SpectralTable W, const BokehTables B,
+__global__ __launch_bounds__(kPassBlock) void kolb_spectral_kernel(const KolbTable T, const SpectralTable W, const BokehTables B,
                                                                    const float4 *__restrict__ samples, const float *__restrict__ lambdas,
                                                                    const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
                                                                    RayRecord *__restrict__ out, DeviceCounters *counters, uint32_t kRows)
 {
     const uint32_t k = HERO ? kRows : 1u;
-    __shared__ __align__(16) float2 lut[kLutEntries];   // (maxScale, centroid.x) pairs of the exit-pupil LUT: setup_ray's lookup
-    if (threadIdx.x < kLutEntries) lut[threadIdx.x] = make_float2(T.lutMaxScale[threadIdx.x], T.lutCentroidX[threadIdx.x]);
-    __syncthreads();
+    __shared__ __align__(16) float2 lut[kLutEntries];
+    stage_lut(T, lut);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kSpecBlock / 64);
-    const uint64_t waveId = static_cast<uint64_t>(blockIdx.x) * (kSpecBlock / 64) + (threadIdx.x >> 6);
+    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kPassBlock / 64);
+    const uint64_t waveId = static_cast<uint64_t>(blockIdx.x) * (kPassBlock / 64) + (threadIdx.x >> 6);
     const uint32_t kOut = static_cast<uint32_t>(kMaxTries) + 1u;
     uint32_t succ = 0, vign = 0, tir = 0;
 
@@ -334,28 +321,26 @@ __global__ __launch_bounds__(kSpecBlock) void kolb_spectral_kernel(const KolbTab
 }
 
 // rows of the other lens models: invalid wavelengths -> a rejected record; the thin-lens kernel's count of that row is taken back
-__global__ __launch_bounds__(kSpecBlock) void spectral_reject_kernel(const float *__restrict__ lambdas, uint64_t n, RayRecord *__restrict__ out,
+__global__ __launch_bounds__(kPassBlock) void spectral_reject_kernel(const float *__restrict__ lambdas, uint64_t n, RayRecord *__restrict__ out,
                                                                      DeviceCounters *counters, int countsRays)
 {
     uint32_t succ = 0, vign = 0;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kSpecBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSpecBlock + threadIdx.x; i < n; i += stride) {
-        if (spectral_valid(lambdas[i])) continue;
+    for_each_item(n, [&](uint64_t i) {
+        if (spectral_valid(lambdas[i])) return;
         const uint32_t flags = out[i].flags;
         if (countsRays) count_taken_back(flags, succ, vign);
         store_zero_record(out, i, kSpectralRejected);
-    }
+    });
     take_back(counters, succ, vign);
 }
 
 // the same rows at k wavelengths: record i of the thin-lens kernel into the valid columns of row i, the others rejected; the count
 // of a row whose hero is rejected is taken back.  (Not the pass above at k = 1: that one works in place and writes rejected rows only.)
-__global__ __launch_bounds__(kSpecBlock) void hero_replicate_kernel(const RayRecord *__restrict__ staged, const float *__restrict__ lambdas, uint64_t n,
+__global__ __launch_bounds__(kPassBlock) void hero_replicate_kernel(const RayRecord *__restrict__ staged, const float *__restrict__ lambdas, uint64_t n,
                                                                     uint32_t k, RayRecord *__restrict__ out, DeviceCounters *counters, int countsRays)
 {
     uint32_t succ = 0, vign = 0;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kSpecBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSpecBlock + threadIdx.x; i < n; i += stride) {
+    for_each_item(n, [&](uint64_t i) {
         const float4 *p = reinterpret_cast<const float4 *>(staged + i);
         const float4 a = p[0], b = p[1];
         const uint32_t flags = __builtin_bit_cast(uint32_t, b.w);
@@ -366,17 +351,11 @@ __global__ __launch_bounds__(kSpecBlock) void hero_replicate_kernel(const RayRec
             if (hero && spectral_valid(lambdas[i * k + j])) store_ray_record(out, i * k + j, a.x, a.y, a.z, a.w, b.x, b.y, b.z, flags);
             else store_zero_record(out, i * k + j, kSpectralRejected);
         }
-    }
+    });
     take_back(counters, succ, vign);
 }
 
 namespace {
-uint32_t spec_grid(uint64_t n, uint64_t itemsPerBlock)
-{
-    const uint64_t blocks = (n + itemsPerBlock - 1) / itemsPerBlock;
-    return static_cast<uint32_t>(blocks < kSpecGridCap ? blocks : kSpecGridCap);
-}
-
 // k == 1: one wavelength per sample, the kernel without the hero's stages
 int launch_wavelength_rays(const KolbTable &table, const SpectralTable &spec, const BokehTables &bokeh, const float *d_samples,
                            const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, uint32_t k, RayRecord *out,
@@ -385,10 +364,8 @@ int launch_wavelength_rays(const KolbTable &table, const SpectralTable &spec, co
     if (n == 0) return 0;
     const auto kernel = k == 1u ? (mode == 0 ? kolb_spectral_kernel<false, false> : kolb_spectral_kernel<true, false>)
                                 : (mode == 0 ? kolb_spectral_kernel<false, true> : kolb_spectral_kernel<true, true>);
-    const dim3 grid(spec_grid(n, static_cast<uint64_t>(kSpecChunk) * (kSpecBlock / 64)));
-    hipLaunchKernelGGL(kernel, grid, dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), table, spec, bokeh,
+    return launch_pass(kernel, pass_grid(n, static_cast<uint64_t>(kSpecChunk) * (kPassBlock / 64)), stream, table, spec, bokeh,
                        reinterpret_cast<const float4 *>(d_samples), d_lambda, reinterpret_cast<const uint4 *>(d_rng), rayBase, n, out, d_counters, k);
-    return static_cast<int>(hipGetLastError());
 }
 }  // namespace
 
@@ -411,9 +388,7 @@ int launch_kolb_hero(const KolbTable &table, const SpectralTable &spec, const Bo
 int launch_spectral_reject(const float *d_lambda, uint64_t n, RayRecord *out, DeviceCounters *d_counters, bool countsRays, void *stream)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(spectral_reject_kernel, dim3(spec_grid(n, kSpecBlock)), dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), d_lambda, n, out,
-                       d_counters, countsRays ? 1 : 0);
-    return static_cast<int>(hipGetLastError());
+    return launch_pass(spectral_reject_kernel, pass_grid(n), stream, d_lambda, n, out, d_counters, countsRays ? 1 : 0);
 }
 
 int launch_hero_replicate(const RayRecord *staged, const float *d_lambda, uint64_t n, uint32_t k, RayRecord *out, DeviceCounters *d_counters,
@@ -421,9 +396,7 @@ int launch_hero_replicate(const RayRecord *staged, const float *d_lambda, uint64
 {
     if (n == 0) return 0;
     if (k < 2 || k > kHeroMaxWavelengths) return static_cast<int>(hipErrorInvalidValue);   // k = 1 is launch_spectral_reject
-    hipLaunchKernelGGL(hero_replicate_kernel, dim3(spec_grid(n, kSpecBlock)), dim3(kSpecBlock), 0, static_cast<hipStream_t>(stream), staged, d_lambda, n, k,
-                       out, d_counters, countsRays ? 1 : 0);
-    return static_cast<int>(hipGetLastError());
+    return launch_pass(hero_replicate_kernel, pass_grid(n), stream, staged, d_lambda, n, k, out, d_counters, countsRays ? 1 : 0);
 }
 
 }  // namespace zoic

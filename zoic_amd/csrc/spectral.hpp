@@ -50,13 +50,14 @@ inline float cauchy_b(float iorD, float abbe)
     return static_cast<float>(static_cast<double>(iorD - 1.0f) / (static_cast<double>(abbe) * span));
 }
 
+constexpr float kLambdaD32 = 587.5618f;   // the d-line in f32: the wavelength of a pass that is given none (spectral_dl gives exactly 0 there)
+
 ZOIC_HD bool spectral_valid(float lambda) { return lambda >= kLambdaMin && lambda <= kLambdaMax; }   // false for NaN
 
 // 1/lambda^2 - 1/lambda_d^2 in f32 (kInvD2 by the same f32 operations)
 ZOIC_HD float spectral_dl(float lambda)
 {
-    const float lambdaD = 587.5618f;
-    const float invD2 = 1.0f / (lambdaD * lambdaD);
+    const float invD2 = 1.0f / (kLambdaD32 * kLambdaD32);
     return 1.0f / (lambda * lambda) - invD2;
 }
 

@@ -1,48 +1,38 @@
 // spectral_differentials.hip -- the traced ray differentials of spectral records (differentials_spectral.hpp): one pass over the
 // records zoic_create_rays_spectral_device wrote.
 //
-// Mapping as differentials.hip, through the same pass (differentials_device.hpp differentials_pass with SPECTRAL): one ray per lane,
-// wave64, 256-lane workgroups, a grid of at most 2048 workgroups striding over the batch a wave (64 consecutive rays) at a time; the
-// all-dead-wave shortcut; the replay of the accepted try; results through a per-wave LDS transpose.  A lane reads one more dword, its
-// wavelength: a lane whose wavelength is invalid is not live, whatever its record says.  The dispersion table arrives by value like the interfaces and is read through the kernel-argument
-// segment (spectral.hpp ZOIC_SPEC_PIN) with scalar loads at the wave-uniform interface index.  CHROMATIC: the wavelength tangent is
-// traced in f64 after the screen tangents (kolb_wavelength_tangent) and its six floats leave through the same transpose as three
-// coalesced 8-byte stores per lane.
+// Mapping as differentials.hip, through the same pass (record_pass.hpp differentials_pass with SPECTRAL).  A lane reads one more dword,
+// its wavelength: a lane whose wavelength is invalid is not live, whatever its record says.  The dispersion table arrives by value like
+// the interfaces and is read through the kernel-argument segment (device_pass.hpp kernarg_view, spectral.hpp ZOIC_SPEC_PIN) with scalar
+// loads at the wave-uniform interface index.  CHROMATIC: the wavelength tangent is traced in f64 after the screen tangents
+// (kolb_wavelength_tangent) and its six floats leave through the same stage as three coalesced 8-byte stores per lane.
 #include <hip/hip_runtime.h>
 
-#include <cstddef>
-
-#include "differentials_device.hpp"
+#include "record_pass.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 
 namespace zoic {
 namespace {
 
-// The Kolb kernel's argument list as a struct (HIP lays kernel arguments out like a C struct, kolb_pool_body.hpp KolbKernelArgs)
+// the Kolb kernel's argument list (device_pass.hpp kernarg_view)
 struct SpectralDiffKernelArgs {
     KolbTable T; SpectralTable W; BokehTables B; const float4 *samples; const float *lambdas; const uint4 *rngStates; uint64_t rayBase; uint64_t n;
     const RayRecord *rays; float dsx; float dsy; float *out; float *chroma;
 };
-typedef const SpectralTable __attribute__((address_space(4))) *SpectralTablePtr;
-__device__ __forceinline__ SpectralTablePtr kernarg_spectral()
-{
-    typedef const char __attribute__((address_space(4))) *KernargBytes;
-    return (SpectralTablePtr)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SpectralDiffKernelArgs, W));
-}
+__device__ __forceinline__ auto kernarg_spectral() { return kernarg_view<SpectralDiffKernelArgs, SpectralTable>(offsetof(SpectralDiffKernelArgs, W)); }
 
 }  // namespace
 
 // budget: 0 scratch, 0 spills; <= 128 VGPRs (4 waves per SIMD) without the wavelength tangent, whose f64 trace may take more
 template <bool CHROMATIC>
-__global__ __launch_bounds__(kDiffBlock) __attribute__((amdgpu_waves_per_eu(CHROMATIC ? 2 : 4))) void kolb_spectral_diff_kernel(
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(CHROMATIC ? 2 : 4))) void kolb_spectral_diff_kernel(
     const KolbTable T, const SpectralTable W, const BokehTables B, const float4 *__restrict__ samples, const float *__restrict__ lambdas,
     const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays, float dsx, float dsy,
     float *__restrict__ out, float *__restrict__ chroma)
 {
-    __shared__ __align__(16) float2 lut[kLutEntries];   // (maxScale, centroid.x) pairs of the exit-pupil LUT: setup_ray's lookup
-    if (threadIdx.x < kLutEntries) lut[threadIdx.x] = make_float2(T.lutMaxScale[threadIdx.x], T.lutCentroidX[threadIdx.x]);
-    __syncthreads();
+    __shared__ __align__(16) float2 lut[kLutEntries];
+    stage_lut(T, lut);
     differentials_pass<false, true, CHROMATIC>(
         [&](float4 s, float lambda, uint32_t a, uint64_t i) {
             const auto surfAt = [&](int k) { return T.surf[__builtin_amdgcn_readfirstlane(k)]; };   // wave-uniform: scalar loads
@@ -55,7 +45,7 @@ __global__ __launch_bounds__(kDiffBlock) __attribute__((amdgpu_waves_per_eu(CHRO
 
 // THINLENS: the wavelength only rejects
 template <bool CHROMATIC>
-__global__ __launch_bounds__(kDiffBlock) __attribute__((amdgpu_waves_per_eu(4))) void thin_spectral_diff_kernel(
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void thin_spectral_diff_kernel(
     const ThinTable T, const BokehTables B, const float4 *__restrict__ samples, const float *__restrict__ lambdas,
     const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays, float dsx, float dsy,
     float *__restrict__ out, float *__restrict__ chroma)
@@ -71,15 +61,13 @@ namespace {
 template <bool CHROMATIC>
 int launch_spectral_diff(int model, const KolbTable &kolb, const SpectralTable &spec, const ThinTable &thin, const BokehTables &bokeh,
                          const float4 *samples, const float *d_lambda, const uint4 *rng, uint64_t rayBase, uint64_t n, const RayRecord *rays,
-                         float dsx, float dsy, float *out, float *chroma, hipStream_t s)
+                         float dsx, float dsy, float *out, float *chroma, void *stream)
 {
     if (model == 1)
-        hipLaunchKernelGGL(kolb_spectral_diff_kernel<CHROMATIC>, dim3(diff_grid(n)), dim3(kDiffBlock), 0, s, kolb, spec, bokeh, samples, d_lambda,
-                           rng, rayBase, n, rays, dsx, dsy, out, chroma);
-    else
-        hipLaunchKernelGGL(thin_spectral_diff_kernel<CHROMATIC>, dim3(diff_grid(n)), dim3(kDiffBlock), 0, s, thin, bokeh, samples, d_lambda, rng,
-                           rayBase, n, rays, dsx, dsy, out, chroma);
-    return static_cast<int>(hipGetLastError());
+        return launch_pass(kolb_spectral_diff_kernel<CHROMATIC>, pass_grid(n), stream, kolb, spec, bokeh, samples, d_lambda, rng, rayBase, n, rays,
+                           dsx, dsy, out, chroma);
+    return launch_pass(thin_spectral_diff_kernel<CHROMATIC>, pass_grid(n), stream, thin, bokeh, samples, d_lambda, rng, rayBase, n, rays, dsx, dsy,
+                       out, chroma);
 }
 }  // namespace
 
@@ -91,9 +79,8 @@ int launch_ray_differentials_spectral(int model, const KolbTable &kolb, const Sp
     if (n == 0) return 0;
     const float4 *samples = reinterpret_cast<const float4 *>(d_samples);
     const uint4 *rng = reinterpret_cast<const uint4 *>(d_rng);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    return d_chromatic ? launch_spectral_diff<true>(model, kolb, spec, thin, bokeh, samples, d_lambda, rng, rayBase, n, rays, dsx, dsy, d_out, d_chromatic, s)
-                       : launch_spectral_diff<false>(model, kolb, spec, thin, bokeh, samples, d_lambda, rng, rayBase, n, rays, dsx, dsy, d_out, nullptr, s);
+    return d_chromatic ? launch_spectral_diff<true>(model, kolb, spec, thin, bokeh, samples, d_lambda, rng, rayBase, n, rays, dsx, dsy, d_out, d_chromatic, stream)
+                       : launch_spectral_diff<false>(model, kolb, spec, thin, bokeh, samples, d_lambda, rng, rayBase, n, rays, dsx, dsy, d_out, nullptr, stream);
 }
 
 }  // namespace zoic

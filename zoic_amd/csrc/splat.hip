@@ -1,9 +1,8 @@
 // splat.hip -- the batch lens splats (splat.hpp), d-line and at a wavelength per point: two kernels (an instance per lens model), one
 // splat per lane.
 //
-// Mapping: wave64, 256-lane workgroups, a grid of at most kSpGridCap workgroups whose lanes walk the n m splats with a grid stride (a
-// 64-bit index).  Splat i belongs to point p = i / m; the lane takes that quotient once, in 32 bits (its first index is below
-// kSpGridCap x 256 = 2^19), and then steps p and the remainder by the stride's own quotient and remainder, which are wave-uniform:
+// Mapping: the launch shape of device_pass.hpp, whose lanes walk the n m splats with a grid stride (a 64-bit index).  Splat i belongs
+// to point p = i / m; the lane takes that quotient once, in 32 bits (its first index is below kPassGridCap x kPassBlock = 2^19), and then steps p and the remainder by the stride's own quotient and remainder, which are wave-uniform:
 // no 64-bit division anywhere.  The TraceBackTable (and, spectral, the BackwardDispersion) arrives by value as a kernel argument, so
 // the interface loop keeps its scalar table loads, as in traceback.hip.  A lane loads its point (12 bytes), the box row and the
 // count / flags row of the point's pupil-bounds record (16 bytes each; the middle row, the blur spot's box, is not read) and, spectral,
@@ -14,6 +13,7 @@
 // past n m.
 #include <hip/hip_runtime.h>
 
+#include "device_pass.hpp"
 #include "splat.hpp"
 
 #pragma STDC FP_CONTRACT OFF
@@ -21,23 +21,14 @@
 namespace zoic {
 namespace {
 
-constexpr int kSpBlock = 256;
-constexpr uint64_t kSpGridCap = 2048;
-
-dim3 sp_grid(uint64_t total)
-{
-    const uint64_t blocks = (total + kSpBlock - 1) / kSpBlock;
-    return dim3(static_cast<uint32_t>(blocks < kSpGridCap ? blocks : kSpGridCap));
-}
-
 // the grid-stride walk of both kernels: trace(p, ox, oy, oz, dx, dy, dz, sx, sy, J) returns the flag word of one ray from point p
 template <class Trace>
 __device__ __forceinline__ void sp_walk(const TraceBackTable &T, const float *__restrict__ points, const float4 *__restrict__ bounds, uint64_t total,
                                         uint32_t m, const float2 *__restrict__ u, float4 *__restrict__ splats, Trace trace)
 {
     const float z = splat_plane(T);
-    const uint32_t stride = gridDim.x * static_cast<uint32_t>(kSpBlock);   // <= 2^19
-    const uint32_t first = blockIdx.x * static_cast<uint32_t>(kSpBlock) + threadIdx.x;
+    const uint32_t stride = gridDim.x * static_cast<uint32_t>(kPassBlock);   // <= 2^19
+    const uint32_t first = blockIdx.x * static_cast<uint32_t>(kPassBlock) + threadIdx.x;
     const uint32_t stepP = stride / m, stepJ = stride % m;                  // wave-uniform
     uint64_t p = first / m;
     uint32_t j = first % m;
@@ -60,24 +51,13 @@ __device__ __forceinline__ void sp_walk(const TraceBackTable &T, const float *__
 
 }  // namespace
 
-// The lens model is a template parameter, as in pupil_bounds.hip: the host picks the instance of the camera's model, and the kernel
-// tells the compiler which one it is, so that each instance carries only its own model's trace.  kSpNoLens: every model that traces
-// no ray (lensModel NONE).  Same operations, same bits.
-constexpr int kSpThin = 0, kSpKolb = 1, kSpNoLens = 2;
-
-template <int kModel>
-__device__ __forceinline__ void sp_model(const TraceBackTable &T)
-{
-    if (kModel == kSpNoLens) __builtin_assume(T.model != kSpThin && T.model != kSpKolb);
-    else __builtin_assume(T.model == kModel);
-}
-
+// The lens model is a template parameter (traceback.hpp assume_model / model_instance).
 // budget (all six): 0 scratch, 0 spills, 0 LDS
 template <int kModel>
-__global__ __launch_bounds__(kSpBlock) void splat_kernel(const TraceBackTable T, const float *__restrict__ points, const float4 *__restrict__ bounds,
+__global__ __launch_bounds__(kPassBlock) void splat_kernel(const TraceBackTable T, const float *__restrict__ points, const float4 *__restrict__ bounds,
                                                          uint64_t total, uint32_t m, const float2 *__restrict__ u, float4 *__restrict__ splats)
 {
-    sp_model<kModel>(T);
+    assume_model<kModel>(T);
     sp_walk(T, points, bounds, total, m, u, splats,
             [&](uint64_t, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy, float *J) {
                 return trace_back_ray_jacobian(T, ox, oy, oz, dx, dy, dz, sx, sy, J);
@@ -85,12 +65,12 @@ __global__ __launch_bounds__(kSpBlock) void splat_kernel(const TraceBackTable T,
 }
 
 template <int kModel>
-__global__ __launch_bounds__(kSpBlock) void splat_spectral_kernel(const TraceBackTable T, const BackwardDispersion D, const float *__restrict__ points,
+__global__ __launch_bounds__(kPassBlock) void splat_spectral_kernel(const TraceBackTable T, const BackwardDispersion D, const float *__restrict__ points,
                                                                   const float4 *__restrict__ bounds, const float *__restrict__ lambda,
                                                                   uint64_t total, uint32_t m, const float2 *__restrict__ u,
                                                                   float4 *__restrict__ splats)
 {
-    sp_model<kModel>(T);
+    assume_model<kModel>(T);
     sp_walk(T, points, bounds, total, m, u, splats,
             [&](uint64_t p, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy, float *J) {
                 return trace_back_ray_jacobian_spectral(T, D, lambda[p], ox, oy, oz, dx, dy, dz, sx, sy, J);
@@ -103,10 +83,9 @@ int launch_splat_points(const TraceBackTable &T, const float *d_points, const vo
     if (n == 0) return 0;
     if (m == 0) return static_cast<int>(hipErrorInvalidValue);
     const uint64_t total = n * m;
-    const auto kernel = T.model == kSpThin ? splat_kernel<kSpThin> : T.model == kSpKolb ? splat_kernel<kSpKolb> : splat_kernel<kSpNoLens>;
-    hipLaunchKernelGGL(kernel, sp_grid(total), dim3(kSpBlock), 0, static_cast<hipStream_t>(stream), T, d_points,
-                       static_cast<const float4 *>(d_bounds), total, m, reinterpret_cast<const float2 *>(d_u), static_cast<float4 *>(d_splats));
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = model_instance(T, splat_kernel<kModelThin>, splat_kernel<kModelKolb>, splat_kernel<kModelNoLens>);
+    return launch_pass(kernel, pass_grid(total), stream, T, d_points, static_cast<const float4 *>(d_bounds), total, m,
+                       reinterpret_cast<const float2 *>(d_u), static_cast<float4 *>(d_splats));
 }
 
 int launch_splat_points_spectral(const TraceBackTable &T, const BackwardDispersion &D, const float *d_points, const void *d_bounds,
@@ -115,13 +94,9 @@ int launch_splat_points_spectral(const TraceBackTable &T, const BackwardDispersi
     if (n == 0) return 0;
     if (m == 0) return static_cast<int>(hipErrorInvalidValue);
     const uint64_t total = n * m;
-    const auto kernel = T.model == kSpThin   ? splat_spectral_kernel<kSpThin>
-                        : T.model == kSpKolb ? splat_spectral_kernel<kSpKolb>
-                                             : splat_spectral_kernel<kSpNoLens>;
-    hipLaunchKernelGGL(kernel, sp_grid(total), dim3(kSpBlock), 0, static_cast<hipStream_t>(stream), T, D, d_points,
-                       static_cast<const float4 *>(d_bounds), d_lambda, total, m, reinterpret_cast<const float2 *>(d_u),
-                       static_cast<float4 *>(d_splats));
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = model_instance(T, splat_spectral_kernel<kModelThin>, splat_spectral_kernel<kModelKolb>, splat_spectral_kernel<kModelNoLens>);
+    return launch_pass(kernel, pass_grid(total), stream, T, D, d_points, static_cast<const float4 *>(d_bounds), d_lambda, total, m,
+                       reinterpret_cast<const float2 *>(d_u), static_cast<float4 *>(d_splats));
 }
 
 }  // namespace zoic

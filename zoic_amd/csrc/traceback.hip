@@ -1,8 +1,7 @@
 // traceback.hip -- the batch trace-back (traceback.hpp), at a wavelength per ray (backward_spectral.hpp) and with its Jacobian
 // (traceback_jacobian.hpp): four kernels, one camera ray per lane.
 //
-// Mapping: wave64, 256-lane workgroups, a grid of at most kTbGridCap workgroups; a batch larger than one grid's worth (a slab of
-// kTbGridCap x 256 rays) is walked slab by slab by the same lanes.  The TraceBackTable (and, spectral, the BackwardDispersion) arrives
+// Mapping: the launch shape and the one-item-per-lane walk of device_pass.hpp.  The TraceBackTable (and, spectral, the BackwardDispersion) arrives
 // by value as a kernel argument: the interface loop's index is wave-uniform, so every table entry is one 16-byte scalar load (the
 // dispersion entry: one 8-byte load).  No LDS, no scratch.  A lane reads its 32-byte record as two 16-byte loads (a wave's 2 KiB are
 // contiguous; the compiler narrows the second to the 8 bytes that are used) and, spectral, one more coalesced dword, its wavelength
@@ -12,6 +11,7 @@
 // bytes of J as three 16-byte stores (a wave's 3 KiB are contiguous).
 #include <hip/hip_runtime.h>
 
+#include "device_pass.hpp"
 #include "traceback_jacobian.hpp"
 
 #pragma STDC FP_CONTRACT OFF
@@ -19,28 +19,18 @@
 namespace zoic {
 namespace {
 
-constexpr int kTbBlock = 256;
-constexpr uint64_t kTbGridCap = 2048;
-
-dim3 tb_grid(uint64_t n)
-{
-    const uint64_t blocks = (n + kTbBlock - 1) / kTbBlock;
-    return dim3(static_cast<uint32_t>(blocks < kTbGridCap ? blocks : kTbGridCap));
-}
-
-// the grid-stride walk of the four kernels: trace(i, ox, oy, oz, dx, dy, dz, sx, sy) returns ray i's flag word
+// the walk of the four kernels: trace(i, ox, oy, oz, dx, dy, dz, sx, sy) returns ray i's flag word
 template <class Trace>
 __device__ __forceinline__ void tb_walk(const float4 *__restrict__ rays, uint64_t n, float2 *__restrict__ screen, uint32_t *__restrict__ flags,
                                         Trace trace)
 {
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kTbBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTbBlock + threadIdx.x; i < n; i += stride) {
+    for_each_item(n, [&](uint64_t i) {
         const float4 a = rays[2u * i], b = rays[2u * i + 1u];   // ox oy oz dx | dy dz weight flags
         float sx, sy;
         const uint32_t f = trace(i, a.x, a.y, a.z, a.w, b.x, b.y, sx, sy);
         screen[i] = make_float2(sx, sy);
         if (flags) flags[i] = f;
-    }
+    });
 }
 
 __device__ __forceinline__ void store_jacobian(float4 *__restrict__ jac, uint64_t i, const float *J)
@@ -53,7 +43,7 @@ __device__ __forceinline__ void store_jacobian(float4 *__restrict__ jac, uint64_
 }  // namespace
 
 // budget (all four): 0 scratch, 0 spills, 0 LDS; the spectral trace-back at most 64 VGPRs (8 waves per SIMD)
-__global__ __launch_bounds__(kTbBlock) void trace_back_kernel(const TraceBackTable T, const float4 *__restrict__ rays, uint64_t n,
+__global__ __launch_bounds__(kPassBlock) void trace_back_kernel(const TraceBackTable T, const float4 *__restrict__ rays, uint64_t n,
                                                               float2 *__restrict__ screen, uint32_t *__restrict__ flags)
 {
     tb_walk(rays, n, screen, flags, [&](uint64_t, float ox, float oy, float oz, float dx, float dy, float dz, float &sx, float &sy) {
@@ -61,7 +51,7 @@ __global__ __launch_bounds__(kTbBlock) void trace_back_kernel(const TraceBackTab
     });
 }
 
-__global__ __launch_bounds__(kTbBlock) void trace_back_spectral_kernel(const TraceBackTable T, const BackwardDispersion D,
+__global__ __launch_bounds__(kPassBlock) void trace_back_spectral_kernel(const TraceBackTable T, const BackwardDispersion D,
                                                                        const float4 *__restrict__ rays, const float *__restrict__ lambda,
                                                                        uint64_t n, float2 *__restrict__ screen, uint32_t *__restrict__ flags)
 {
@@ -70,7 +60,7 @@ __global__ __launch_bounds__(kTbBlock) void trace_back_spectral_kernel(const Tra
     });
 }
 
-__global__ __launch_bounds__(kTbBlock) void trace_back_jacobian_kernel(const TraceBackTable T, const float4 *__restrict__ rays, uint64_t n,
+__global__ __launch_bounds__(kPassBlock) void trace_back_jacobian_kernel(const TraceBackTable T, const float4 *__restrict__ rays, uint64_t n,
                                                                        float2 *__restrict__ screen, uint32_t *__restrict__ flags,
                                                                        float4 *__restrict__ jac)
 {
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(kTbBlock) void trace_back_jacobian_kernel(const Tra
     });
 }
 
-__global__ __launch_bounds__(kTbBlock) void trace_back_jacobian_spectral_kernel(const TraceBackTable T, const BackwardDispersion D,
+__global__ __launch_bounds__(kPassBlock) void trace_back_jacobian_spectral_kernel(const TraceBackTable T, const BackwardDispersion D,
                                                                                 const float4 *__restrict__ rays,
                                                                                 const float *__restrict__ lambda, uint64_t n,
                                                                                 float2 *__restrict__ screen, uint32_t *__restrict__ flags,
@@ -99,38 +89,34 @@ __global__ __launch_bounds__(kTbBlock) void trace_back_jacobian_spectral_kernel(
 int launch_trace_back(const TraceBackTable &T, const void *d_rays, uint64_t n, float *d_screen, uint32_t *d_flags, void *stream)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(trace_back_kernel, tb_grid(n), dim3(kTbBlock), 0, static_cast<hipStream_t>(stream), T, static_cast<const float4 *>(d_rays),
+    return launch_pass(trace_back_kernel, pass_grid(n), stream, T, static_cast<const float4 *>(d_rays),
                        n, reinterpret_cast<float2 *>(d_screen), d_flags);
-    return static_cast<int>(hipGetLastError());
 }
 
 int launch_trace_back_spectral(const TraceBackTable &T, const BackwardDispersion &D, const void *d_rays, const float *d_lambda, uint64_t n,
                                float *d_screen, uint32_t *d_flags, void *stream)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(trace_back_spectral_kernel, tb_grid(n), dim3(kTbBlock), 0, static_cast<hipStream_t>(stream), T, D,
+    return launch_pass(trace_back_spectral_kernel, pass_grid(n), stream, T, D,
                        static_cast<const float4 *>(d_rays), d_lambda, n, reinterpret_cast<float2 *>(d_screen), d_flags);
-    return static_cast<int>(hipGetLastError());
 }
 
 int launch_trace_back_jacobian(const TraceBackTable &T, const void *d_rays, uint64_t n, float *d_screen, uint32_t *d_flags, float *d_jacobian,
                                void *stream)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(trace_back_jacobian_kernel, tb_grid(n), dim3(kTbBlock), 0, static_cast<hipStream_t>(stream), T,
+    return launch_pass(trace_back_jacobian_kernel, pass_grid(n), stream, T,
                        static_cast<const float4 *>(d_rays), n, reinterpret_cast<float2 *>(d_screen), d_flags,
                        reinterpret_cast<float4 *>(d_jacobian));
-    return static_cast<int>(hipGetLastError());
 }
 
 int launch_trace_back_jacobian_spectral(const TraceBackTable &T, const BackwardDispersion &D, const void *d_rays, const float *d_lambda,
                                         uint64_t n, float *d_screen, uint32_t *d_flags, float *d_jacobian, void *stream)
 {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(trace_back_jacobian_spectral_kernel, tb_grid(n), dim3(kTbBlock), 0, static_cast<hipStream_t>(stream), T, D,
+    return launch_pass(trace_back_jacobian_spectral_kernel, pass_grid(n), stream, T, D,
                        static_cast<const float4 *>(d_rays), d_lambda, n, reinterpret_cast<float2 *>(d_screen), d_flags,
                        reinterpret_cast<float4 *>(d_jacobian));
-    return static_cast<int>(hipGetLastError());
 }
 
 }  // namespace zoic

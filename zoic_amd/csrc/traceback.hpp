@@ -109,6 +109,27 @@ struct TraceBackTable {
     TbSurface surf[kMaxSurfaces];
 };
 
+// Kernels with an instance per lens model (pupil_bounds.hip, splat.hip): the host picks the instance of the camera's model, and the
+// kernel tells the compiler which one it is, so that each instance carries only its own model's trace (the table fields of the other
+// one are not held in scalar registers across its loops).  kModelNoLens: every model that traces no ray (lensModel NONE).  Same
+// operations, same bits.
+constexpr int kModelThin = 0, kModelKolb = 1, kModelNoLens = 2;
+
+template <class Kernel>
+inline Kernel model_instance(const TraceBackTable &T, Kernel thin, Kernel kolb, Kernel noLens)
+{
+    return T.model == kModelThin ? thin : T.model == kModelKolb ? kolb : noLens;
+}
+
+#if defined(__HIPCC__)
+template <int kModel>
+__device__ __forceinline__ void assume_model(const TraceBackTable &T)
+{
+    if (kModel == kModelNoLens) __builtin_assume(T.model != kModelThin && T.model != kModelKolb);
+    else __builtin_assume(T.model == kModel);
+}
+#endif
+
 ZOIC_HD int tb_uniform(int j)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -33,7 +33,7 @@
 //              "Building an orthonormal basis, revisited", JCGT 2017, for u.z < 0: 1 - u.z >= 1, no cancellation at any angle).
 //              d(x, y)/d origin = [-1 0 dx/dz; 0 -1 dy/dz];  d(x, y)/d dir = s [1 0 -dx/dz; 0 1 -dy/dz];
 //              du/d dir = (I - u u^T) / |dir|, whose coordinates in (e1, e2) are e1^T / |dir| and e2^T / |dir|.
-//   Interface  Igehy's transfer and refraction (differentials_device.hpp applies them in the forward direction), per tangent:
+//   Interface  Igehy's transfer and refraction (record_pass.hpp applies them in the forward direction), per tangent:
 //              dt = -n . (dp + t du) / (n . u);  dh = dp + t du + u dt;  dn = c dh;  dcos = -(du . n + u . dn);
 //              d sqrt(k2) = eta^2 cos dcos / sqrt(k2), so dg = dcos (eta - eta^2 cos / sqrt(k2)) = dcos (-eta g / sqrt(k2));
 //              du' = eta du + dg n + g dn;  dz follows z + S.dz unchanged.
