@@ -787,6 +787,48 @@ zoic_status zoic_splat_point(const zoic_camera *cam, const zoic_vec3 *Po, const 
 zoic_status zoic_splat_point_spectral(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, float wavelength_nm,
                                       uint32_t m, const float *u /* m x 2 */, zoic_splat *splats /* m */);
 
+/* ---- trace-back transmittance: the Fresnel losses of backward lens paths (opt-in; csrc/traceback_throughput.hpp has the full definition) --
+ * The backward calls above return geometry; the forward side's zoic_ray_transmittance_device says how much light the glass lets
+ * through.  These calls give the same factor for a ray traced BACK, so that a light tracer, a splatter or a bidirectional integrator
+ * weights both directions by the same lens: T = the product over the interfaces, front to rear, of the unpolarised Fresnel
+ * transmittance of each, bare or with the interface's quarter-wave film (zoic_camera_set_coatings), at the ray's wavelength (the d-line
+ * forms: 587.5618 nm), from the cosines and indices of the trace-back's own path.  No absorption.
+ *   T          a traced ray (ZOIC_TRACED_BACK): a number in (0, 1].  Anything else -- every refusal reason, a wavelength outside
+ *              [360, 830] nm or NaN -- gets +0.0.  THINLENS with depth of field: 1.0 where traced.  NONE, THINLENS without: +0.0.
+ *   Ps, flags  the bits of the spectral trace-back call for every input (the d-line forms: of the d-line call); T rides along.
+ *   Reciprocal the T of a forward record traced back equals zoic_ray_transmittance_device's T of that record, to rounding.
+ *   Splat side the T of the very rays the two device splat calls trace (same point, bounds record, m and u): multiply a splat's weight
+ *              by it.  A point with an empty box (ZOIC_SPLAT_NO_BOX) gets +0.0.
+ * The films and the dispersion are read at the call: a zoic_camera_set_coatings or zoic_camera_set_abbe_numbers change needs no update.
+ * The device calls and the host calls give the same bits for the same item in every precision mode.
+ * Arguments, error codes, alignment, stream semantics and the threading contract: the ray side as the spectral trace-back device call,
+ * the splat side as the spectral splat device call, except that d_screen and d_flags may both be NULL.  d_transmittance: floats, device
+ * memory, 4-byte aligned.  n = 0 returns ZOIC_OK; m = 0 with n > 0 is ZOIC_ERR_INVALID_ARGUMENT; ZOIC_ERR_NO_DEVICE on a tables-only
+ * camera.  No output is written on an argument error; no counter and no retry stream is touched. */
+zoic_status zoic_trace_back_transmittance_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_transmittance /* n */,
+                                                 float *d_screen /* n x 2, may be NULL */, uint32_t *d_flags /* may be NULL */, void *stream);
+zoic_status zoic_trace_back_transmittance_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays,
+                                                          const float *d_wavelengths /* n */, float *d_transmittance /* n */,
+                                                          float *d_screen /* n x 2, may be NULL */, uint32_t *d_flags /* may be NULL */,
+                                                          void *stream);
+zoic_status zoic_splat_transmittance_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */,
+                                            const zoic_pupil_bounds *d_bounds /* n */, uint32_t m, const float *d_u /* n x m x 2 */,
+                                            float *d_transmittance /* n x m */, void *stream);
+zoic_status zoic_splat_transmittance_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points /* n x 3 */,
+                                                     const zoic_pupil_bounds *d_bounds /* n */, const float *d_wavelengths /* n */, uint32_t m,
+                                                     const float *d_u /* n x m x 2 */, float *d_transmittance /* n x m */, void *stream);
+/* The host build of the same code for one ray, and for one point and its m aims (works on a ZOIC_DEVICE_NONE camera).  u and T of the
+ * splat forms: host memory, 4-byte aligned; m = 0, a NULL pointer and a misaligned u or T are ZOIC_ERR_INVALID_ARGUMENT: T is not written. */
+zoic_status zoic_trace_back_ray_transmittance(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir,
+                                              float *Ps /* [2], may be NULL */, uint32_t *flags /* may be NULL */, float *T);
+zoic_status zoic_trace_back_ray_transmittance_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir,
+                                                       float wavelength_nm, float *Ps /* [2], may be NULL */,
+                                                       uint32_t *flags /* may be NULL */, float *T);
+zoic_status zoic_splat_point_transmittance(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, uint32_t m,
+                                           const float *u /* m x 2 */, float *T /* m */);
+zoic_status zoic_splat_point_transmittance_spectral(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds,
+                                                    float wavelength_nm, uint32_t m, const float *u /* m x 2 */, float *T /* m */);
+
 /* Page-locked host memory for the buffers of zoic_create_rays_host: with pinned samples/rays the call runs as a
  * three-stream pipeline (copy-in of piece k+2, trace of piece k+1 and copy-out of piece k at once) at PCIe rate.  zoic_host_register pins
  * memory the caller already owns (keep it registered across calls: registration costs more than one transfer). */

@@ -171,6 +171,14 @@ SYMBOLS = {
     "zoic_splat_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "zoic_splat_point": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(PupilBounds), _u32, _vp, _vp]),
     "zoic_splat_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(PupilBounds), C.c_float, _u32, _vp, _vp]),
+    "zoic_trace_back_transmittance_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "zoic_trace_back_transmittance_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zoic_trace_back_ray_transmittance": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(C.c_float)]),
+    "zoic_trace_back_ray_transmittance_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32), C.POINTER(C.c_float)]),
+    "zoic_splat_transmittance_device": (C.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "zoic_splat_transmittance_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "zoic_splat_point_transmittance": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(PupilBounds), _u32, _vp, _vp]),
+    "zoic_splat_point_transmittance_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.POINTER(PupilBounds), C.c_float, _u32, _vp, _vp]),
     "zoic_project_points_spectral_device": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zoic_project_point_spectral": (C.c_int, [_vp, C.POINTER(Vec3), C.c_float, C.POINTER(C.c_float), C.POINTER(_u32)]),
     "zoic_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),

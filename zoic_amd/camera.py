@@ -758,6 +758,11 @@ class ZoicCamera:
         det d(sx, sy)/d(ax, ay), angle = dPs/d(omega) and the trace-back's flags, or _capi.SPLAT_NO_BOX for an empty box
         (csrc/splat.hpp).  Draws nothing: u is the caller's.  Works on a tables-only camera (device=-1).
         wavelength (nm): the trace at that wavelength (zoic_splat_point_spectral)."""
+        return self._splat_item(self._lib.zoic_splat_point, self._lib.zoic_splat_point_spectral, Po, bounds, u, wavelength, _capi.SPLAT_DTYPE)
+
+    def _splat_item(self, dline, spectral, Po, bounds, u, wavelength, dtype):
+        """the host single-point wrappers' call of the splat family: the (m,) array of `dtype` both entry points write for Po, its
+        bounds (the dict of pupil_bounds_point, or one record) and the aims u (m,2)"""
         po = _capi.Vec3(*[float(v) for v in Po])
         if isinstance(bounds, dict):
             rec = np.zeros(1, _capi.PUPIL_BOUNDS_DTYPE)
@@ -771,10 +776,9 @@ class ZoicCamera:
         if uu.ndim != 2 or uu.shape[1] != 2:
             raise ValueError("u must be (m, 2)")
         m = uu.shape[0]
-        out = np.zeros(m, _capi.SPLAT_DTYPE)
+        out = np.zeros(m, dtype)
         up, op = uu.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
-        self._spectral_or(self._lib.zoic_splat_point, self._lib.zoic_splat_point_spectral, None if wavelength is None else float(wavelength),
-                          (C.byref(po), C.byref(b)), (m, up, op))
+        self._spectral_or(dline, spectral, None if wavelength is None else float(wavelength), (C.byref(po), C.byref(b)), (m, up, op))
         return out
 
     def splat_points(self, points, bounds, u, wavelengths=None, out=None, stream=None):
@@ -805,6 +809,84 @@ class ZoicCamera:
         out = self._result("out", out, (n, m, 8), points)
         lam = self._wavelength_pointer(wavelengths, n)
         self._spectral_or(self._lib.zoic_splat_points_device, self._lib.zoic_splat_points_spectral_device, lam,
+                          (n, points.data_ptr(), bounds.data_ptr()), (m, u.data_ptr(), out.data_ptr(), self._stream(stream)))
+        return out
+
+    def trace_back_ray_transmittance(self, origin, dir, wavelength=None):
+        """Trace-back of one camera ray on the host with its Fresnel transmittance (zoic_trace_back_ray_transmittance): (sx, sy, flags,
+        T).  sx, sy and flags are trace_back_ray's bit for bit; T is the share of unpolarised light the interfaces let through along
+        that path, front to rear, bare or with the films of set_coatings: in (0, 1] where flags bit 0 is set, +0.0 otherwise; 1.0
+        for a traced THINLENS ray (csrc/traceback_throughput.hpp).  Works on a tables-only camera (device=-1).
+        wavelength (nm): the trace and the films at that wavelength (zoic_trace_back_ray_transmittance_spectral); None: the d-line."""
+        t = C.c_float(0.0)
+        return self._screen_sample(self._lib.zoic_trace_back_ray_transmittance, self._lib.zoic_trace_back_ray_transmittance_spectral,
+                                   (origin, dir), wavelength, C.byref(t)) + (float(t.value),)
+
+    def trace_back_transmittance(self, rays, wavelengths=None, out=None, screen=None, flags=None, stream=None):
+        """Trace-back of n camera rays with the Fresnel transmittance of each backward path (zoic_trace_back_transmittance_device):
+        returns (T (n,) float32, screen (n,2) float32, flags (n,) int32).  screen and flags are trace_back's bit for bit; T[i] is in
+        (0, 1] where bit 0 of flags[i] is set and +0.0 elsewhere (csrc/traceback_throughput.hpp).  For the records of a forward call
+        T equals what transmittance() gives for them, to rounding.  The films (set_coatings) and the dispersion (set_abbe_numbers)
+        are read at the call.
+
+        rays, wavelengths, stream: as trace_back takes them -- an (n,8) float32 device tensor of zoic_ray records or the dict a
+                     create_rays call on device tensors returned (its "rays" buffer is read in place), asynchronous on `stream`
+                     (default: torch's current stream); or numpy ((n,) zoic_ray records, the dict of a numpy create_rays call, or an
+                     (n,8) float32 array): copied to the camera's device through torch, the call waits and returns numpy arrays.
+                     wavelengths: (n,) float32 (nm), numpy with numpy rays, a device tensor with device rays
+                     (zoic_trace_back_transmittance_spectral_device); None: the d-line call.
+        out / screen / flags: optional (n,) float32, (n,2) float32 and (n,) int32 tensors on the rays' device to write into (torch
+                     rays only; they must be None with numpy rays)."""
+        lib = self._lib
+        rays = _records(rays)
+        if not _is_torch(rays):
+            res = self._through_device(
+                "rays", 8, rays, [("wavelengths", wavelengths, _f32_flat)], dict(out=out, screen=screen, flags=flags),
+                lambda a, w: lib.zoic_trace_back_transmittance_device(self._h, len(a), None, None, None, None, None),
+                lambda t, w: self.trace_back_transmittance(t, w))
+            return tuple(t.cpu().numpy() for t in res)
+        n = self._device_tensor("rays", rays, (None, 8)).shape[0]
+        res = [self._result("out", out, (n,), rays), self._result("screen", screen, (n, 2), rays),
+               self._result("flags", flags, (n,), rays, ints=True)]
+        w = self._wavelength_pointer(wavelengths, n)
+        self._spectral_or(lib.zoic_trace_back_transmittance_device, lib.zoic_trace_back_transmittance_spectral_device, w,
+                          (n, rays.data_ptr()), [t.data_ptr() for t in res] + [self._stream(stream)])
+        return tuple(res)
+
+    def splat_point_transmittance(self, Po, bounds, u, wavelength=None):
+        """The Fresnel transmittance of the m rays splat_point traces for one scene point, on the host
+        (zoic_splat_point_transmittance): (m,) float32, T[j] of the ray from Po towards aim u[j] of the box of `bounds` -- Po, bounds
+        and u as splat_point takes them.  In (0, 1] where that splat record has flags bit 0 set, +0.0 elsewhere, _capi.SPLAT_NO_BOX
+        records included (csrc/traceback_throughput.hpp).  Works on a tables-only camera (device=-1).
+        wavelength (nm): the trace and the films at that wavelength (zoic_splat_point_transmittance_spectral)."""
+        return self._splat_item(self._lib.zoic_splat_point_transmittance, self._lib.zoic_splat_point_transmittance_spectral, Po, bounds, u,
+                                wavelength, np.float32)
+
+    def splat_transmittance(self, points, bounds, u, wavelengths=None, out=None, stream=None):
+        """The Fresnel transmittance of the rays splat_points traces (zoic_splat_transmittance_device): (n,m) float32, entry (p, j) for
+        the ray of splat record (p, j) of splat_points(points, bounds, u, wavelengths): in (0, 1] where that record has flags bit 0
+        set, +0.0 elsewhere (csrc/traceback_throughput.hpp).  A splatter multiplies each splat's weight by it.
+
+        points, bounds, u, wavelengths, stream: as splat_points takes them -- torch device tensors ((n,3), the (n,12) tensor
+                     pupil_bounds returned, read in place, (n,m,2), (n,)), asynchronous on `stream` (default: torch's current stream);
+                     or numpy (bounds: the structured records or (n,12) float32): copied to the camera's device through torch, the
+                     call waits and returns a numpy array.
+        out: an optional (n,m) float32 tensor on the points' device to write into (torch points only; None with numpy points)."""
+        lib = self._lib
+        if not _is_torch(points):
+            res = self._through_device(
+                "points", 3, points, [("bounds", bounds, _bounds_floats), ("u", u, _f32), ("wavelengths", wavelengths, _f32_flat)], dict(out=out),
+                lambda a, b, uu, lam: lib.zoic_splat_transmittance_device(self._h, len(a), None, None, 1, None, None, None),
+                lambda t, b, uu, lam: self.splat_transmittance(t, b, uu, lam))
+            return res.cpu().numpy()
+        n = self._device_tensor("points", points, (None, 3)).shape[0]
+        self._device_tensor("bounds", bounds, (n, 12))
+        m = self._device_tensor("u", u, (n, None, 2)).shape[1]
+        if m < 1:
+            raise ValueError("u must hold at least one aim per point: (n,m,2), m >= 1")
+        out = self._result("out", out, (n, m), points)
+        lam = self._wavelength_pointer(wavelengths, n)
+        self._spectral_or(lib.zoic_splat_transmittance_device, lib.zoic_splat_transmittance_spectral_device, lam,
                           (n, points.data_ptr(), bounds.data_ptr()), (m, u.data_ptr(), out.data_ptr(), self._stream(stream)))
         return out
 

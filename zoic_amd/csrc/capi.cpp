@@ -45,6 +45,7 @@
 #include "pupil_bounds.hpp"
 #include "splat.hpp"
 #include "ghost.hpp"
+#include "traceback_throughput.hpp"
 #include "transmittance.hpp"
 #include "lens_system.hpp"
 #include "host_util.hpp"
@@ -2333,6 +2334,105 @@ zoic_status zoic_splat_points_spectral_device(zoic_camera *cam, uint64_t n, cons
             return launch_splat_points_spectral(cam->traceBack, backward_dispersion(cam), d_points, d_bounds, d_wavelengths, n, m, d_u, d_splats,
                                                 stream);
         });
+}
+
+// ---- trace-back transmittance (traceback_throughput.hpp): the d-line forms are the spectral ones at kLambdaD32 (d_wavelengths NULL) ----
+static zoic_status trace_back_transmittance_batch(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths, bool spectral,
+                                                  float *d_transmittance, float *d_screen, uint32_t *d_flags, void *stream)
+{
+    return backward_batch(cam, n, {{"d_rays", d_rays, 16}, {"d_wavelengths", d_wavelengths, 4, !spectral}, {"d_transmittance", d_transmittance, 4},
+                                   {"d_screen", d_screen, 8, true}, {"d_flags", d_flags, 4, true}},
+                          [&] {
+                              FilmTable F;
+                              fill_film(cam, F);
+                              return launch_trace_back_throughput(cam->traceBack, backward_dispersion(cam), F, d_rays, d_wavelengths, n,
+                                                                  d_transmittance, d_screen, d_flags, stream);
+                          });
+}
+
+zoic_status zoic_trace_back_transmittance_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, float *d_transmittance, float *d_screen,
+                                                 uint32_t *d_flags, void *stream)
+{
+    return trace_back_transmittance_batch(cam, n, d_rays, nullptr, false, d_transmittance, d_screen, d_flags, stream);
+}
+
+zoic_status zoic_trace_back_transmittance_spectral_device(zoic_camera *cam, uint64_t n, const zoic_ray *d_rays, const float *d_wavelengths,
+                                                          float *d_transmittance, float *d_screen, uint32_t *d_flags, void *stream)
+{
+    return trace_back_transmittance_batch(cam, n, d_rays, d_wavelengths, true, d_transmittance, d_screen, d_flags, stream);
+}
+
+zoic_status zoic_trace_back_ray_transmittance_spectral(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float wavelength_nm,
+                                                       float *Ps, uint32_t *flags, float *T)
+{
+    return backward_item(cam, origin && dir && T, "origin, dir and T", flags, [&] {
+        FilmTable F;
+        fill_film(cam, F);
+        float sx, sy, t;
+        const uint32_t f = trace_back_ray_throughput(cam->traceBack, backward_dispersion(cam), static_cast<const FilmTable *>(&F), wavelength_nm,
+                                                     origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, sx, sy, t);
+        if (Ps) { Ps[0] = sx; Ps[1] = sy; }
+        *T = t;
+        return f;
+    });
+}
+
+zoic_status zoic_trace_back_ray_transmittance(const zoic_camera *cam, const zoic_vec3 *origin, const zoic_vec3 *dir, float *Ps, uint32_t *flags,
+                                              float *T)
+{
+    return zoic_trace_back_ray_transmittance_spectral(cam, origin, dir, kLambdaD32, Ps, flags, T);
+}
+
+static zoic_status splat_transmittance_batch(zoic_camera *cam, uint64_t n, const float *d_points, const zoic_pupil_bounds *d_bounds,
+                                             const float *d_wavelengths, bool spectral, uint32_t m, const float *d_u, float *d_transmittance,
+                                             void *stream)
+{
+    if (zoic_status s = splat_arguments(n, m)) return s;
+    return backward_batch(cam, n, {{"d_points", d_points, 4}, {"d_bounds", d_bounds, 16}, {"d_wavelengths", d_wavelengths, 4, !spectral},
+                                   {"d_u", d_u, 8}, {"d_transmittance", d_transmittance, 4}},
+                          [&] {
+                              FilmTable F;
+                              fill_film(cam, F);
+                              return launch_splat_throughput(cam->traceBack, backward_dispersion(cam), F, d_points, d_bounds, d_wavelengths, n, m, d_u,
+                                                             d_transmittance, stream);
+                          });
+}
+
+zoic_status zoic_splat_transmittance_device(zoic_camera *cam, uint64_t n, const float *d_points, const zoic_pupil_bounds *d_bounds, uint32_t m,
+                                            const float *d_u, float *d_transmittance, void *stream)
+{
+    return splat_transmittance_batch(cam, n, d_points, d_bounds, nullptr, false, m, d_u, d_transmittance, stream);
+}
+
+zoic_status zoic_splat_transmittance_spectral_device(zoic_camera *cam, uint64_t n, const float *d_points, const zoic_pupil_bounds *d_bounds,
+                                                     const float *d_wavelengths, uint32_t m, const float *d_u, float *d_transmittance, void *stream)
+{
+    return splat_transmittance_batch(cam, n, d_points, d_bounds, d_wavelengths, true, m, d_u, d_transmittance, stream);
+}
+
+zoic_status zoic_splat_point_transmittance_spectral(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds,
+                                                    float wavelength_nm, uint32_t m, const float *u, float *T)
+{
+    if (zoic_status s = splat_arguments(1, m)) return s;
+    if (zoic_status s = check_pointer("u", u, 4)) return s;
+    if (zoic_status s = check_pointer("T", T, 4)) return s;
+    return backward_item(cam, Po && bounds, "Po and bounds", nullptr, [&] {
+        const PupilBounds B = get_pupil_bounds(bounds);
+        const BackwardDispersion D = backward_dispersion(cam);
+        FilmTable F;
+        fill_film(cam, F);
+        const float z = splat_plane(cam->traceBack);
+        for (uint32_t j = 0; j < m; ++j)
+            T[j] = splat_throughput(cam->traceBack, D, static_cast<const FilmTable *>(&F), wavelength_nm, z, Po->x, Po->y, Po->z, B.aim[0], B.aim[1],
+                                    B.aim[2], B.aim[3], B.count, B.flags, u[2u * j], u[2u * j + 1u]);
+        return 0u;
+    });
+}
+
+zoic_status zoic_splat_point_transmittance(const zoic_camera *cam, const zoic_vec3 *Po, const zoic_pupil_bounds *bounds, uint32_t m, const float *u,
+                                           float *T)
+{
+    return zoic_splat_point_transmittance_spectral(cam, Po, bounds, kLambdaD32, m, u, T);
 }
 
 zoic_status zoic_host_alloc(size_t bytes, void **out)
