@@ -64,6 +64,8 @@ extern "C" {
  *      _spectral forms (the trace-back with its Jacobian dPs / d(origin, dir)).
  *      Added later without a new number (additive): zoic_ray_transmittance_device, zoic_camera_set_coatings and
  *      zoic_camera_get_coatings (the Fresnel transmittance of traced rays, with single-layer coatings).
+ *      Added later without a new number (additive): zoic_camera_set_coating_stacks, zoic_camera_get_coating_stacks and
+ *      ZOIC_COATING_MAX_LAYERS (multilayer coatings: thin-film stacks for the transmittance calls and the ghosts' weights).
  *      Added later without a new number (additive): zoic_create_ghost_rays_device and zoic_camera_get_ghost_pairs (ghost rays: the
  *      two-reflection paths through the lens with their Fresnel weights), ZOIC_GHOST_MAX_PAIRS and the ZOIC_GHOST_* flag macros.
  *      Added later without a new number (additive): zoic_pupil_bounds_device, zoic_pupil_bounds_point and their _spectral forms
@@ -410,6 +412,31 @@ zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *f
 /* The film table of the camera's lens (works on a ZOIC_DEVICE_NONE camera): returns the surface count and writes up to `capacity`
  * entries, trace order (rear first), into the arrays that are not NULL; -1 for a NULL camera or a negative capacity. */
 int zoic_camera_get_coatings(const zoic_camera *cam, int capacity, float *film_index, float *film_lambda0_nm);
+/* Multilayer coatings (csrc/coating_stack.hpp has the full definition): per interface an optional stack of 1 to ZOIC_COATING_MAX_LAYERS
+ * homogeneous, loss-free layers that do not disperse, each with an index and a physical thickness (nm).  The stack is evaluated by the
+ * characteristic-matrix method at the ray's own angle and wavelength for both polarisations, and is honoured wherever the single film
+ * is: zoic_ray_transmittance_device, the weights of zoic_create_ghost_rays_device, and the trace-back and splat transmittance calls,
+ * host and device with the same bits.
+ *   Order      interfaces in FILE order (front to rear) like zoic_camera_set_coatings; the arrays are count x ZOIC_COATING_MAX_LAYERS,
+ *              row-major, and within an interface layer 0 adjoins the front-side medium.
+ *   layers[i]  0 ... ZOIC_COATING_MAX_LAYERS.  0: no stack there, the interface's zoic_camera_set_coatings entry stays in force (or it
+ *              is bare); otherwise the stack overrides that entry.  Every used index must be finite and in [1, 4], every used thickness
+ *              finite and in (0, 1000] nm, else ZOIC_ERR_INVALID_ARGUMENT; entries past layers[i] are not looked at.
+ *   count      the surface count; 0 clears (the arrays may be NULL).  A count that differs from the loaded lens's surface count returns
+ *              ZOIC_ERR_INVALID_ARGUMENT, here and at every zoic_camera_update while the override is set.  A refused call changes nothing.
+ *   Special    an interface between equal media (the stop) ignores its stack; where a layer carries no wave at the ray's angle
+ *              ((n1 / n_layer)^2 sin^2 i >= 1) the interface is priced bare.
+ * Read at the call: no update is needed.  Like zoic_camera_update it is a setter of the camera -- call it while no call on the camera
+ * is in flight; on a device camera it uploads the table with a blocking copy that has landed when it returns.  Cameras without a
+ * stack run the kernels they ran before and return the same bits. */
+#define ZOIC_COATING_MAX_LAYERS 8
+zoic_status zoic_camera_set_coating_stacks(zoic_camera *cam, int count, const int32_t *layers, const float *layer_index,
+        const float *layer_thickness_nm);
+/* The stack table of the camera's lens (works on a ZOIC_DEVICE_NONE camera): returns the surface count and writes up to `capacity`
+ * interfaces, trace order (rear first), each interface's layers in the order a forward ray (rear to front) meets them, into the arrays
+ * that are not NULL (layer_index and layer_thickness_nm: ZOIC_COATING_MAX_LAYERS per interface); -1 for a NULL camera or a negative
+ * capacity. */
+int zoic_camera_get_coating_stacks(const zoic_camera *cam, int capacity, int32_t *layers, float *layer_index, float *layer_thickness_nm);
 /* ---- ghost rays (opt-in; csrc/ghost.hpp has the full definition) -------------------------------------------------------------------
  * The light the transmittance above subtracts, followed: reflected at one interface and again at another it reaches the sensor as a
  * ghost (flare discs, veiling glare).  One ghost belongs to one main record, one wavelength and one ordered pair of interfaces (a, b),

@@ -22,6 +22,7 @@ TRACE_BACK_WAVELENGTH = 8
 PROJECT_WAVELENGTH = 6
 # zoic_create_rays_hero_device: the most wavelengths per sample, and the flag bit (8) of a companion that did not come through
 HERO_MAX_WAVELENGTHS = 8
+COATING_MAX_LAYERS = 8   # ZOIC_COATING_MAX_LAYERS
 RAY_COMPANION_LOST = 0x100
 
 STATUS_NAMES = ["ZOIC_OK", "ZOIC_ERR_INVALID_ARGUMENT", "ZOIC_ERR_LENS_PATH", "ZOIC_ERR_LENS_COLUMNS",
@@ -134,6 +135,8 @@ SYMBOLS = {
     "zoic_ray_transmittance_device": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "zoic_camera_set_coatings": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "zoic_camera_get_coatings": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "zoic_camera_set_coating_stacks": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "zoic_camera_get_coating_stacks": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "zoic_create_ghost_rays_device": (C.c_int, [_vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "zoic_camera_get_ghost_pairs": (C.c_int, [_vp, C.c_int, _vp]),
     "zoic_camera_create_ray": (C.c_int, [_vp, C.POINTER(CameraInput), C.POINTER(CameraOutput), C.c_uint16]),

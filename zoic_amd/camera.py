@@ -827,7 +827,7 @@ class ZoicCamera:
         returns (T (n,) float32, screen (n,2) float32, flags (n,) int32).  screen and flags are trace_back's bit for bit; T[i] is in
         (0, 1] where bit 0 of flags[i] is set and +0.0 elsewhere (csrc/traceback_throughput.hpp).  For the records of a forward call
         T equals what transmittance() gives for them, to rounding.  The films (set_coatings) and the dispersion (set_abbe_numbers)
-        are read at the call.
+        are read at the call.  Multilayer stacks (set_coating_stacks) are honoured where an interface has one.
 
         rays, wavelengths, stream: as trace_back takes them -- an (n,8) float32 device tensor of zoic_ray records or the dict a
                      create_rays call on device tensors returned (its "rays" buffer is read in place), asynchronous on `stream`
@@ -866,6 +866,7 @@ class ZoicCamera:
         """The Fresnel transmittance of the rays splat_points traces (zoic_splat_transmittance_device): (n,m) float32, entry (p, j) for
         the ray of splat record (p, j) of splat_points(points, bounds, u, wavelengths): in (0, 1] where that record has flags bit 0
         set, +0.0 elsewhere (csrc/traceback_throughput.hpp).  A splatter multiplies each splat's weight by it.
+        Multilayer stacks (set_coating_stacks) are honoured where an interface has one.
 
         points, bounds, u, wavelengths, stream: as splat_points takes them -- torch device tensors ((n,3), the (n,12) tensor
                      pupil_bounds returned, read in place, (n,m,2), (n,)), asynchronous on `stream` (default: torch's current stream);
@@ -936,6 +937,7 @@ class ZoicCamera:
     def transmittance(self, samples, rays, wavelengths=None, rng_states=None, ray_index_base=0, out=None, stream=None):
         """Fresnel transmittance (zoic_ray_transmittance_device) of rays create_rays / create_rays_hero made from device tensors: the
         share of unpolarised light the lens's interfaces let through along each record's path, with the coatings of set_coatings.
+        Multilayer stacks (set_coating_stacks) are honoured where an interface has one.
 
         samples, wavelengths, rng_states, ray_index_base: what the forward call was given; rays: the record tensor it returned (or its
         result dict).  wavelengths None: (n,8) records of create_rays(samples), at the d-line; (n,): the spectral records of
@@ -957,7 +959,7 @@ class ZoicCamera:
     def set_coatings(self, index, lambda0_nm):
         """Single-layer coatings in FILE order (front to rear, as the prescription lists the interfaces): the film's index and the
         wavelength (nm) at which it is a quarter wave thick, one per interface (a scalar lambda0_nm serves all); index 0: uncoated.
-        set_coatings(None, None) clears them."""
+        set_coatings(None, None) clears them.  An interface with a multilayer stack (set_coating_stacks) is priced by the stack."""
         if index is None:
             self._check(self._lib.zoic_camera_set_coatings(self._h, 0, None, None))
             return
@@ -970,6 +972,39 @@ class ZoicCamera:
         lambda0_nm.  Works on a tables-only camera (device=-1)."""
         return self._table(self._lib.zoic_camera_get_coatings, np.float32, ("index", "lambda0_nm"))
 
+    def set_coating_stacks(self, stacks):
+        """Multilayer coatings (zoic_camera_set_coating_stacks, csrc/coating_stack.hpp): one entry per interface in FILE order (front
+        to rear), each a sequence of up to 8 (index, thickness_nm) pairs, layer 0 adjoining the front-side medium; an empty entry or
+        None: no stack there, the interface's set_coatings film (or the bare interface) holds.  set_coating_stacks(None) clears.
+        Read at the call: no update is needed."""
+        if stacks is None:
+            self._check(self._lib.zoic_camera_set_coating_stacks(self._h, 0, None, None, None))
+            return
+        stacks = list(stacks)
+        count, width = len(stacks), _capi.COATING_MAX_LAYERS
+        layers = np.zeros(count, np.int32)
+        index, thick = np.zeros((count, width), np.float32), np.zeros((count, width), np.float32)
+        for i, entry in enumerate(stacks):
+            pairs = np.zeros((0, 2), np.float32) if entry is None or len(entry) == 0 else np.asarray(entry, dtype=np.float32)
+            if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] > width:
+                raise ValueError("stack %d must be a sequence of at most %d (index, thickness_nm) pairs" % (i, width))
+            layers[i] = pairs.shape[0]
+            index[i, :layers[i]], thick[i, :layers[i]] = pairs[:, 0], pairs[:, 1]
+        self._check(self._lib.zoic_camera_set_coating_stacks(self._h, count, layers.ctypes.data, index.ctypes.data, thick.ctypes.data))
+
+    def coating_stacks(self):
+        """The lens's stack table (zoic_camera_get_coating_stacks), trace order (rear first), each interface's layers in the order a
+        forward ray (rear to front) meets them: dict of layers (count,) int32, index (count,8) and thickness_nm (count,8) float32.
+        Works on a tables-only camera (device=-1)."""
+        get = self._lib.zoic_camera_get_coating_stacks
+        n = get(self._h, 0, None, None, None)
+        if n < 0:
+            self._check(1)
+        width = _capi.COATING_MAX_LAYERS
+        a = dict(layers=np.zeros(n, np.int32), index=np.zeros((n, width), np.float32), thickness_nm=np.zeros((n, width), np.float32))
+        get(self._h, n, *[v.ctypes.data for v in a.values()])
+        return a
+
     def ghost_pairs(self):
         """The interface pairs that can make a ghost (zoic_camera_get_ghost_pairs): an (m,2) int32 array of rows (a, b), trace-order
         indices (rear first), a > b, both interfaces between unequal media at the d-line; ordered by a, then b.  Works on a
@@ -980,7 +1015,8 @@ class ZoicCamera:
     def create_ghost_rays(self, samples, rays, pairs, wavelengths=None, rng_states=None, ray_index_base=0, out=None, stream=None):
         """Ghost rays (zoic_create_ghost_rays_device) of rays create_rays made from device tensors: for every sample and every pair
         (a, b) of `pairs` -- (p,2) integers, trace-order interface indices, a > b: ghost_pairs() lists the ones that reflect -- the
-        path that is reflected at a and again at b, with its Fresnel weight (csrc/ghost.hpp).
+        path that is reflected at a and again at b, with its Fresnel weight (csrc/ghost.hpp).  Multilayer stacks
+        (set_coating_stacks) are honoured where an interface has one.
 
         samples, wavelengths, rng_states, ray_index_base: what the forward call was given; rays: the (n,8) record tensor it returned
         (or its result dict); wavelengths None: the records of create_rays(samples), at the d-line, else the (n,) tensor of

@@ -318,6 +318,12 @@ struct zoic_camera {  // struct cameraData, zoic.cpp:627-643
     TraceBackTable traceBack{};                  // traceback.hpp: the trace-back table of the tables above (filled by every successful update)
     GhostTable ghost{};                          // ghost.hpp: the ghost tracer's geometry of the tables above (filled by every successful update) ...
     GhostTable *dGhost = nullptr;                // ... and its copy on the device, which the ghost kernel reads (its arguments have no room for it)
+    // zoic_camera_set_coating_stacks: layer counts, indices and thicknesses (nm) in file order, count x ZOIC_COATING_MAX_LAYERS (empty: none)
+    std::vector<int32_t> stackLayers;
+    std::vector<float> stackIndex, stackThickness;
+    StackTable stacks{};                         // coating_stack.hpp: the override on the current lens, trace order (fill_stacks) ...
+    StackTable *dStacks = nullptr;               // ... and its copy on the device, which the stack-aware kernels read
+    bool stacksOn = false;                       // an interface of the current lens has a stack: the stack-aware kernels run
 
     TidState *tid_state(uint16_t tid);
     CallContext *lease_context(hipError_t &err);
@@ -894,6 +900,37 @@ void fill_film(const zoic_camera *cam, FilmTable &F)
     }
 }
 
+// the stack table of the camera's lens (coating_stack.hpp): the override (file order, front first, layer 0 at the front-side medium:
+// both reversed here) or no stack anywhere; and its copy on the device.  Called by the setter and by every update, so the kernels
+// read the table in force without either waiting for the other.
+zoic_status fill_stacks(zoic_camera *cam)
+{
+    StackTable &K = cam->stacks;
+    K = StackTable{};
+    cam->stacksOn = false;
+    const size_t rows = cam->lens.rows.size();
+    if (rows != 0 && rows <= static_cast<size_t>(kMaxSurfaces) && cam->stackLayers.size() == rows) {
+        for (size_t i = 0; i < rows; ++i) {
+            const size_t f = rows - 1 - i;
+            const int L = cam->stackLayers[f];
+            K.layers[i] = L;
+            for (int l = 0; l < L; ++l) {
+                K.layer[i][l] = StackLayer{cam->stackIndex[f * kCoatingMaxLayers + (L - 1 - l)], cam->stackThickness[f * kCoatingMaxLayers + (L - 1 - l)]};
+            }
+        }
+        cam->stacksOn = stacks_in_use(K, static_cast<int>(rows));
+    }
+    if (cam->device != ZOIC_DEVICE_NONE) {
+        DeviceGuard guard(cam->device);
+        ZOIC_HIP(guard.error());
+        ZOIC_HIP(hipMemcpy(cam->dStacks, &K, sizeof(StackTable), hipMemcpyHostToDevice));
+    }
+    return ZOIC_OK;
+}
+
+// the table the stack-aware kernels read, or nullptr: the plain kernels run
+const StackTable *device_stacks(const zoic_camera *cam) { return cam->stacksOn ? cam->dStacks : nullptr; }
+
 // what the backward tables' fillers read of the camera's current tables (backward_tables.hpp)
 LensView lens_view(const zoic_camera *cam)
 {
@@ -928,7 +965,7 @@ zoic_status fill_backward_tables(zoic_camera *cam)
     fill_traceback_table(cam->traceBack, V);
     fill_ghost_table(cam->ghost, V);
     if (cam->device != ZOIC_DEVICE_NONE) ZOIC_HIP(hipMemcpy(cam->dGhost, &cam->ghost, sizeof(GhostTable), hipMemcpyHostToDevice));
-    return ZOIC_OK;
+    return fill_stacks(cam);
 }
 
 // what the ghost tracer reads at the call (ghost.hpp): the dispersion and the films, trace order
@@ -1114,6 +1151,8 @@ zoic_status zoic_camera_create(int device, zoic_camera **out)
     if (e == hipSuccess) e = hipMemset(cam->dWorkCursor, 0, kLaunchSlots * 2 * kCursorStride * sizeof(unsigned int));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&cam->dGhost), sizeof(GhostTable));
     if (e == hipSuccess) e = hipMemset(cam->dGhost, 0, sizeof(GhostTable));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&cam->dStacks), sizeof(StackTable));
+    if (e == hipSuccess) e = hipMemset(cam->dStacks, 0, sizeof(StackTable));
     for (unsigned i = 0; e == hipSuccess && i < kLaunchSlots; ++i) {
         cam->slots[i].cursor = cam->dWorkCursor + i * 2 * kCursorStride;
         e = hipEventCreateWithFlags(&cam->slots[i].done, hipEventDisableTiming);
@@ -1150,6 +1189,7 @@ void zoic_camera_destroy(zoic_camera *cam)
         if (cam->dCounters) (void)hipFree(cam->dCounters);
         if (cam->dWorkCursor) (void)hipFree(cam->dWorkCursor);
         if (cam->dGhost) (void)hipFree(cam->dGhost);
+        if (cam->dStacks) (void)hipFree(cam->dStacks);
     }
     if (cam->tidStates) for (unsigned i = 0; i < kTidStates; ++i) delete cam->tidStates[i].load(std::memory_order_relaxed);
     delete cam;
@@ -1324,6 +1364,8 @@ zoic_status zoic_camera_update(zoic_camera *cam, const zoic_params *p)
         return surface_count_mismatch("zoic_camera_set_abbe_numbers", cam->abbeOverride.size(), "V-numbers", cam->lens.rows.size());
     if (p->lensModel == ZOIC_RAYTRACED && !cam->coatingIndex.empty() && cam->coatingIndex.size() != cam->lens.rows.size())
         return surface_count_mismatch("zoic_camera_set_coatings", cam->coatingIndex.size(), "coatings", cam->lens.rows.size());
+    if (p->lensModel == ZOIC_RAYTRACED && !cam->stackLayers.empty() && cam->stackLayers.size() != cam->lens.rows.size())
+        return surface_count_mismatch("zoic_camera_set_coating_stacks", cam->stackLayers.size(), "coating stacks", cam->lens.rows.size());
 
     // camera->params = parms, zoic.cpp:1719
     cam->params.p = *p;
@@ -1612,7 +1654,8 @@ zoic_status zoic_ray_transmittance_device(zoic_camera *cam, uint64_t n, uint32_t
             FilmTable F;
             fill_film(cam, F);
             return launch_status(launch_ray_transmittance(model, cam->kolb, W, F, cam->bokehDev, d_samples, d_wavelengths, d_rng_states,
-                                                          ray_index_base, n, k, reinterpret_cast<const RayRecord *>(d_rays), d_transmittance, st));
+                                                          ray_index_base, n, k, reinterpret_cast<const RayRecord *>(d_rays), d_transmittance, st,
+                                                          device_stacks(cam)));
         });
 }
 
@@ -1651,6 +1694,59 @@ zoic_status zoic_camera_set_coatings(zoic_camera *cam, int count, const float *f
     return ZOIC_OK;
 }
 
+int zoic_camera_get_coating_stacks(const zoic_camera *cam, int capacity, int32_t *layers, float *layer_index, float *layer_thickness_nm)
+{
+    if (!cam) { fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL"); return -1; }
+    if (capacity < 0) { fail(ZOIC_ERR_INVALID_ARGUMENT, "capacity is negative"); return -1; }
+    const int count = static_cast<int>(std::min<size_t>(cam->lens.rows.size(), kMaxSurfaces));
+    const StackTable &K = cam->stacks;
+    for (int i = 0; i < count && i < capacity; ++i) {
+        if (layers) layers[i] = K.layers[i];
+        for (int l = 0; l < kCoatingMaxLayers; ++l) {
+            if (layer_index) layer_index[i * kCoatingMaxLayers + l] = K.layer[i][l].index;
+            if (layer_thickness_nm) layer_thickness_nm[i * kCoatingMaxLayers + l] = K.layer[i][l].thickness;
+        }
+    }
+    return count;
+}
+
+zoic_status zoic_camera_set_coating_stacks(zoic_camera *cam, int count, const int32_t *layers, const float *layer_index,
+                                           const float *layer_thickness_nm)
+{
+    static_assert(ZOIC_COATING_MAX_LAYERS == kCoatingMaxLayers, "ZOIC_COATING_MAX_LAYERS");
+    if (!cam) return fail(ZOIC_ERR_INVALID_ARGUMENT, "cam is NULL");
+    if (count < 0 || count > ZOIC_MAX_LENS_SURFACES) return fail(ZOIC_ERR_INVALID_ARGUMENT, "count out of range");
+    if (count == 0) {
+        cam->stackLayers.clear(); cam->stackIndex.clear(); cam->stackThickness.clear();
+        return fill_stacks(cam);
+    }
+    if (!layers || !layer_index || !layer_thickness_nm)
+        return fail(ZOIC_ERR_INVALID_ARGUMENT, "layers, layer_index and layer_thickness_nm must be non-NULL");
+    const bool loaded = cam->updated && cam->params.p.lensModel == ZOIC_RAYTRACED && !cam->lens.rows.empty();
+    if (loaded && static_cast<size_t>(count) != cam->lens.rows.size())
+        return surface_count_mismatch("zoic_camera_set_coating_stacks", static_cast<size_t>(count), "coating stacks", cam->lens.rows.size());
+    for (int i = 0; i < count; ++i) {
+        if (layers[i] < 0 || layers[i] > kCoatingMaxLayers)
+            return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coating_stacks: entry " + std::to_string(i) + " needs 0 ... 8 layers");
+        for (int l = 0; l < layers[i]; ++l) {   // entries past layers[i] are not looked at
+            const float nj = layer_index[i * kCoatingMaxLayers + l], dj = layer_thickness_nm[i * kCoatingMaxLayers + l];
+            if (!std::isfinite(nj) || !(nj >= 1.0f && nj <= 4.0f) || !std::isfinite(dj) || !(dj > 0.0f && dj <= 1000.0f))
+                return fail(ZOIC_ERR_INVALID_ARGUMENT, "zoic_camera_set_coating_stacks: entry " + std::to_string(i) + ", layer " + std::to_string(l) +
+                                                           " needs a finite index in [1, 4] and a finite thickness in (0, 1000] nm");
+        }
+    }
+    const size_t cells = static_cast<size_t>(count) * kCoatingMaxLayers;
+    cam->stackLayers.assign(layers, layers + count);
+    cam->stackIndex.assign(cells, 0.0f);
+    cam->stackThickness.assign(cells, 0.0f);
+    for (int i = 0; i < count; ++i)
+        for (int l = 0; l < layers[i]; ++l) {
+            cam->stackIndex[i * kCoatingMaxLayers + l] = layer_index[i * kCoatingMaxLayers + l];
+            cam->stackThickness[i * kCoatingMaxLayers + l] = layer_thickness_nm[i * kCoatingMaxLayers + l];
+        }
+    return fill_stacks(cam);
+}
+
 zoic_status zoic_create_ghost_rays_device(zoic_camera *cam, uint64_t n, uint32_t p, const uint32_t *pairs, const float *d_samples,
                                           const float *d_wavelengths, const uint32_t *d_rng_states, uint64_t ray_index_base,
                                           const zoic_ray *d_rays, zoic_ray *d_ghosts, void *stream)
@@ -1671,7 +1767,7 @@ zoic_status zoic_create_ghost_rays_device(zoic_camera *cam, uint64_t n, uint32_t
             fill_ghost_media(cam, M);
             return launch_status(launch_ghost_rays(cam->ghost.model, cam->kolb, M, cam->bokehDev, cam->dGhost, p, pairs, d_samples, d_wavelengths,
                                                    d_rng_states, ray_index_base, n, reinterpret_cast<const RayRecord *>(d_rays),
-                                                   reinterpret_cast<RayRecord *>(d_ghosts), static_cast<hipStream_t>(stream)));
+                                                   reinterpret_cast<RayRecord *>(d_ghosts), static_cast<hipStream_t>(stream), device_stacks(cam)));
         });
 }
 
@@ -2346,7 +2442,7 @@ static zoic_status trace_back_transmittance_batch(zoic_camera *cam, uint64_t n, 
                               FilmTable F;
                               fill_film(cam, F);
                               return launch_trace_back_throughput(cam->traceBack, backward_dispersion(cam), F, d_rays, d_wavelengths, n,
-                                                                  d_transmittance, d_screen, d_flags, stream);
+                                                                  d_transmittance, d_screen, d_flags, stream, device_stacks(cam));
                           });
 }
 
@@ -2370,7 +2466,8 @@ zoic_status zoic_trace_back_ray_transmittance_spectral(const zoic_camera *cam, c
         fill_film(cam, F);
         float sx, sy, t;
         const uint32_t f = trace_back_ray_throughput(cam->traceBack, backward_dispersion(cam), static_cast<const FilmTable *>(&F), wavelength_nm,
-                                                     origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, sx, sy, t);
+                                                     origin->x, origin->y, origin->z, dir->x, dir->y, dir->z, sx, sy, t,
+                                                     static_cast<const StackTable *>(&cam->stacks));
         if (Ps) { Ps[0] = sx; Ps[1] = sy; }
         *T = t;
         return f;
@@ -2394,7 +2491,7 @@ static zoic_status splat_transmittance_batch(zoic_camera *cam, uint64_t n, const
                               FilmTable F;
                               fill_film(cam, F);
                               return launch_splat_throughput(cam->traceBack, backward_dispersion(cam), F, d_points, d_bounds, d_wavelengths, n, m, d_u,
-                                                             d_transmittance, stream);
+                                                             d_transmittance, stream, device_stacks(cam));
                           });
 }
 
@@ -2424,7 +2521,7 @@ zoic_status zoic_splat_point_transmittance_spectral(const zoic_camera *cam, cons
         const float z = splat_plane(cam->traceBack);
         for (uint32_t j = 0; j < m; ++j)
             T[j] = splat_throughput(cam->traceBack, D, static_cast<const FilmTable *>(&F), wavelength_nm, z, Po->x, Po->y, Po->z, B.aim[0], B.aim[1],
-                                    B.aim[2], B.aim[3], B.count, B.flags, u[2u * j], u[2u * j + 1u]);
+                                    B.aim[2], B.aim[3], B.count, B.flags, u[2u * j], u[2u * j + 1u], static_cast<const StackTable *>(&cam->stacks));
         return 0u;
     });
 }

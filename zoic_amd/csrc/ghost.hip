@@ -9,6 +9,8 @@
 // kernarg_view, spectral.hpp ZOIC_SPEC_PIN), the geometry from the camera's GhostTable in device memory -- the kernel arguments have no
 // room for it beside the KolbTable that the replay takes.  Records leave as whole 32-byte stores, sample-major, n x p: no stage.  Nothing
 // goes to scratch.
+// Multilayer coatings (coating_stack.hpp): a camera with a stack on any interface runs kolb_stack_flare_kernel, the same body under the
+// coating policy `const StackTable *` -- the camera's table in device memory beside its GhostTable, scalar loads at the same index.
 #include <hip/hip_runtime.h>
 
 #include "ghost.hpp"
@@ -30,13 +32,13 @@ struct GhostKernelArgs {
 __device__ __forceinline__ auto kernarg_media() { return kernarg_view<GhostKernelArgs, GhostMedia>(offsetof(GhostKernelArgs, M)); }
 __device__ __forceinline__ auto kernarg_pairs() { return kernarg_view<GhostKernelArgs, uint32_t>(offsetof(GhostKernelArgs, P)); }
 
-}  // namespace
-
-// budget: 0 scratch, 0 spills, <= 128 VGPRs (4 waves per SIMD)
-__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_ghost_kernel(
-    const KolbTable T, const GhostMedia M, const BokehTables B, const GhostPairs P, const GhostTable *__restrict__ G,
-    const float4 *__restrict__ samples, const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
-    const RayRecord *__restrict__ rays, RayRecord *__restrict__ out, uint32_t p)
+// the one body of both Kolb kernels; KP: the coating policy.  (The stack-aware kernel's extra argument comes last: the offsets of
+// GhostKernelArgs hold for both.)
+template <class KP>
+__device__ __forceinline__ void ghost_pass(const KolbTable T, const BokehTables B, const GhostTable *__restrict__ G,
+                                           const float4 *__restrict__ samples, const float *__restrict__ lambdas,
+                                           const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
+                                           const RayRecord *__restrict__ rays, RayRecord *__restrict__ out, uint32_t p, KP K)
 {
     __shared__ __align__(16) float2 lut[kLutEntries];
     stage_lut(T, lut);
@@ -57,10 +59,30 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
             auto pairs = kernarg_pairs();
             ZOIC_SPEC_PIN(pairs);
             const uint32_t pair = pairs[j];
-            const GhostRay g = ghost_record(G, kernarg_media(), pair, start, lambda, o0, d0);
+            const GhostRay g = ghost_record(G, kernarg_media(), pair, start, lambda, o0, d0, K);
             if (have) store_ray_record(out, i * p + j, g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.weight, g.flags);
         }
     }
+}
+
+}  // namespace
+
+// budget: 0 scratch, 0 spills, <= 128 VGPRs (4 waves per SIMD)
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_ghost_kernel(
+    const KolbTable T, const GhostMedia M, const BokehTables B, const GhostPairs P, const GhostTable *__restrict__ G,
+    const float4 *__restrict__ samples, const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
+    const RayRecord *__restrict__ rays, RayRecord *__restrict__ out, uint32_t p)
+{
+    ghost_pass(T, B, G, samples, lambdas, rngStates, rayBase, n, rays, out, p, NoStacks{});
+}
+
+// the same with multilayer coatings; budget: the plain kernel's, and no LDS beyond its
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_stack_flare_kernel(
+    const KolbTable T, const GhostMedia M, const BokehTables B, const GhostPairs P, const GhostTable *__restrict__ G,
+    const float4 *__restrict__ samples, const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n,
+    const RayRecord *__restrict__ rays, RayRecord *__restrict__ out, uint32_t p, const StackTable *__restrict__ stacks)
+{
+    ghost_pass(T, B, G, samples, lambdas, rngStates, rayBase, n, rays, out, p, stacks);
 }
 
 // THINLENS / NONE: a lens without interfaces has no ghosts.  One record per lane.
@@ -71,7 +93,7 @@ __global__ __launch_bounds__(kPassBlock) void ghost_model_kernel(uint64_t total,
 
 int launch_ghost_rays(int model, const KolbTable &kolb, const GhostMedia &media, const BokehTables &bokeh, const GhostTable *d_table,
                       uint32_t p, const uint32_t *pairs, const float *d_samples, const float *d_lambda, const uint32_t *d_rng,
-                      uint64_t rayBase, uint64_t n, const RayRecord *rays, RayRecord *d_out, void *stream)
+                      uint64_t rayBase, uint64_t n, const RayRecord *rays, RayRecord *d_out, void *stream, const StackTable *d_stacks)
 {
     if (n == 0) return 0;
     if (p == 0 || p > static_cast<uint32_t>(kGhostMaxPairs)) return static_cast<int>(hipErrorInvalidValue);
@@ -79,6 +101,9 @@ int launch_ghost_rays(int model, const KolbTable &kolb, const GhostMedia &media,
     if (!d_table) return static_cast<int>(hipErrorInvalidValue);
     GhostPairs P{};
     for (uint32_t j = 0; j < p; ++j) P.packed[j] = pairs[j];
+    if (d_stacks)
+        return launch_pass(kolb_stack_flare_kernel, pass_grid(n), stream, kolb, media, bokeh, P, d_table, reinterpret_cast<const float4 *>(d_samples),
+                           d_lambda, reinterpret_cast<const uint4 *>(d_rng), rayBase, n, rays, d_out, p, d_stacks);
     return launch_pass(kolb_ghost_kernel, pass_grid(n), stream, kolb, media, bokeh, P, d_table, reinterpret_cast<const float4 *>(d_samples), d_lambda,
                        reinterpret_cast<const uint4 *>(d_rng), rayBase, n, rays, d_out, p);
 }

@@ -48,6 +48,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "coating_stack.hpp"
 #include "traceback.hpp"
 #include "transmittance.hpp"
 
@@ -107,9 +108,11 @@ ZOIC_HD void ghost_media(MP M, int count, int i, float dl, float &lo, float &hi)
 
 // The ghost of the pair (a, b), or with a = b = -1 the plain path, from the start (o, d) at lambda.  GP: pointer to the GhostTable; MP:
 // `const GhostMedia *` on the host, a pointer into the kernel-argument segment on the device (ZOIC_SPEC_PIN).  The pair is wave-uniform
-// on the device, so the whole interface sequence is, and every table index goes through tb_uniform.
-template <class GP, class MP>
-ZOIC_HD GhostRay ghost_trace(GP G, MP M, int a, int b, float lambda, V3 o, V3 d)
+// on the device, so the whole interface sequence is, and every table index goes through tb_uniform.  KP: the coating policy
+// (coating_stack.hpp): NoStacks, or a pointer to the camera's StackTable, whose layers a +z leg meets in the table's order and leg 1
+// backwards.
+template <class GP, class MP, class KP = NoStacks>
+ZOIC_HD GhostRay ghost_trace(GP G, MP M, int a, int b, float lambda, V3 o, V3 d, KP K = KP{})
 {
     if (G->model != 1) return ghost_end(kGhostModel, 0, 0);
     const int count = G->count;
@@ -170,7 +173,7 @@ ZOIC_HD GhostRay ghost_trace(GP G, MP M, int a, int b, float lambda, V3 o, V3 d)
         const float k2 = fmaf(eta2, cosi * cosi, 1.0f - eta2);
         if (reflect) {
             float R = 1.0f;   // total reflection
-            if (k2 >= 0.0f) R = 1.0f - interface_transmittance(nFrom, nTo, fabsf(cosi), tb_sqrt(k2), nc, lambda0, lambda);
+            if (k2 >= 0.0f) R = 1.0f - coated_transmittance(K, ii, plus, nFrom, nTo, fabsf(cosi), tb_sqrt(k2), nc, lambda0, lambda);
             w = w * R;
             const float g = cosi + cosi;
             ux = fmaf(g, nx, ux); uy = fmaf(g, ny, uy);
@@ -181,7 +184,7 @@ ZOIC_HD GhostRay ghost_trace(GP G, MP M, int a, int b, float lambda, V3 o, V3 d)
         } else {
             if (!(k2 >= 0.0f)) return ghost_end(kGhostTir, ii, lg);
             const float sk = tb_sqrt(k2);
-            if (nFrom != nTo) w = w * interface_transmittance(nFrom, nTo, fabsf(cosi), sk, nc, lambda0, lambda);
+            if (nFrom != nTo) w = w * coated_transmittance(K, ii, plus, nFrom, nTo, fabsf(cosi), sk, nc, lambda0, lambda);
             const float g = fmaf(eta, cosi, -sk);
             ux = fmaf(eta, ux, g * nx); uy = fmaf(eta, uy, g * ny); um = fmaf(eta, um, g * nz);
             x = hx; y = hy; zm = hz;
@@ -201,14 +204,14 @@ ZOIC_HD GhostRay ghost_trace(GP G, MP M, int a, int b, float lambda, V3 o, V3 d)
 }
 
 // One column of the call: the pair as the C-ABI packs it (a | b << 8), and whether the sample has a start at all
-template <class GP, class MP>
-ZOIC_HD GhostRay ghost_record(GP G, MP M, uint32_t pair, bool haveStart, float lambda, V3 o, V3 d)
+template <class GP, class MP, class KP = NoStacks>
+ZOIC_HD GhostRay ghost_record(GP G, MP M, uint32_t pair, bool haveStart, float lambda, V3 o, V3 d, KP K = KP{})
 {
     if (G->model != 1) return ghost_end(kGhostModel, 0, 0);
     const int a = static_cast<int>(pair & 0xFFu), b = static_cast<int>((pair >> 8) & 0xFFu);
     if ((pair >> 16) != 0u || !(a > b && a < G->count)) return ghost_end(kGhostInvalidPair, 0, 0);
     if (!haveStart) return ghost_end(kGhostNoStart, 0, 0);
-    return ghost_trace(G, M, a, b, lambda, o, d);
+    return ghost_trace(G, M, a, b, lambda, o, d, K);
 }
 
 // Host: the table of a camera from its LensView (backward_tables.hpp), the rows and the validity conditions of
@@ -244,8 +247,10 @@ inline void fill_ghost_table(GhostTable &G, int model, int count, const float *r
 // The records of launch_kolb_rays / launch_kolb_spectral (k == 1) -> n x p ghost records, sample-major.  pairs: p <= kGhostMaxPairs packed
 // pairs (host).  d_table: the camera's GhostTable on the device (RAYTRACED; not read otherwise).  d_lambda: n f32 (nm) or nullptr: the
 // d-line.  model: ZOIC_THINLENS (0), ZOIC_RAYTRACED (1) or ZOIC_LENS_NONE (2).  Nothing but d_out is written.
+// d_stacks: the camera's StackTable on the device where an interface has a stack (the stack-aware kernel), nullptr otherwise.
 int launch_ghost_rays(int model, const KolbTable &kolb, const GhostMedia &media, const BokehTables &bokeh, const GhostTable *d_table,
                       uint32_t p, const uint32_t *pairs, const float *d_samples, const float *d_lambda, const uint32_t *d_rng,
-                      uint64_t rayBase, uint64_t n, const RayRecord *rays, RayRecord *d_out, void *stream);
+                      uint64_t rayBase, uint64_t n, const RayRecord *rays, RayRecord *d_out, void *stream,
+                      const StackTable *d_stacks = nullptr);
 
 }  // namespace zoic

@@ -37,6 +37,7 @@
 #include <cstdint>
 
 #include "backward_spectral.hpp"
+#include "coating_stack.hpp"
 #include "splat.hpp"
 #include "traceback.hpp"
 #include "transmittance.hpp"
@@ -47,8 +48,9 @@ namespace zoic {
 
 // The rider: tb_trace's Tangents.  FP: `const FilmTable *` on the host, a pointer into the kernel-argument segment on the device.
 // interface() is called once per interface the ray refracts at, front to rear, so the rider counts them itself; the count is the same
-// in every lane that is still tracing.
-template <class FP>
+// in every lane that is still tracing.  KP: the coating policy (coating_stack.hpp): NoStacks, or a pointer to the camera's StackTable,
+// whose layers this ray, going front to rear, meets backwards.
+template <class FP, class KP = NoStacks>
 struct TbThroughput {
     const BwdMedium *med;
     FP film;
@@ -57,6 +59,7 @@ struct TbThroughput {
     float T;        // 1.0f before the first interface
     int j;          // the next interface, front to rear
     int count;
+    KP stacks;
 
     ZOIC_HD void line(float, float, float) {}
     ZOIC_HD void thin(const TraceBackTable &, float, float) {}
@@ -70,15 +73,15 @@ struct TbThroughput {
         nFront = n2;
         j = jj + 1;
         if (n1 == n2) return;
-        T = T * interface_transmittance(n1, n2, fabsf(cosi), sk, nc, lambda0, lambda);
+        T = T * coated_transmittance(stacks, i, false, n1, n2, fabsf(cosi), sk, nc, lambda0, lambda);
     }
     ZOIC_HD void sensor(const TraceBackTable &, float, float, float, float, float, float, float) {}
 };
 
 // the trace-back of one ray at its wavelength (nm) with its transmittance: returns the flag word, writes sx, sy and T
-template <class FP>
+template <class FP, class KP = NoStacks>
 ZOIC_HD uint32_t trace_back_ray_throughput(const TraceBackTable &T, const BackwardDispersion &D, FP film, float lambda, float ox, float oy,
-                                           float oz, float dx, float dy, float dz, float &sx, float &sy, float &t)
+                                           float oz, float dx, float dy, float dz, float &sx, float &sy, float &t, KP K = KP{})
 {
     t = 0.0f;
     if (!spectral_valid(lambda)) {
@@ -87,32 +90,36 @@ ZOIC_HD uint32_t trace_back_ray_throughput(const TraceBackTable &T, const Backwa
     }
     const float dl = spectral_dl(lambda);
     TbSpectral M{D.med, dl, 1.0f};
-    TbThroughput<FP> G{D.med, film, dl, lambda, 1.0f, 1.0f, 0, T.count};
+    TbThroughput<FP, KP> G{D.med, film, dl, lambda, 1.0f, 1.0f, 0, T.count, K};
     const uint32_t f = tb_trace(T, ox, oy, oz, dx, dy, dz, sx, sy, M, G);
     if ((f & kTbTraced) != 0u) t = G.T;
     return f;
 }
 
 // One splat's T: splat_of's box test, aim and ray (splat.hpp), then the trace above
-template <class FP>
+template <class FP, class KP = NoStacks>
 ZOIC_HD float splat_throughput(const TraceBackTable &T, const BackwardDispersion &D, FP film, float lambda, float z, float px, float py,
-                               float pz, float lox, float loy, float hix, float hiy, uint32_t count, uint32_t boxFlags, float u0, float u1)
+                               float pz, float lox, float loy, float hix, float hiy, uint32_t count, uint32_t boxFlags, float u0, float u1,
+                               KP K = KP{})
 {
     if (count == 0u || (boxFlags & kPbSome) == 0u) return 0.0f;
     const float ax = splat_aim(lox, hix, u0), ay = splat_aim(loy, hiy, u1);
     const float dx = px - ax, dy = py - ay, dz = pz - z;
     float sx, sy, t;
-    (void)trace_back_ray_throughput(T, D, film, lambda, px, py, pz, dx, dy, dz, sx, sy, t);
+    (void)trace_back_ray_throughput(T, D, film, lambda, px, py, pz, dx, dy, dz, sx, sy, t, K);
     return t;
 }
 
 // ---- launchers (traceback_throughput.hip) ----------------------------------------------------------------------------------------
 // d_rays = n 32-byte zoic_ray records (16-byte aligned); d_lambda = n f32 wavelengths (nm) or nullptr: the d-line; d_out = n floats;
-// d_screen = n x 2 floats (8-byte aligned) or nullptr; d_flags = n uint32 or nullptr.  Asynchronous on `stream`.
+// d_screen = n x 2 floats (8-byte aligned) or nullptr; d_flags = n uint32 or nullptr.  Asynchronous on `stream`.  d_stacks (both
+// launchers): the camera's StackTable on the device where an interface has a stack (the stack-aware kernels), nullptr otherwise.
 int launch_trace_back_throughput(const TraceBackTable &T, const BackwardDispersion &D, const FilmTable &F, const void *d_rays,
-                                 const float *d_lambda, uint64_t n, float *d_out, float *d_screen, uint32_t *d_flags, void *stream);
+                                 const float *d_lambda, uint64_t n, float *d_out, float *d_screen, uint32_t *d_flags, void *stream,
+                                 const StackTable *d_stacks = nullptr);
 // d_points, d_bounds, d_u as launch_splat_points; d_lambda = n f32 (one per point) or nullptr: the d-line; d_out = n x m floats.
 int launch_splat_throughput(const TraceBackTable &T, const BackwardDispersion &D, const FilmTable &F, const float *d_points,
-                            const void *d_bounds, const float *d_lambda, uint64_t n, uint32_t m, const float *d_u, float *d_out, void *stream);
+                            const void *d_bounds, const float *d_lambda, uint64_t n, uint32_t m, const float *d_u, float *d_out, void *stream,
+                            const StackTable *d_stacks = nullptr);
 
 }  // namespace zoic

@@ -9,8 +9,12 @@
 // dispersion table and the film table arrive by value and are read through the kernel-argument segment (device_pass.hpp kernarg_view,
 // spectral.hpp ZOIC_SPEC_PIN) with scalar loads at the wave-uniform interface index.  The n x k floats leave as coalesced stores:
 // directly for k == 1, through the wave's stage otherwise.
+// Multilayer coatings (coating_stack.hpp): a camera with a stack on any interface runs kolb_stack_loss_kernel, the same body under the
+// coating policy `const StackTable *` -- the camera's table in device memory, read with scalar loads at the same wave-uniform index.
+// A camera without stacks runs kolb_transmittance_kernel as before.
 #include <hip/hip_runtime.h>
 
+#include "coating_stack.hpp"
 #include "hero.hpp"
 #include "record_pass.hpp"
 #include "transmittance.hpp"
@@ -32,13 +36,12 @@ __device__ __forceinline__ auto kernarg_surfaces()
 __device__ __forceinline__ auto kernarg_spectral() { return kernarg_view<TransmittanceKernelArgs, SpectralTable>(offsetof(TransmittanceKernelArgs, W)); }
 __device__ __forceinline__ auto kernarg_film() { return kernarg_view<TransmittanceKernelArgs, FilmTable>(offsetof(TransmittanceKernelArgs, F)); }
 
-}  // namespace
-
-// budget: 0 scratch, 0 spills, <= 128 VGPRs (4 waves per SIMD)
-__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_transmittance_kernel(
-    const KolbTable T, const SpectralTable W, const FilmTable F, const BokehTables B, const float4 *__restrict__ samples,
-    const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays,
-    float *__restrict__ out, uint32_t k)
+// the one body of both Kolb kernels; KP: the coating policy.  (The stack-aware kernel's extra argument comes last: the offsets of
+// TransmittanceKernelArgs hold for both.)
+template <class KP>
+__device__ __forceinline__ void transmittance_pass(const KolbTable &T, const BokehTables &B, const float4 *__restrict__ samples,
+                                                   const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase,
+                                                   uint64_t n, const RayRecord *__restrict__ rays, float *__restrict__ out, uint32_t k, KP K)
 {
     __shared__ __align__(16) float2 lut[kLutEntries];
     __shared__ float stage[kPassBlock / 64][64 * kHeroMaxWavelengths];
@@ -66,13 +69,33 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4)))
             float t = 0.0f;
             if (__ballot(live) != 0ull && live) {
                 const float lambda = lambdas ? lambdas[row + j] : kLambdaD32;   // d_lambda == nullptr: the d-line
-                t = path_transmittance(kernarg_surfaces(), kernarg_spectral(), kernarg_film(), T.lensCount, lambda, o0, d0);
+                t = path_transmittance(kernarg_surfaces(), kernarg_spectral(), kernarg_film(), K, T.lensCount, lambda, o0, d0);
             }
             if (k == 1u) { if (have) out[i] = t; }
             else st[lane * k + j] = t;
         }
         if (k > 1u) staged_store(st, out + base * k, tile_valid(n, base), k);
     }
+}
+
+}  // namespace
+
+// budget: 0 scratch, 0 spills, <= 128 VGPRs (4 waves per SIMD)
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_transmittance_kernel(
+    const KolbTable T, const SpectralTable W, const FilmTable F, const BokehTables B, const float4 *__restrict__ samples,
+    const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays,
+    float *__restrict__ out, uint32_t k)
+{
+    transmittance_pass(T, B, samples, lambdas, rngStates, rayBase, n, rays, out, k, NoStacks{});
+}
+
+// the same with multilayer coatings; budget: the plain kernel's, and no LDS beyond its
+__global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(4))) void kolb_stack_loss_kernel(
+    const KolbTable T, const SpectralTable W, const FilmTable F, const BokehTables B, const float4 *__restrict__ samples,
+    const float *__restrict__ lambdas, const uint4 *__restrict__ rngStates, uint64_t rayBase, uint64_t n, const RayRecord *__restrict__ rays,
+    float *__restrict__ out, uint32_t k, const StackTable *__restrict__ stacks)
+{
+    transmittance_pass(T, B, samples, lambdas, rngStates, rayBase, n, rays, out, k, stacks);
 }
 
 // THINLENS: a thin lens has no interface; 1.0 where the record has weight and the wavelength is valid.  One record per lane.
@@ -88,10 +111,13 @@ __global__ __launch_bounds__(kPassBlock) void thin_transmittance_kernel(const fl
 
 int launch_ray_transmittance(int model, const KolbTable &kolb, const SpectralTable &spec, const FilmTable &film, const BokehTables &bokeh,
                              const float *d_samples, const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, uint32_t k,
-                             const RayRecord *rays, float *d_out, void *stream)
+                             const RayRecord *rays, float *d_out, void *stream, const StackTable *d_stacks)
 {
     if (n == 0) return 0;
     if (k == 0 || k > kHeroMaxWavelengths) return static_cast<int>(hipErrorInvalidValue);   // the stage holds 64 x kHeroMaxWavelengths floats
+    if (model == 1 && d_stacks)
+        return launch_pass(kolb_stack_loss_kernel, pass_grid(n), stream, kolb, spec, film, bokeh, reinterpret_cast<const float4 *>(d_samples),
+                           d_lambda, reinterpret_cast<const uint4 *>(d_rng), rayBase, n, rays, d_out, k, d_stacks);
     if (model == 1)
         return launch_pass(kolb_transmittance_kernel, pass_grid(n), stream, kolb, spec, film, bokeh, reinterpret_cast<const float4 *>(d_samples),
                            d_lambda, reinterpret_cast<const uint4 *>(d_rng), rayBase, n, rays, d_out, k);

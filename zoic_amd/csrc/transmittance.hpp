@@ -125,9 +125,11 @@ ZOIC_HD float path_transmittance(SP surf, WP W, FP F, int count, float lambda, V
 // ---- launcher (transmittance.hip) ----------------------------------------------------------------------------------------
 // The records of launch_kolb_rays / launch_kolb_spectral (k == 1) or launch_kolb_hero (k >= 2), n x k sample-major, -> n x k floats.
 // d_lambda: n x k f32 (nm), or nullptr with k == 1: the d-line.  model: ZOIC_THINLENS (0) or ZOIC_RAYTRACED (1).  Nothing but d_out is
-// written.
+// written.  d_stacks: the camera's StackTable (coating_stack.hpp) on the device where an interface has a multilayer stack (the
+// stack-aware kernel), nullptr otherwise.
+struct StackTable;
 int launch_ray_transmittance(int model, const KolbTable &kolb, const SpectralTable &spec, const FilmTable &film, const BokehTables &bokeh,
                              const float *d_samples, const float *d_lambda, const uint32_t *d_rng, uint64_t rayBase, uint64_t n, uint32_t k,
-                             const RayRecord *rays, float *d_out, void *stream);
+                             const RayRecord *rays, float *d_out, void *stream, const StackTable *d_stacks = nullptr);
 
 }  // namespace zoic
